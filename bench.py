@@ -10,15 +10,25 @@ push scatter-add (keys[i] = start + i, values U[-1,1) from seed 42): the configu
 of HBM roofline target is quoted on. With N GPUs (torchrun), the key space is
 RangePartitioner(N, N * 2^30) and every rank pushes its own dense range (cfg4a: clients own
 contiguous key ranges, no exchange step) -- weak scaling, no collective in the timed region.
-The default 1-GPU run also measures BASELINE.json configs[1] (2^28 keys, the extra key `cfg2_2p28`).
+A plain run sets up, warms up, times the K steps and prints the line; everything else it can measure or
+check sits behind --full: the post-run shard check (`check`), BASELINE.json configs[1] beside the
+default 1-GPU line (2^28 keys, the extra key `cfg2_2p28`), the CPU baselines (`cpu_baseline`) and the
+replayed PMC traffic and practical-floor figures. Without --full those keys are null or absent.
 
 Algorithmic bytes per record: 8 (key) + 8 (value) + 8 + 8 (shard read + write)
 = 32 B; value = all ranks' algorithmic bytes / max-over-ranks wall time of the K timed steps.
 The roofline figure uses the push kernels' own device time from HIP events carried on each launch
 on its stream (glint_prof_*); PMC HBM traffic comes from profiles/ when present.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--log2-keys 30]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR] [--log2-keys 30]
                     [--pattern dense|zipf|matrix|exchange|pull|rowpull] [--scaling weak|strong]
+
+--dump-outputs DIR writes, after the timed steps, what the timed path left its caller with as
+DIR/<name>.npy (float64): a push line's shard(s) as they stand after the last timed push (`shard`, or
+`shard0`, `shard1`, ... when the rank hosts several), a pull line's output buffer (`pulled`); at N > 1
+every rank writes its own, suffixed `_rank<r>`. At most 2^22 elements (32 MiB) in all: a larger output
+is sampled at fixed, seeded positions (ascending, repeats allowed). Keys, values and positions come
+from fixed seeds, so two runs with the same arguments push the same records and dump the same elements.
 
 --gpus N without torchrun starts N worker processes itself (one per GPU, before touching any GPU);
 under torchrun (WORLD_SIZE set) every process is one rank.
@@ -74,11 +84,17 @@ def parse():
                          "of 2^16 Zipf(1.0) rows (8200 B/row)")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak: 2^k keys per GPU (cfg4a); strong: one 2^k-key vector split over the GPUs")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU-baseline sample length")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed line: the post-run shard check, the cfg2 (2^28) leg of the default "
+                         "1-GPU run, the CPU baselines and the replayed PMC traffic / practical-floor figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float64, sampled above 2^22 "
+                         "elements)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: CPU-baseline sample length")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--no-north-star", action="store_true",
-                    help="skip the extra cfg2 (2^28) leg of the default 1-GPU run")
-    ap.add_argument("--no-check", action="store_true", help="skip the post-run shard check")
+                    help="--full without the extra cfg2 (2^28) leg of the default 1-GPU run")
+    ap.add_argument("--no-check", action="store_true", help="--full without the post-run shard check")
     ap.add_argument("--batches", type=int, default=1,
                     help="push patterns: K different batches of the same distribution, rotated per step")
     ap.add_argument("--parts-per-gpu", type=int, default=1,
@@ -225,10 +241,15 @@ def segment_sums(v, counts, chunk: int = 1 << 22):
     return torch.cat(out) if out else v[:0]
 
 
+DUMP_ELEMS = 1 << 22  # --dump-outputs: elements written per rank in all (32 MiB of float64)
+
+
 def run_line(ctx, pat: str, log2_keys: int, scaling: str, steps: int, warmup: int, check: bool,
-             mps: int = 1, nb: int = 1) -> dict:
+             mps: int = 1, nb: int = 1, replays: bool = True, dump: bool = False) -> dict:
     """Builds the workload of one bench line, times `steps` pushes (or pulls) after `warmup`, checks
-    the shard afterwards and returns the line's fields (without the CPU baseline)."""
+    the shard afterwards (`check`) and returns the line's fields (without the CPU baseline).
+    `replays`: the PMC traffic and practical-floor figures read from profiles/. `dump`: the line
+    carries `_outputs`, {name: float64 array}, what the last timed step left its caller with."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -459,6 +480,32 @@ def run_line(ctx, pat: str, log2_keys: int, scaling: str, steps: int, warmup: in
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
+    outputs = None
+    if dump:
+        # a push leaves the shard(s) updated, a pull fills `out`: pulled back through the pull path
+        # at every position, or at DUMP_ELEMS seeded positions (ascending, repeats allowed) when larger
+        srng = np.random.default_rng(4242)
+
+        def positions(total, budget):
+            if total <= budget:
+                return torch.arange(total, dtype=torch.int64, device=dev)
+            return torch.from_numpy(np.sort(srng.integers(0, total, budget))).to(dev)
+
+        sfx = f"_rank{rank}" if world > 1 else ""
+        outputs = {}
+        if not push:
+            flat = out.reshape(-1)
+            outputs["pulled" + sfx] = flat[positions(flat.numel(), DUMP_ELEMS)]
+        else:
+            per = DUMP_ELEMS // len(shards)
+            for j, (sh, p) in enumerate(zip(shards, my_parts)):
+                name = (f"shard{j}" if len(shards) > 1 else "shard") + sfx
+                if mat:  # whole rows
+                    outputs[name] = sh.getRows(positions(p.size, max(1, per // cols_n)) + p.start).reshape(-1)
+                else:
+                    outputs[name] = sh.get(positions(p.size, per) + p.start)
+        outputs = {k: v.to(torch.float64).cpu().numpy() for k, v in outputs.items()}
+
     def kernel_avg(kid):
         """Device time of one kernel kind per step (a large push runs its check and apply as one
         launch per window of records: the launches of a step are summed) and its launch count."""
@@ -583,7 +630,7 @@ def run_line(ctx, pat: str, log2_keys: int, scaling: str, steps: int, warmup: in
     if overlap:  # the local shards' pushes run on concurrent streams: their summed device time exceeds the
         kern_ms = dt / steps * 1e3  # step, so the roofline is taken over the step's wall time instead
     achieved = bytes_per_step / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0
-    traffic, traffic_src, traffic_recs = pmc_traffic(tag)
+    traffic, traffic_src, traffic_recs = pmc_traffic(tag) if replays else (None, None, None)
     if traffic is not None and traffic_recs and push:
         # the summary is per profiled shard push: scaled to the records this step's pushes take (the
         # 8-partition exchange line's step is eight shard pushes of ~2^23 records each)
@@ -624,13 +671,15 @@ def run_line(ctx, pat: str, log2_keys: int, scaling: str, steps: int, warmup: in
         line["batches"] = {"k": len(batches), "rotation": "step s pushes batch s % K",
                            "distinct_keys_per_batch": [bt[3] for bt in batches] if not exch else None,
                            "check": "every batch replayed (value x times pushed) into one fp64 segment sum"}
-    floor = sparse_floor(tag + ("_slab" if slab is not None else ""), dt / steps * 1e3)
+    floor = sparse_floor(tag + ("_slab" if slab is not None else ""), dt / steps * 1e3) if replays else None
     if floor is not None:
         line["practical_floor"] = floor
     for sh in shards:
         sh.destroy()
     if slab is not None:  # after its views
         slab.destroy()
+    if outputs is not None:
+        line["_outputs"] = outputs
     return line
 
 
@@ -692,19 +741,25 @@ def main():
     log2_keys = args.log2_keys if args.log2_keys is not None else (30 if headline else 28)
     if args.batches > 1 and args.pattern not in ("dense", "zipf", "matrix", "exchange"):
         raise SystemExit("--batches applies to the push patterns")
-    line = run_line(ctx, args.pattern, log2_keys, args.scaling, args.steps, args.warmup, not args.no_check,
-                    args.parts_per_gpu, max(1, args.batches))
+    check = args.full and not args.no_check
+    line = run_line(ctx, args.pattern, log2_keys, args.scaling, args.steps, args.warmup, check,
+                    args.parts_per_gpu, max(1, args.batches), replays=args.full, dump=bool(args.dump_outputs))
+    if args.dump_outputs:  # every rank writes its own arrays
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in line.pop("_outputs").items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
     if world > 1:
         line["world_size"] = dist.get_world_size()
         line["devices"] = rank_devices(dev, backend, local_pinned="GLINT_BENCH_DEVICE" in os.environ)
     # BASELINE.json configs[1] (cfg2: 2^28 keys) beside the north-star line, with its own roofline and check
-    if world == 1 and headline and not args.no_north_star:
+    if args.full and world == 1 and headline and not args.no_north_star:
         torch.cuda.empty_cache()
-        c2 = run_line(ctx, "dense", 28, "weak", args.steps, args.warmup, not args.no_check)
+        c2 = run_line(ctx, "dense", 28, "weak", args.steps, args.warmup, check)
         line["cfg2_2p28"] = {k: c2[k] for k in ("value", "unit", "ms_per_step", "steps", "warmup",
                                                 "pct_hbm_peak_per_gpu", "roofline", "check")}
         line["cfg2_2p28"]["workload"] = c2["config"]["workload"]
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(log2_keys, args.cpu_seconds)
     if rank == 0:
         print(json.dumps(line), flush=True)

@@ -106,11 +106,13 @@ def test_route_int_edge_partitioner(gpu):
         np.testing.assert_array_equal(counts, want)
 
 
-def _bench(args, **env):
+def _bench(args, full=True, **env):
+    """One bench.py run; with --full by default: these tests are about the post-run check, the cfg2
+    leg and the other figures a plain run leaves out."""
     e = dict(os.environ, **env)
     e.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py")] + args, capture_output=True, text=True,
-                       timeout=300, env=e, cwd=str(ROOT))
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py")] + (["--full"] if full else []) + args,
+                       capture_output=True, text=True, timeout=300, env=e, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout  # rank 0 alone prints
@@ -157,6 +159,37 @@ def test_bench_default_line_is_the_north_star(gpu):
     d = _bench(["--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
     assert "2^30" in d["config"]["workload"] and d["config"]["keys_per_gpu"] == 1 << 30 and d["check"] is True
     assert d["cfg2_2p28"]["check"] is True and "2^28" in d["cfg2_2p28"]["workload"]
+
+
+@pytest.mark.parametrize("log2_keys", [22, 23])
+def test_bench_plain_run_dumps_its_outputs(gpu, tmp_path, log2_keys):
+    """Without --full the run times its steps and nothing else (no check, no cfg2 leg, no CPU
+    baseline, no replayed figures), and --dump-outputs writes the shard as the last timed push left
+    it: every element at 2^22 keys, 2^22 seeded positions of it at 2^23. The dense push is ordered,
+    so the dump equals the W + K additions of the seeded values bit for bit."""
+    import torch
+    steps, warmup = 3, 2
+    d = _bench(["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--log2-keys", str(log2_keys),
+                "--dump-outputs", str(tmp_path / "out")], full=False)
+    assert d["steps"] == steps and d["warmup"] == warmup and d["value"] > 0 and d["dtype"] == "f64"
+    assert d["ms_per_step"] > 0 and d["unit"] == "GB/s" and d["higher_is_better"] is True
+    assert d["check"] is None and "cpu_baseline" not in d and "cfg2_2p28" not in d and "_outputs" not in d
+    assert d["roofline"]["traffic"] is None and d["roofline"]["achieved"] > 0
+    assert sorted(f.name for f in (tmp_path / "out").iterdir()) == ["shard.npy"]
+    got = np.load(tmp_path / "out" / "shard.npy")
+    n = 1 << log2_keys
+    dev = torch.device("cuda", gpu)
+    g = torch.Generator(device=dev)
+    g.manual_seed(42)
+    vals = torch.rand(n, dtype=torch.float64, device=dev, generator=g) * 2 - 1
+    acc = torch.zeros_like(vals)
+    for _ in range(warmup + steps):
+        acc += vals
+    want = acc.cpu().numpy()
+    if n > 1 << 22:
+        want = want[np.sort(np.random.default_rng(4242).integers(0, n, 1 << 22))]
+    assert got.dtype == np.float64 and got.shape == (1 << 22,)
+    np.testing.assert_array_equal(got, want)
 
 
 @pytest.mark.parametrize("n", [1, 7, 100_001, 1 << 20])

@@ -1,6 +1,6 @@
 set -o pipefail
 mkdir -p gpurun_out/r05k
-B="python bench.py --no-cpu-baseline --no-north-star --pattern exchange --parts-per-gpu 8"
+B="python bench.py --full --no-cpu-baseline --no-north-star --pattern exchange --parts-per-gpu 8"
 for r in 1 2; do
   GLINT_SYNC_FLUSH=1 timeout -k 10 200 $B > gpurun_out/r05k/flush_$r.json 2> gpurun_out/r05k/flush_$r.err || exit 1
   GLINT_SYNC_FLUSH=0 timeout -k 10 200 $B > gpurun_out/r05k/noflush_$r.json 2> gpurun_out/r05k/noflush_$r.err || exit 1

@@ -41,7 +41,7 @@ kstats() {  # kstats <name> <seconds> <bench args...>: kernel stats CSV of one b
   shift 2
   echo "[$(date +%T)] kstats $name" >&2
   (cd /tmp && timeout -k 10 $secs rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$name -o run \
-     -- python3 $R/bench.py --no-cpu-baseline --no-north-star "$@" > $OUT/prof_$name.log 2>&1) || { tail -30 $OUT/prof_$name.log >&2; exit 1; }
+     -- python3 $R/bench.py --full --no-cpu-baseline --no-north-star "$@" > $OUT/prof_$name.log 2>&1) || { tail -30 $OUT/prof_$name.log >&2; exit 1; }
   find /tmp/prof_$name -name "*kernel_stats.csv" -exec cp {} $OUT/kstats_$name.csv \;
 }
 pmc() {  # pmc <name> <bench args...>: FETCH_SIZE and WRITE_SIZE in two separate passes
@@ -62,11 +62,11 @@ for s in ${STAGES:-tests bench}; do
       step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
       ;;
     bench)
-      step bench_default 400 python3 bench.py
+      step bench_default 400 python3 bench.py --full
       for pat in zipf matrix exchange pull rowpull; do
-        step bench_$pat 300 python3 bench.py --no-cpu-baseline --pattern $pat
+        step bench_$pat 300 python3 bench.py --full --no-cpu-baseline --pattern $pat
       done
-      step bench_exchange_mps8 300 python3 bench.py --no-cpu-baseline --pattern exchange --parts-per-gpu 8
+      step bench_exchange_mps8 300 python3 bench.py --full --no-cpu-baseline --pattern exchange --parts-per-gpu 8
       ;;
     prof2p30)
       kstats dense_2p28 300 --log2-keys 28
@@ -110,7 +110,7 @@ for s in ${STAGES:-tests bench}; do
       ;;
     quickbench)  # the binned lines only, no CPU baseline
       for pat in ${PATTERNS:-matrix zipf exchange}; do
-        step qb_$pat 300 python3 bench.py --no-cpu-baseline --no-north-star --pattern $pat
+        step qb_$pat 300 python3 bench.py --full --no-cpu-baseline --no-north-star --pattern $pat
       done
       ;;
     phases)  # phase clocks of the binned kernels (tools/bin_phases.py, a -DGLINT_BIN_PROF build)
@@ -152,8 +152,8 @@ for s in ${STAGES:-tests bench}; do
       ;;
     ab)  # the binned patterns: the previous build's library (GLINT_GPU_LIB=$AB_LIB) and this one, back to back
       for pat in ${PATTERNS:-zipf matrix exchange}; do
-        step ab_old_$pat 300 env GLINT_GPU_LIB=$AB_LIB python3 bench.py --no-cpu-baseline --pattern $pat
-        step ab_new_$pat 300 python3 bench.py --no-cpu-baseline --pattern $pat
+        step ab_old_$pat 300 env GLINT_GPU_LIB=$AB_LIB python3 bench.py --full --no-cpu-baseline --pattern $pat
+        step ab_new_$pat 300 python3 bench.py --full --no-cpu-baseline --pattern $pat
       done
       ;;
     abn)  # LIBS="tag=path ...": each binned pattern on each library, ROUNDS rounds interleaved (one box)
@@ -163,7 +163,7 @@ for s in ${STAGES:-tests bench}; do
             spec=${lv#*=}
             extra=""
             case $spec in *,*) extra=$(echo ${spec#*,} | tr ',' ' ') ;; esac
-            step ab_${lv%%=*}_${pat}_$r 300 env GLINT_GPU_LIB=${spec%%,*} $extra python3 bench.py --no-cpu-baseline --no-north-star --pattern $pat
+            step ab_${lv%%=*}_${pat}_$r 300 env GLINT_GPU_LIB=${spec%%,*} $extra python3 bench.py --full --no-cpu-baseline --no-north-star --pattern $pat
           done
         done
       done
