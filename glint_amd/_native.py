@@ -19,6 +19,7 @@ GLINT_K_PUSH_APPLY, GLINT_K_PUSH_SCATTER, GLINT_K_VEC_PULL, GLINT_K_MAT_PULL, GL
 GLINT_K_PUSH_CHECK = 5
 GLINT_K_PUSH_BINNED = 6
 GLINT_K_PUSH_ORDERED = 7
+GLINT_K_PUSH_ROWS = 8
 GLINT_ROUTE_RANGE, GLINT_ROUTE_CYCLIC = 0, 1
 GLINT_RING_SLOTS, GLINT_ZERO_COPY_MAX = 16, 4096
 
@@ -41,6 +42,8 @@ SIGNATURES = {
     "glint_mat_push": (_I, [_P, _P, _P, _P, _I64, _I]),
     "glint_mat_pull": (_I, [_P, _P, _P, _P, _I64]),
     "glint_mat_pull_rows": (_I, [_P, _P, _P, _I64]),
+    "glint_mat_push_rows": (_I, [_P, _P, _P, _I64, _I]),
+    "glint_mat_push_rows_dev": (_I, [_P, _P, _P, _I64, _I, _P]),
     "glint_shard_last_error": (_I, [_P, C.POINTER(_I64)]),
     "glint_vec_push_dev": (_I, [_P, _P, _P, _I64, _I, _P]),
     "glint_vec_push_dev_gated": (_I, [_P, _P, _P, _I64, _I, _P, _P]),

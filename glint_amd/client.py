@@ -9,6 +9,8 @@ Mirrors the reference's client factory and asynchronous models, minus the Akka t
   bucketed by partition preserving their order inside each bucket (``mapPartitions``, :96-98),
   one shard call per partition, and pulled values scattered back to the caller's order (:61-79).
 * ``BigMatrix.push/pull`` -- AsyncBigMatrix (AsyncBigMatrix.scala:53-170), including the row pull.
+* ``BigMatrix.pushRows`` -- an extension with no AsyncBigMatrix counterpart: the row pull's write
+  side, whole rows added without expanding them into (row, col, value) triplets.
 
 Out-of-range keys raise ``IndexOutOfBoundsException`` before any shard is touched, as the
 reference's ``partitioner.partition`` does synchronously inside ``mapPartitions``.
@@ -98,6 +100,23 @@ class BigMatrix:
             idx = order[off[p]:off[p + 1]]
             if idx.size:
                 sh.update(rows[idx], cols[idx], values[idx], deterministic=deterministic)
+        return True
+
+    def pushRows(self, rows, values, deterministic: bool = False) -> bool:
+        """Whole rows: row rows[i] += values[i] (an (n, cols) array, or flat), in the caller's order
+        -- ``push`` of the triplets (rows[i], c, values[i][c]) without expanding them. Bucketed by
+        partition as ``push``; one PartialMatrix.updateRows per non-empty partition."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        values = np.ascontiguousarray(values, dtype=self.shards[0].np_dtype)
+        if values.size != rows.size * self.cols:
+            raise ValueError(f"values: {values.size} elements, expected {rows.size} rows x {self.cols} columns")
+        values = values.reshape(rows.size, self.cols)
+        owner = self.partitioner.partition_indices(rows)
+        order, off = bucket(owner, len(self.shards))
+        for p, sh in enumerate(self.shards):
+            idx = order[off[p]:off[p + 1]]
+            if idx.size:
+                sh.updateRows(rows[idx], values[idx], deterministic=deterministic)
         return True
 
     def pull(self, rows, cols=None) -> np.ndarray:

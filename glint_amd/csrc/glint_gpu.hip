@@ -1192,6 +1192,16 @@ void* host_dev_ptr(const void* p, size_t bytes, size_t align, HostHold* hold = n
 int ring_flush_locked(glint_shard* s);
 int ring_retire_through(glint_shard* s, u64 t);
 
+// argument checks of glint_mat_push_rows / _dev: a matrix shard, sane sizes, only the two order flags
+// (no validating or gated row push), 32-bit record indices for the sort
+inline int push_rows_args(const glint_shard* s, const void* rows, const void* vals, int64_t n, int flags) {
+  if (!s || s->part.cols == 0 || n < 0) return GLINT_EINVAL;
+  if (n > 0 && (!rows || !vals)) return GLINT_EINVAL;
+  if (flags & ~(GLINT_PUSH_DETERMINISTIC | GLINT_PUSH_UNORDERED)) return GLINT_EINVAL;
+  if (n >= ((i64)1 << 32) - kSortTile) return GLINT_EINVAL;
+  return GLINT_OK;
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -1201,7 +1211,7 @@ std::atomic<unsigned> g_env_gen{1};
 
 extern "C" {
 
-int glint_version(void) { return 100; }
+int glint_version(void) { return 200; }  // 0.2.0: glint_mat_push_rows / _dev, GLINT_K_PUSH_ROWS
 
 int glint_reload_env(void) {
   g_env_gen.fetch_add(1, std::memory_order_acq_rel);
@@ -1597,6 +1607,16 @@ int glint_mat_pull_rows_dev(glint_shard_t s, const int64_t* rows, void* out, int
   DeviceGuard g(s->device);
   if (int rc = dev_order_after_host(s, (hipStream_t)stream)) return rc;
   GLINT_DISPATCH(s->dtype, launch_mat_pull_rows, s, (const i64*)rows, out, n, pick(s, stream));
+}
+
+int glint_mat_push_rows_dev(glint_shard_t s, const int64_t* rows, const void* vals, int64_t n, int flags,
+                            void* stream) {
+  if (int rc = push_rows_args(s, rows, vals, n, flags)) return rc;
+  if (n == 0) return GLINT_OK;
+  ShardLock lk(s);
+  DeviceGuard g(s->device);
+  if (int rc = dev_order_after_host(s, (hipStream_t)stream)) return rc;
+  GLINT_DISPATCH(s->dtype, push_rows, s, (const i64*)rows, vals, n, flags, pick(s, stream));
 }
 
 }  // extern "C"
@@ -2417,6 +2437,33 @@ int host_pull(glint_shard* s, int kind, const int64_t* keys, const int32_t* cols
   return finish(s);
 }
 
+// glint_mat_push_rows: every row is checked before anything is enqueued (a rejected message applies
+// nothing, as host_push's ring messages), then the two sections are staged and the push runs on the
+// shard's stream in message order (kPushHostSequential).
+int host_push_rows(glint_shard* s, const int64_t* rows, const void* vals, int64_t n, int flags) {
+  ShardLock lk(s);
+  DeviceGuard g(s->device);
+  int rc = refuse_slab(s);
+  if (rc == GLINT_OK) rc = order_after_dev(s);
+  if (rc == GLINT_OK) rc = ring_flush_locked(s);
+  if (rc == GLINT_OK) rc = reject_if_bad(s, rows, nullptr, n);
+  if (rc) return rc;
+  Staged st;
+  const void* src[2] = {rows, vals};
+  size_t bytes[2] = {(size_t)n * 8, (size_t)n * (size_t)s->part.cols * s->vsize};
+  rc = stage(s, src, bytes, 2, st, 0, nullptr);
+  if (rc) return rc;
+  HostCall hc(s);  // this call's rejected records are its own (d_err_host, read by finish)
+  rc = [&]() -> int {
+    GLINT_DISPATCH(s->dtype, push_rows, s, (const i64*)st.p[0], st.p[1], n, flags | kPushHostSequential, s->stream);
+  }();
+  if (rc) {
+    (void)hipStreamSynchronize(s->stream);  // the staging buffers stay busy until the stream drains
+    return rc;
+  }
+  return finish(s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2445,6 +2492,12 @@ int glint_mat_pull(glint_shard_t s, const int64_t* rows, const int32_t* cols, vo
 int glint_mat_pull_rows(glint_shard_t s, const int64_t* rows, void* out, int64_t n) {
   if (!s) return GLINT_EINVAL;
   return host_pull(s, 2, rows, nullptr, out, n);
+}
+
+int glint_mat_push_rows(glint_shard_t s, const int64_t* rows, const void* vals, int64_t n, int flags) {
+  if (int rc = push_rows_args(s, rows, vals, n, flags)) return rc;
+  if (n == 0) return GLINT_OK;
+  return host_push_rows(s, rows, vals, n, flags);
 }
 
 // RequestSerializer.fromBinary (RequestSerializer.scala:59-130) for the push messages, applied

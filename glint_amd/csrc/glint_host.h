@@ -481,4 +481,14 @@ int launch_validate_gate_binned(LaunchCtl* ctl, u64* gate, void* bc, u32* T, u32
 // one-launch order-preserving push (glint_ordered.hip): n <= kOrderedMax, elems < 2^32
 template <typename V, bool MAT>
 int push_ordered(glint_shard* s, const PushArgs<V>& a, hipStream_t st);
+// the stable LSD radix sort of glint_sort.hip (instantiated there for the row push's u32 pairs): m
+// pairs by the low end_bit bits of the key, in tiles of kSortTile keys; hist and offs hold 256 words per
+// tile, tot 256 words; *where = which of the two buffer pairs holds the result
+constexpr int kSortTile = 2048;
+template <typename K, typename V>
+int rs_sort(K* k0, V* v0, K* k1, V* v1, i64 m, int end_bit, u32* hist, u32* offs, u32* tot, hipStream_t st,
+            int* where);
+// whole-row matrix push (glint_rows.hip), instantiated for V in {int, long long, float, double}
+template <typename V>
+int push_rows(glint_shard* s, const i64* rows, const void* vals, i64 n, int flags, hipStream_t st);
 }  // namespace glint

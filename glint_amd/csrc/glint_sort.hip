@@ -374,6 +374,9 @@ int rs_sort(K* k0, V* v0, K* k1, V* v1, i64 m, int end_bit, u32* hist, u32* offs
   *where = cur;
   return GLINT_OK;
 }
+static_assert(kSTile == kSortTile, "callers size the sort's scratch by kSortTile");
+// the row push (glint_rows.hip) sorts (local row, record index) pairs
+template int rs_sort<u32, u32>(u32*, u32*, u32*, u32*, i64, int, u32*, u32*, u32*, hipStream_t, int*);
 
 // ---- hot chains ---------------------------------------------------------------------------------
 // An element with hundreds of thousands of records is a fold chain of that many dependent adds (the

@@ -267,7 +267,7 @@ class _Shard:
         import torch
         return getattr(torch, np.dtype(self.np_dtype).name)
 
-    def _check_dev(self, n: int, keys, cols=None, values=None, out=None, out_elems=None) -> None:
+    def _check_dev(self, n: int, keys, cols=None, values=None, out=None, out_elems=None, value_elems=None) -> None:
         """Device-resident arguments: every tensor on the shard's GPU, contiguous, of the dtype the
         kernels read (keys/rows int64, cols int32, values/out the shard's type) and long enough --
         the kernels take raw pointers, so a mismatch would read or write past a buffer."""
@@ -276,7 +276,7 @@ class _Shard:
         if cols is not None:
             spec.append(("cols", cols, torch.int32, n))
         if values is not None:
-            spec.append(("values", values, self.torch_dtype, n))
+            spec.append(("values", values, self.torch_dtype, n if value_elems is None else value_elems))
         if out is not None:
             spec.append(("out", out, self.torch_dtype, n if out_elems is None else out_elems))
         for name, t, dt, want in spec:
@@ -411,6 +411,30 @@ class PartialMatrix(_Shard):
             raise ValueError("rows, cols and values differ in length")
         check(self.lib.glint_mat_push(self.handle, r.ctypes.data, c.ctypes.data, v.ctypes.data, r.size, flags),
               self.handle)
+        return True
+
+    def updateRows(self, rows, values, deterministic: bool = False, sync: bool = True,
+                   unordered: bool = False) -> bool:
+        """The write counterpart of getRows (an extension; the reference has no such message):
+        PartialMatrix.update applied to the triplets (rows[i], c, values[i][c]), for i in order and c
+        in [0, cols) inside each i. ``values`` is (n, cols) or flat, dense row-major. Host arrays keep
+        the push order for Float/Double unless ``unordered``; device tensors keep it with
+        ``deterministic`` (a row that occurs once is bit-exact either way)."""
+        flags = _flags(deterministic, unordered)
+        if _is_torch_cuda(rows):
+            n = rows.numel()
+            self._check_dev(n, rows, values=values, value_elems=n * self.cols)
+            rc = self.lib.glint_mat_push_rows_dev(self.handle, rows.data_ptr(), values.data_ptr(), n, flags,
+                                                  self._stream_of(rows))
+            check(rc, self.handle)
+            if sync:
+                self.sync(self._stream_of(rows))
+            return True
+        r = _host(rows, np.int64).reshape(-1)
+        v = _host(values, self.np_dtype).reshape(-1)
+        if v.size != r.size * self.cols:
+            raise ValueError(f"values: {v.size} elements, expected {r.size} rows x {self.cols} columns")
+        check(self.lib.glint_mat_push_rows(self.handle, r.ctypes.data, v.ctypes.data, r.size, flags), self.handle)
         return True
 
     def get(self, rows, cols, out=None, sync: bool = True):

@@ -147,6 +147,16 @@ int glint_mat_pull(glint_shard_t shard, const int64_t* rows, const int32_t* cols
  * (n x cols) the way ResponseSerializer sends ResponseRows* (ResponseSerializer.scala:52-61). */
 int glint_mat_pull_rows(glint_shard_t shard, const int64_t* rows, void* out, int64_t n);
 
+/* The write counterpart of glint_mat_pull_rows (an extension: the reference has no row-push
+ * message). PartialMatrix.update (PartialMatrix.scala:74-83) over whole rows: for i in order, for c in
+ * [0, cols): data[l(rows[i])][c] += vals[i*cols + c].
+ * vals: n x cols values of the shard's type, dense row-major (NO pitch).
+ * Matrix shards only; n < 2^32 - 2048; GLINT_PUSH_VALIDATE or an unknown flag is GLINT_EINVAL. Every
+ * row is checked before anything is applied: on a row outside the partition nothing is applied
+ * (GLINT_EOUTOFRANGE, the record's index in glint_shard_last_error). Float/Double sums of repeated rows
+ * keep the push order, bit for bit the sequential loop, unless GLINT_PUSH_UNORDERED is given. */
+int glint_mat_push_rows(glint_shard_t shard, const int64_t* rows, const void* vals, int64_t n, int flags);
+
 /* After GLINT_EOUTOFRANGE: index (within the failing call) of the first rejected record. */
 int glint_shard_last_error(glint_shard_t shard, int64_t* first_bad_record);
 
@@ -163,6 +173,12 @@ int glint_mat_push_dev(glint_shard_t shard, const int64_t* rows, const int32_t* 
 int glint_mat_pull_dev(glint_shard_t shard, const int64_t* rows, const int32_t* cols, void* out,
                        int64_t n, void* stream);
 int glint_mat_pull_rows_dev(glint_shard_t shard, const int64_t* rows, void* out, int64_t n,
+                            void* stream);
+/* glint_mat_push_rows, device-resident: a row outside the partition is skipped and reported by
+ * glint_shard_sync (the lowest such record index); the other rows are applied. Int/Long sums are
+ * exact. Float/Double: a row that occurs once in the push is bit-exact; sums of repeated rows keep the
+ * push order with GLINT_PUSH_DETERMINISTIC, else long lists may be split and added unordered. */
+int glint_mat_push_rows_dev(glint_shard_t shard, const int64_t* rows, const void* vals, int64_t n, int flags,
                             void* stream);
 
 /* glint_vec_push_dev / glint_mat_push_dev behind a device-side gate: the push is enqueued at once,
@@ -338,7 +354,8 @@ enum glint_kernel_id {
   GLINT_K_PUSH_CHECK = 5,   /* order / affinity check over the keys in front of push_apply */
   GLINT_K_PUSH_BINNED = 6,  /* the binned unordered-push pipeline (count, partition, apply) */
   GLINT_K_PUSH_ORDERED = 7, /* the order-preserving push of message-sized pushes (one launch) */
-  GLINT_K_COUNT = 8
+  GLINT_K_PUSH_ROWS = 8,    /* the per-destination fold of a whole-row push (glint_mat_push_rows*) */
+  GLINT_K_COUNT = 9
 };
 int glint_prof_enable(glint_shard_t shard, int on);
 int glint_prof_read(glint_shard_t shard, int kernel_id, double* total_ms, int64_t* launches);
