@@ -140,6 +140,37 @@ class BigMatrix:
                 out[idx] = sh.get(rows[idx], cols[idx])
         return out
 
+    def pullSparse(self, rows):
+        """pull(rows) with only the non-zero elements (an extension): a CSR triple ``(indptr, cols,
+        values)`` over the requested rows in the caller's order -- ``indptr`` n + 1 int64, request i's
+        entries ``cols[indptr[i]:indptr[i+1]]`` (int32, ascending) with their ``values``. Bucketed by
+        partition as ``pull``; one PartialMatrix.getRowsSparse per non-empty partition, and the partial
+        triples merged without a Python loop over rows."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        owner = self.partitioner.partition_indices(rows)
+        order, off = bucket(owner, len(self.shards))
+        n = rows.size
+        counts = np.zeros(n, dtype=np.int64)  # entries per request, caller's order
+        src0 = np.zeros(n, dtype=np.int64)    # where a request's entries start in the concatenated partials
+        part_cols, part_vals, base = [], [], 0
+        for p, sh in enumerate(self.shards):
+            idx = order[off[p]:off[p + 1]]
+            if idx.size:
+                ip, c, v = sh.getRowsSparse(rows[idx])
+                ip = np.asarray(ip, dtype=np.int64)
+                counts[idx] = np.diff(ip)
+                src0[idx] = base + ip[:-1]
+                part_cols.append(np.asarray(c, dtype=np.int32))
+                part_vals.append(np.asarray(v, dtype=self.shards[0].np_dtype))
+                base += int(ip[-1])
+        indptr = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(counts, out=indptr[1:])
+        if not base:
+            return indptr, np.zeros(0, np.int32), np.zeros(0, self.shards[0].np_dtype)
+        # entry e of the answer belongs to request i = its row; it is entry e - indptr[i] of that request
+        take = np.repeat(src0 - indptr[:-1], counts) + np.arange(base, dtype=np.int64)
+        return indptr, np.concatenate(part_cols)[take], np.concatenate(part_vals)[take]
+
     def destroy(self) -> bool:
         for sh in self.shards:
             sh.destroy()

@@ -1202,6 +1202,17 @@ inline int push_rows_args(const glint_shard* s, const void* rows, const void* va
   return GLINT_OK;
 }
 
+// argument checks of glint_mat_pull_rows_sparse / _dev: a matrix shard, 31-bit request count, outputs
+// present unless the call only counts
+inline int pull_sparse_args(const glint_shard* s, const void* rows, int64_t n, const void* row_ptr,
+                            const void* out_cols, const void* out_vals, int64_t cap) {
+  if (!s || s->part.cols == 0) return GLINT_EINVAL;
+  if (n < 0 || n >= ((i64)1 << 31) || cap < 0) return GLINT_EINVAL;
+  if (!row_ptr || (n > 0 && !rows)) return GLINT_EINVAL;
+  if (cap > 0 && (!out_cols || !out_vals)) return GLINT_EINVAL;
+  return GLINT_OK;
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -1211,7 +1222,7 @@ std::atomic<unsigned> g_env_gen{1};
 
 extern "C" {
 
-int glint_version(void) { return 200; }  // 0.2.0: glint_mat_push_rows / _dev, GLINT_K_PUSH_ROWS
+int glint_version(void) { return 300; }  // 0.3.0: glint_mat_pull_rows_sparse / _dev, GLINT_K_PULL_ROWS_SPARSE
 
 int glint_reload_env(void) {
   g_env_gen.fetch_add(1, std::memory_order_acq_rel);
@@ -1617,6 +1628,18 @@ int glint_mat_push_rows_dev(glint_shard_t s, const int64_t* rows, const void* va
   DeviceGuard g(s->device);
   if (int rc = dev_order_after_host(s, (hipStream_t)stream)) return rc;
   GLINT_DISPATCH(s->dtype, push_rows, s, (const i64*)rows, vals, n, flags, pick(s, stream));
+}
+
+int glint_mat_pull_rows_sparse_dev(glint_shard_t s, const int64_t* rows, int64_t n, int64_t* row_ptr,
+                                   int32_t* out_cols, void* out_vals, int64_t cap, void* stream) {
+  if (int rc = pull_sparse_args(s, rows, n, row_ptr, out_cols, out_vals, cap)) return rc;
+  ShardLock lk(s);
+  DeviceGuard g(s->device);
+  if (int rc = dev_order_after_host(s, (hipStream_t)stream)) return rc;
+  hipStream_t st = pick(s, stream);
+  int rc = [&]() -> int { GLINT_DISPATCH(s->dtype, sparse_count_scan, s, (const i64*)rows, n, (i64*)row_ptr, st); }();
+  if (rc) return rc;
+  GLINT_DISPATCH(s->dtype, sparse_emit, s, (const i64*)rows, n, (const i64*)row_ptr, out_cols, out_vals, cap, st);
 }
 
 }  // extern "C"
@@ -2464,6 +2487,60 @@ int host_push_rows(glint_shard* s, const int64_t* rows, const void* vals, int64_
   return finish(s);
 }
 
+// glint_mat_pull_rows_sparse: the rows are checked and staged, the count and its scan run, and the host
+// reads row_ptr -- the one thing it cannot size beforehand is the answer. The emit then writes into
+// device buffers of min(nnz, cap) entries (the shard's deterministic-path scratch: the scan is done
+// with it by then), and only those come back: (n + 1) * 8 + min(nnz, cap) * (4 + vsize) bytes.
+int host_pull_rows_sparse(glint_shard* s, const int64_t* rows, int64_t n, int64_t* row_ptr, int32_t* out_cols,
+                          void* out_vals, int64_t cap, int64_t* nnz) {
+  ShardLock lk(s);
+  DeviceGuard g(s->device);
+  int rc = refuse_slab(s);
+  if (rc == GLINT_OK) rc = order_after_dev(s);
+  if (rc == GLINT_OK) rc = ring_flush_locked(s);
+  if (rc == GLINT_OK) rc = reject_if_bad(s, rows, nullptr, n);
+  if (rc) return rc;
+  if (n == 0) {
+    row_ptr[0] = 0;
+    if (nnz) *nnz = 0;
+    return GLINT_OK;
+  }
+  Staged st;
+  const void* src[1] = {rows};
+  size_t bytes[1] = {(size_t)n * 8};
+  char* d_ptr = nullptr;
+  rc = stage(s, src, bytes, 1, st, (size_t)(n + 1) * 8, &d_ptr);
+  if (rc) return rc;
+  HostCall hc(s);  // (every row was checked: nothing is recorded)
+  const i64* d_rows = (const i64*)st.p[0];
+  rc = [&]() -> int { GLINT_DISPATCH(s->dtype, sparse_count_scan, s, d_rows, n, (i64*)d_ptr, s->stream); }();
+  if (rc) {
+    (void)hipStreamSynchronize(s->stream);  // the staging buffers stay busy until the stream drains
+    return rc;
+  }
+  HIPCHK(hipMemcpyAsync(row_ptr, d_ptr, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  const i64 total = row_ptr[n];
+  if (nnz) *nnz = total;
+  const i64 m = std::min<i64>(total, cap);
+  if (m <= 0) return finish(s);
+  const size_t cb = pad256((size_t)m * 4);
+  rc = grow(&s->d_det, &s->det_bytes, cb + (size_t)m * s->vsize);
+  if (rc) return rc;
+  int32_t* d_cols = (int32_t*)s->d_det;
+  char* d_vals = (char*)s->d_det + cb;
+  rc = [&]() -> int {
+    GLINT_DISPATCH(s->dtype, sparse_emit, s, d_rows, n, (const i64*)d_ptr, d_cols, (void*)d_vals, m, s->stream);
+  }();
+  if (rc) {
+    (void)hipStreamSynchronize(s->stream);
+    return rc;
+  }
+  HIPCHK(hipMemcpyAsync(out_cols, d_cols, (size_t)m * 4, hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(hipMemcpyAsync(out_vals, d_vals, (size_t)m * s->vsize, hipMemcpyDeviceToHost, s->stream));
+  return finish(s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2498,6 +2575,12 @@ int glint_mat_push_rows(glint_shard_t s, const int64_t* rows, const void* vals, 
   if (int rc = push_rows_args(s, rows, vals, n, flags)) return rc;
   if (n == 0) return GLINT_OK;
   return host_push_rows(s, rows, vals, n, flags);
+}
+
+int glint_mat_pull_rows_sparse(glint_shard_t s, const int64_t* rows, int64_t n, int64_t* row_ptr, int32_t* out_cols,
+                               void* out_vals, int64_t cap, int64_t* nnz) {
+  if (int rc = pull_sparse_args(s, rows, n, row_ptr, out_cols, out_vals, cap)) return rc;
+  return host_pull_rows_sparse(s, rows, n, row_ptr, out_cols, out_vals, cap, nnz);
 }
 
 // RequestSerializer.fromBinary (RequestSerializer.scala:59-130) for the push messages, applied

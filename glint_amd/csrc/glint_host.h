@@ -491,4 +491,13 @@ int rs_sort(K* k0, V* v0, K* k1, V* v1, i64 m, int end_bit, u32* hist, u32* offs
 // whole-row matrix push (glint_rows.hip), instantiated for V in {int, long long, float, double}
 template <typename V>
 int push_rows(glint_shard* s, const i64* rows, const void* vals, i64 n, int flags, hipStream_t st);
+// sparse row pull (glint_sparse.hip), instantiated for the same V. sparse_count_scan: row_ptr[0..n]
+// (device) = exclusive prefix of the requested rows' non-zero counts; rows outside the partition
+// count 0 and are recorded in err_of(s); the scan's scratch is s->d_det. sparse_emit: the entries
+// with position < cap, given that row_ptr. Both enqueue on st without host synchronisation.
+template <typename V>
+int sparse_count_scan(glint_shard* s, const i64* rows, i64 n, i64* row_ptr, hipStream_t st);
+template <typename V>
+int sparse_emit(glint_shard* s, const i64* rows, i64 n, const i64* row_ptr, int32_t* out_cols, void* out_vals,
+                i64 cap, hipStream_t st);
 }  // namespace glint

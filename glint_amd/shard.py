@@ -478,6 +478,63 @@ class PartialMatrix(_Shard):
         check(self.lib.glint_mat_pull_rows(self.handle, r.ctypes.data, res.ctypes.data, r.size), self.handle)
         return res
 
+    def getRowsSparse(self, rows, cap: Optional[int] = None, sync: bool = True):
+        """The non-zero elements of the requested rows as a CSR triple ``(indptr, cols, values)`` (an
+        extension; glint_mat_pull_rows_sparse*): ``indptr`` has n + 1 int64 entries, request i's entries
+        are ``cols[indptr[i]:indptr[i+1]]`` (int32, ascending) and ``values[...]`` (the stored bits).
+        Non-zero is the type's ``v != 0``: -0.0 is dropped, NaN kept. Scattered into zeros the triple is
+        getRows(rows).
+
+        Host arrays: exact-size numpy arrays (a count-only call, then the pull; with ``cap=k`` one call
+        and at most k entries); only the non-zeros cross the link. Device tensors with
+        ``cap=None``: a count, one synchronisation to read the total, then exact-size tensors. Device
+        tensors with ``cap=k``: one stream-ordered call, returns ``(indptr, cols[:k], values[:k])``;
+        entries at positions >= k are not stored, and the caller compares ``indptr[-1]`` with k."""
+        if _is_torch_cuda(rows):
+            import torch
+            n = rows.numel()
+            self._check_dev(n, rows)
+            if cap is not None and int(cap) < 0:
+                raise ValueError("cap must be >= 0")
+            st = self._stream_of(rows)
+            indptr = torch.empty(n + 1, dtype=torch.int64, device=rows.device)
+            if cap is None:
+                check(self.lib.glint_mat_pull_rows_sparse_dev(self.handle, rows.data_ptr(), n, indptr.data_ptr(),
+                                                              None, None, 0, st), self.handle)
+                k = int(indptr[-1].item())
+            else:
+                k = int(cap)
+            cols = torch.empty(k, dtype=torch.int32, device=rows.device)
+            vals = torch.empty(k, dtype=self.torch_dtype, device=rows.device)
+            if k or cap is not None:
+                check(self.lib.glint_mat_pull_rows_sparse_dev(self.handle, rows.data_ptr(), n, indptr.data_ptr(),
+                                                              cols.data_ptr() if k else None,
+                                                              vals.data_ptr() if k else None, k, st), self.handle)
+            if sync:
+                self.sync(st)
+            return indptr, cols, vals
+        r = _host(rows, np.int64).reshape(-1)
+        indptr = np.empty(r.size + 1, np.int64)
+        nnz = C.c_int64(0)
+        if cap is None:  # a count-only call sizes the arrays (cheaper than faulting in room for n x cols)
+            check(self.lib.glint_mat_pull_rows_sparse(self.handle, r.ctypes.data, r.size, indptr.ctypes.data, None,
+                                                      None, 0, C.byref(nnz)), self.handle)
+            k = nnz.value
+            if k == 0:
+                return indptr, np.empty(0, np.int32), np.empty(0, self.np_dtype)
+        else:
+            k = int(cap)
+            if k < 0:
+                raise ValueError("cap must be >= 0")
+        cols = np.empty(k, np.int32)
+        vals = np.empty(k, self.np_dtype)
+        check(self.lib.glint_mat_pull_rows_sparse(self.handle, r.ctypes.data, r.size, indptr.ctypes.data,
+                                                  cols.ctypes.data if k else None, vals.ctypes.data if k else None,
+                                                  k, C.byref(nnz)), self.handle)
+        if nnz.value < k:
+            cols, vals = cols[:nnz.value].copy(), vals[:nnz.value].copy()
+        return indptr, cols, vals
+
     def push_wire(self, payload: bytes, deterministic: bool = False) -> int:
         buf = (C.c_uint8 * len(payload)).from_buffer_copy(payload)
         mid = C.c_int32()

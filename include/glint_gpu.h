@@ -157,6 +157,32 @@ int glint_mat_pull_rows(glint_shard_t shard, const int64_t* rows, void* out, int
  * keep the push order, bit for bit the sequential loop, unless GLINT_PUSH_UNORDERED is given. */
 int glint_mat_push_rows(glint_shard_t shard, const int64_t* rows, const void* vals, int64_t n, int flags);
 
+/* Sparse row pull (an extension: the reference declares ResponseSparseDouble(indices, values) but wires
+ * it into no request): the non-zero elements of the requested rows as a CSR triple, compacted on the
+ * device so that only they cross the link.
+ *   row_ptr   n + 1 int64: row_ptr[0] = 0, row_ptr[i+1] - row_ptr[i] = the number of elements of
+ *             requested row i with v != 0 (the type's own test: -0.0 is dropped, NaN is kept);
+ *   out_cols  int32 column of entry j of request i at position row_ptr[i] + j, ascending inside a row;
+ *   out_vals  its value, the stored bits unchanged (the shard's type).
+ * Requests are answered in the caller's order; a row requested twice appears twice. Scattering the
+ * triple into zeros gives what glint_mat_pull_rows returns (a dropped -0.0 comes back as +0.0). The
+ * answer is deterministic (no atomic decides a position).
+ * Capacity as with snprintf: row_ptr is always written in full, so row_ptr[n] is the capacity the
+ * answer needs; an entry is stored only if its position is < cap, and nothing at or beyond cap is
+ * touched. cap == 0 is a count-only call, and only then may out_cols and out_vals be NULL. *nnz (may
+ * be NULL) receives row_ptr[n]. With n == 0, row_ptr[0] = 0 is still written.
+ * GLINT_EINVAL: a NULL or vector shard, n < 0, n >= 2^31, cap < 0, a NULL row_ptr, NULL rows with
+ * n > 0, NULL out_cols / out_vals with cap > 0. Every row is checked first: a row outside the
+ * partition returns GLINT_EOUTOFRANGE (its index in glint_shard_last_error) with nothing written.
+ * Device staging and the bytes copied back are (n + 1) * 8 + min(nnz, cap) * (4 + value size) --
+ * never cap or n * cols values: the call counts and scans, reads the total, then emits into buffers of
+ * that size. */
+int glint_mat_pull_rows_sparse(glint_shard_t shard, const int64_t* rows, int64_t n, int64_t* row_ptr,
+                               int32_t* out_cols, void* out_vals, int64_t cap, int64_t* nnz);
+/* Counts one scan workgroup covers in the sparse pull's prefix sum over the n + 1 row counts: a pull of
+ * more requests scans in two levels, of more than its square in three (tests size their cases by it). */
+#define GLINT_SPARSE_SCAN_TILE 1024
+
 /* After GLINT_EOUTOFRANGE: index (within the failing call) of the first rejected record. */
 int glint_shard_last_error(glint_shard_t shard, int64_t* first_bad_record);
 
@@ -180,6 +206,14 @@ int glint_mat_pull_rows_dev(glint_shard_t shard, const int64_t* rows, void* out,
  * push order with GLINT_PUSH_DETERMINISTIC, else long lists may be split and added unordered. */
 int glint_mat_push_rows_dev(glint_shard_t shard, const int64_t* rows, const void* vals, int64_t n, int flags,
                             void* stream);
+
+/* glint_mat_pull_rows_sparse, device-resident: the same triple and capacity rule, stream-ordered on
+ * `stream` with no host synchronisation, so the caller reads row_ptr[n] itself (and compares it with
+ * cap) after waiting on the stream. A row outside the partition has 0 entries and is reported by
+ * glint_shard_sync (the lowest such request index), as for glint_mat_pull_rows_dev; the other rows are
+ * answered. Scratch is the shard's growable device scratch. */
+int glint_mat_pull_rows_sparse_dev(glint_shard_t shard, const int64_t* rows, int64_t n, int64_t* row_ptr,
+                                   int32_t* out_cols, void* out_vals, int64_t cap, void* stream);
 
 /* glint_vec_push_dev / glint_mat_push_dev behind a device-side gate: the push is enqueued at once,
  * and when it runs it applies NOTHING if the 64-bit device word *gate is nonzero (a route status word,
@@ -355,7 +389,10 @@ enum glint_kernel_id {
   GLINT_K_PUSH_BINNED = 6,  /* the binned unordered-push pipeline (count, partition, apply) */
   GLINT_K_PUSH_ORDERED = 7, /* the order-preserving push of message-sized pushes (one launch) */
   GLINT_K_PUSH_ROWS = 8,    /* the per-destination fold of a whole-row push (glint_mat_push_rows*) */
-  GLINT_K_COUNT = 9
+  /* the sparse row pull (glint_mat_pull_rows_sparse*): its emit kernel, and under the same id its
+   * count kernel and the launches of its scan, so the sum is the pull's whole device time */
+  GLINT_K_PULL_ROWS_SPARSE = 9,
+  GLINT_K_COUNT = 10
 };
 int glint_prof_enable(glint_shard_t shard, int on);
 int glint_prof_read(glint_shard_t shard, int kernel_id, double* total_ms, int64_t* launches);

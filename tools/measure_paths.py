@@ -3,7 +3,9 @@ device-resident rates from HIP events around each kernel (glint_prof_*), and hos
 ("end-to-end": pageable host memory -> H2D -> kernels -> D2H) rates by wall clock, which is what
 the JNI shim sees. One JSON line per measurement on stdout.
 
-    python tools/measure_paths.py [--quick]
+    python tools/measure_paths.py [--quick] [--sparse]
+
+--sparse runs only the sparse-row-pull leg (dense getRows against getRowsSparse on a cfg5 shard).
 """
 import ctypes as C
 import json
@@ -44,6 +46,20 @@ def timed(fn, reps, h):
     return dt
 
 
+def kernel_total_ms(h, kid):
+    ms, cnt = C.c_double(), C.c_int64()
+    lib.glint_prof_read(h, kid, C.byref(ms), C.byref(cnt))
+    return ms.value, cnt.value
+
+
+def wall(fn, reps):
+    fn()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    return (time.perf_counter() - t0) / reps
+
+
 def emit(**kw):
     print(json.dumps(kw), flush=True)
 
@@ -60,7 +76,68 @@ def zipf_keys(rng, n_keys, n, s):
     return perm[ranks].astype(np.int64)
 
 
+def sparse_leg(rng):
+    """cfg5 per GPU: a 2^17 x 512 Double shard, 2^14 Zipf(1.0) rows, at element densities 1 %, 10 %
+    and 100 %. Host: glint_mat_pull_rows against glint_mat_pull_rows_sparse, wall time and the bytes
+    copied back. Device: kernel time (glint_prof) of the dense row pull against the sparse pull's
+    count + scan + emit (all under GLINT_K_PULL_ROWS_SPARSE)."""
+    shard_rows, cols, n = 1 << 17, 512, 1 << 14
+    msh = glint_amd.PartialMatrix(glint_amd.RangePartition(0, 0, shard_rows), cols, "double", 0)
+    h = msh.handle
+    rows = zipf_keys(rng, shard_rows, n, 1.0)
+    qr = torch.from_numpy(rows).to(dev)
+    dense_out = np.empty((n, cols), np.float64)
+    ptr = np.empty(n + 1, np.int64)
+    # room for every element: only the pages the answer lands in are touched
+    ocols, ovals = np.empty(n * cols, np.int32), np.empty(n * cols, np.float64)
+    nnz = C.c_int64()
+    d_dense = torch.empty((n, cols), dtype=torch.float64, device=dev)
+    d_ptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    for density in (0.01, 0.1, 0.5, 0.7, 1.0):  # 0.5 and 0.7 bracket the host crossover
+        msh.zero()
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(int(density * 1000))
+        for r0 in range(0, shard_rows, 1 << 14):  # fill in slices: the triplets of a slice fit easily
+            mask = torch.rand((1 << 14, cols), device=dev, generator=gen) < density
+            rr, cc = mask.nonzero(as_tuple=True)
+            vv = torch.rand(rr.numel(), dtype=torch.float64, device=dev, generator=gen) + 0.5
+            msh.update((rr + r0).contiguous(), cc.to(torch.int32).contiguous(), vv)
+        del mask, rr, cc, vv
+        reps = 5
+        t_dense = wall(lambda: lib.glint_mat_pull_rows(h, rows.ctypes.data, dense_out.ctypes.data, n), reps)
+        t_sparse = wall(lambda: lib.glint_mat_pull_rows_sparse(h, rows.ctypes.data, n, ptr.ctypes.data,
+                                                               ocols.ctypes.data, ovals.ctypes.data, n * cols,
+                                                               C.byref(nnz)), reps)
+        # the Python methods allocate their answers per call: fresh pages, faulted in by the copies
+        t_dense_py = wall(lambda: msh.getRows(rows), reps)
+        t_sparse_py = wall(lambda: msh.getRowsSparse(rows), reps)
+        k = nnz.value
+        assert k == int((dense_out != 0).sum())
+        # device-resident: one dense row pull against one sparse pull with an exact cap
+        d_cols = torch.empty(k, dtype=torch.int32, device=dev)
+        d_vals = torch.empty(k, dtype=torch.float64, device=dev)
+        timed(lambda: lib.glint_mat_pull_rows_dev(h, qr.data_ptr(), d_dense.data_ptr(), n, stream), 10, h)
+        k_dense = kernel_ms(h, N.GLINT_K_MAT_PULL_ROWS)
+        timed(lambda: lib.glint_mat_pull_rows_sparse_dev(h, qr.data_ptr(), n, d_ptr.data_ptr(), d_cols.data_ptr(),
+                                                         d_vals.data_ptr(), k, stream), 10, h)
+        ms_total, launches = kernel_total_ms(h, N.GLINT_K_PULL_ROWS_SPARSE)
+        emit(op="mat_pull_rows_sparse", pattern="zipf1.0 rows", shape=[shard_rows, cols], rows=n, density=density,
+             nnz=k, measured_density=k / (n * cols),
+             host_dense_ms=t_dense * 1e3, host_sparse_ms=t_sparse * 1e3, host_speedup=t_dense / t_sparse,
+             getRows_ms=t_dense_py * 1e3, getRowsSparse_ms=t_sparse_py * 1e3,
+             host_dense_bytes_back=n * cols * 8, host_sparse_bytes_back=(n + 1) * 8 + k * 12,
+             dev_dense_kernel_ms=k_dense, dev_sparse_kernels_ms=ms_total / 10, dev_sparse_launches_per_pull=launches / 10,
+             note="host_*: the C calls into reused pageable numpy buffers, synchronous, mean of 5; getRows*: the "
+                  "Python methods, fresh arrays per call (getRowsSparse = a count-only call + the pull); device: HIP-event kernel time, mean of 10; "
+                  "the sparse figure sums count + scan + emit")
+        del d_cols, d_vals
+    msh.destroy()
+
+
 def main():
+    if "--sparse" in sys.argv:
+        sparse_leg(np.random.default_rng(42))
+        return
     lg = 26 if QUICK else 28
     n = 1 << lg
     rng = np.random.default_rng(42)
@@ -201,6 +278,9 @@ def main():
     emit(op="mat_push_dev", pattern="dense row-major sweep", records=dr.numel(), ms=dt * 1e3,
          algorithmic_GBps=36.0 * dr.numel() / dt / 1e9, note="36 B/record: row 8 + col 4 + value 8 + shard 16")
     msh.destroy()
+
+    # ---- sparse row pull against the dense one (cfg5 shard, three densities) ------------------------
+    sparse_leg(rng)
 
     # ---- configs[0] end to end over loopback TCP: HBM shards behind the wire ingest ----------------
     import subprocess
