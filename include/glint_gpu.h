@@ -50,7 +50,11 @@ enum glint_push_flags {
    * Host-pointer and wire pushes (glint_vec_push, glint_mat_push, glint_push_wire: what the actor's
    * update() calls) of up to 131 072 records -- above the 79 999-record frame cap, glint.conf:143 --
    * keep the message's order WITHOUT this flag too (one launch, glint_ordered.hip), unless
-   * GLINT_PUSH_UNORDERED is given. */
+   * GLINT_PUSH_UNORDERED is given.
+   * IEEE edge values: in every mode subnormals are kept (no input or partial sum is flushed) and
+   * infinities and NaN propagate as classes, with the NaN's payload unspecified; the ordered paths add
+   * in the shard's type and keep the sign of a zero as the sequential loop does, the unordered ones
+   * leave it unspecified. */
   GLINT_PUSH_DETERMINISTIC = 1,
   /* Hint: the keys are in no particular order and the caller does not need the reference's
    * summation order. A large push skips the order check and sums the records per shard slab in
@@ -133,7 +137,9 @@ int glint_shard_info(glint_shard_t shard, int32_t* size, int32_t* cols, int* dty
 /* PartialVector.update(keys, values) -- PartialVector.scala:35-43. vals: n elements of dtype. */
 int glint_vec_push(glint_shard_t shard, const int64_t* keys, const void* vals, int64_t n, int flags);
 
-/* PartialVector.get(keys) -- PartialVector.scala:51-60. out: n elements of dtype. */
+/* PartialVector.get(keys) -- PartialVector.scala:51-60. out: n elements of dtype. Every pull entry
+ * point (host, device, ring and wire forms) moves the stored bits unchanged: -0.0, a NaN's payload
+ * and sign, subnormals. */
 int glint_vec_pull(glint_shard_t shard, const int64_t* keys, void* out, int64_t n);
 
 /* PartialMatrix.update(rows, cols, values) -- PartialMatrix.scala:74-83. */

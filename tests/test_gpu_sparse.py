@@ -17,6 +17,7 @@ from glint_amd import _native as N
 from glint_amd import ArrayIndexOutOfBoundsException, Client, CyclicPartition, PartialMatrix, PartialVector, \
     RangePartition
 from glint_amd.shard import check as check_rc
+from ieee_cases import write_image
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -81,24 +82,6 @@ def image(dtype, cols, fill):
         img[5, 0], img[6, cols - 1] = special[0], special[1]
     img.setflags(write=False)
     return img
-
-
-def write_image(sh, gpu, img, pad_value):
-    """The image into the shard's memory as it lies (row pitch from glint_shard_pitch), the pitch
-    padding set to a NON-ZERO value: a kernel that read it would count it."""
-    import torch
-    lib = N.load()
-    pitch = C.c_int64()
-    assert lib.glint_shard_pitch(sh.handle, C.byref(pitch)) == N.GLINT_OK
-    assert pitch.value >= img.shape[1]
-    padded = np.full((img.shape[0], pitch.value), pad_value, img.dtype)
-    padded[:, :img.shape[1]] = img
-    d = torch.device("cuda", gpu)
-    src = torch.from_numpy(padded).to(d)
-    segs = np.array([0, 0, padded.nbytes], np.int64)
-    assert lib.glint_copy_segments_dev(src.data_ptr(), sh.data_ptr(), segs.ctypes.data_as(C.POINTER(C.c_int64)), 1,
-                                       torch.cuda.current_stream(d).cuda_stream) == N.GLINT_OK
-    torch.cuda.synchronize(d)
 
 
 def load_shard(sh, ref, gpu, img, fill):
