@@ -25,7 +25,9 @@ ORACLE_LIB = ORACLE_DIR / "build" / "libglint_oracle.so"
 CSRC = PKG / "csrc"
 HIP_SOURCES = [CSRC / "glint_gpu.hip", CSRC / "glint_sort.hip", CSRC / "glint_route.hip", CSRC / "glint_ordered.hip", CSRC / "glint_bin.hip",
                CSRC / "glint_exchange.hip", CSRC / "glint_rows.hip", CSRC / "glint_sparse.hip"]
-HIP_HEADERS = [CSRC / "glint_kernels.h", CSRC / "glint_device.h", CSRC / "glint_host.h", ROOT / "include" / "glint_gpu.h"]
+PLAN_HEADERS = [CSRC / "glint_push_plan.h", CSRC / "glint_bin_plan.h"]  # plain C++: the push planners
+HIP_HEADERS = [CSRC / "glint_kernels.h", CSRC / "glint_device.h", CSRC / "glint_host.h", ROOT / "include" / "glint_gpu.h",
+               *PLAN_HEADERS]
 HIP_DEPS = HIP_SOURCES + HIP_HEADERS
 OBJ_DIR = ROOT / "build" / "obj"
 ORACLE_SOURCES = [ORACLE_DIR / "glint_oracle.c"]
@@ -135,11 +137,34 @@ def build_jni_driver(force: bool = False, verbose: bool = False) -> Path:
     return JNI_DRIVER
 
 
+PLAN_PROBE_SRC = ROOT / "tests" / "c" / "plan_probe.cpp"
+PLAN_PROBE = ROOT / "tests" / "c" / "build" / "libplan_probe.so"
+
+
+def build_plan_probe(force: bool = False, verbose: bool = False) -> Path:
+    """The push planners (glint_push_plan.h, glint_bin_plan.h) as a host-only library of C wrappers:
+    what tests/test_plan_cpu.py loads. g++ alone compiles it, which is also the check that the two
+    headers need nothing of HIP."""
+    deps = [PLAN_PROBE_SRC, *PLAN_HEADERS, ROOT / "include" / "glint_gpu.h"]
+    if not force and not _stale(PLAN_PROBE, deps):
+        return PLAN_PROBE
+    PLAN_PROBE.parent.mkdir(parents=True, exist_ok=True)
+    tmp = PLAN_PROBE.with_suffix(".so.tmp")
+    cxx = shutil.which("g++") or "c++"
+    cmd = [cxx, "-O2", "-std=c++17", "-Wall", "-Werror", "-fPIC", "-shared", "-o", str(tmp), str(PLAN_PROBE_SRC)]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True, cwd=str(ROOT))
+    os.replace(tmp, PLAN_PROBE)
+    return PLAN_PROBE
+
+
 def build_all(force: bool = False, verbose: bool = False) -> None:
     build_gpu_lib(force=force, verbose=verbose)
     build_oracle(force=force, verbose=verbose)
     build_loopback(force=force, verbose=verbose)
     build_jni_driver(force=force, verbose=verbose)
+    build_plan_probe(force=force, verbose=verbose)
 
 
 if __name__ == "__main__":

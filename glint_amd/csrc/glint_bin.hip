@@ -28,6 +28,7 @@
 // window at its own range, and the fine sort's gathers are 64-bit addressed, so buffers may pass 4 GiB.
 #include "glint_device.h"
 #include "glint_host.h"
+#include "glint_bin_plan.h"
 
 #include <atomic>
 #include <cstring>
@@ -35,55 +36,21 @@
 
 namespace glint {
 
-#ifndef GLINT_SLAB_BITS
-#define GLINT_SLAB_BITS 12
-#endif
-constexpr int kSlabBits = GLINT_SLAB_BITS;  // (a build-time experiment knob; 12 = 32 KiB of Double per slab)
-constexpr int kSlab = 1 << kSlabBits;
-constexpr int kMaxDigit = 1024;        // coarse buckets and fine slabs per bucket, at most
-#ifndef GLINT_PART_TPB
-#define GLINT_PART_TPB 1024
-#endif
-constexpr int kATPB = GLINT_PART_TPB;  // partition workgroup size (build-time knob: 1024 or 512)
-#ifndef GLINT_PART_PER
-#define GLINT_PART_PER 4
-#endif
-constexpr int kAPer = GLINT_PART_PER;  // records per thread per chunk (build-time knob)
-#ifndef GLINT_PART_PER_PLAIN
-#define GLINT_PART_PER_PLAIN 8
-#endif
-// The plain front end of a large push takes chunks of 8 records per thread (no hot or dedup table
-// beside its staging in LDS): runs of 64 records per bucket and half the barriers per record. Same box,
-// two rounds (profiles/r06/ab_part_per_plain.txt): cfg4b 2.20 -> 2.16 ms; cfg5 (a small push) 0.311 ->
-// 0.314, so a small push keeps 4
-constexpr int kAPerPlain = GLINT_PART_PER_PLAIN;
+// (the knobs and constants that the sizes of a push depend on, and BinGeom: glint_bin_plan.h)
 constexpr int kAChunk = kATPB * kAPer; // records per partition chunk (and dedup table fill)
 constexpr int kASlots = 2 * kAChunk;   // dedup hash slots (load <= 0.5)
 constexpr int kASlotBits = kASlots == 8192 ? 13 : kASlots == 4096 ? 12 : 11;
 static_assert((1 << kASlotBits) == kASlots, "dedup table size");
-// partition workgroups per CU: LDS-bound (the dedup table; the plain front end's staging)
-constexpr int kPartWgPerCuDedup = kATPB == 1024 ? 1 : 2;
-#ifndef GLINT_PART_WPC
-#define GLINT_PART_WPC (kATPB == 1024 ? 1 : 2)
-#endif
 #ifndef GLINT_PART_AHEAD
 #define GLINT_PART_AHEAD 2
 #endif
 constexpr int kPartAhead = GLINT_PART_AHEAD;  // partition chunks in flight per workgroup (build-time knob)
-constexpr int kPartWgPerCuPlain = GLINT_PART_WPC;  // what fits (VGPRs): a second round of
-                                                           // workgroups measured 3-9 % slower
 #ifndef GLINT_APPLY_TPB
 #define GLINT_APPLY_TPB 256
 #endif
 constexpr int kCTPB = GLINT_APPLY_TPB;  // slab-apply workgroup size (build-time knob)
 constexpr u32 kEmptySlot = 0xFFFFFFFFu;
 
-struct BinGeom {
-  u32 fb;     // fine digit bits
-  u32 nb;     // coarse buckets (power of two)
-  u32 nf;     // fine slabs per bucket (power of two)
-  u32 nslab;  // nb * nf
-};
 __device__ __forceinline__ u32 bucket_of(u32 a, const BinGeom& g) { return a >> (kSlabBits + g.fb); }
 __device__ __forceinline__ u32 fine_of(u32 a, const BinGeom& g) { return (a >> kSlabBits) & (g.nf - 1); }
 
@@ -353,7 +320,6 @@ __device__ __forceinline__ u32 hot_mix(u32 x) {  // murmur3 fmix32
   return x;
 }
 
-constexpr int kWideSlots = 8192;  // the plain + hot front end's hot table (see bin_hot_select)
 __device__ __forceinline__ u32 wide_slot(u32 a) { return hot_mix(a) & (kWideSlots - 1); }
 // The verdict of a validating gated push whose tail is binned (after bin_part validated the tail and
 // push_check the records before the break): 0 or ~(first rejected record) to the caller's gate word; a
@@ -385,7 +351,6 @@ __global__ __launch_bounds__(256) void push_validate_gate_binned_kernel(LaunchCt
 // sum to the shard once at the end (one device atomic per hot element per workgroup), so only the
 // cold elements are partitioned. Any choice of hot set gives the same sums; the sample only decides
 // how much work moves off the partition path.
-constexpr int kHotSlots = 2048;     // direct-mapped hot table (per dedup workgroup: tags + sums in LDS)
 constexpr int kHotSample = 16384;   // records sampled per push, as kHotRuns runs of kHotRun records
 constexpr int kHotRun = 128;
 constexpr int kHotRuns = kHotSample / kHotRun;
@@ -1144,27 +1109,10 @@ __global__ __launch_bounds__(kScanTPB) void bin_scan_kernel(BinGeom g, const u32
 // runs into apply units of <= kUnitCap records at item boundaries (a slab with one unit is exclusive:
 // plain read-modify-write; a hot slab's units flush with device atomics). bin_apply2 sums a unit's runs
 // in LDS and writes the slab back.
-#ifndef GLINT_FSORT_TPB
-#define GLINT_FSORT_TPB 1024
-#endif
-// Records per thread of a fine item: 12 for every push, the values held in registers from their load to
-// their staging round (two rounds of 8192 through the 64 KiB stage), at two workgroups per CU (64
-// VGPRs). Same boxes (profiles/r06/ab_chunk_local.txt): 16 per thread with the values loaded again in
-// each staging round measured cfg4b 2.10 against 1.89 ms, cfg3 1.06 against 0.99; 8 per thread 1.92 /
-// 0.99 / cfg5 0.339 against 0.328. (Before the chunk-local partition, with contiguous items, 16 late
-// had been the best: ab_fsort_per16.txt.) Build-time knobs GLINT_FSORT_PER_SMALL / _LARGE (small: the
-// pushes with the plan fused in, see push_binned).
+// (kSTPB threads per fine item, kSPerSmall / kSPerLarge records per thread: glint_bin_plan.h)
 #ifndef GLINT_PLAN_SPLIT
 #define GLINT_PLAN_SPLIT 2
 #endif
-#ifndef GLINT_FSORT_PER_SMALL
-#define GLINT_FSORT_PER_SMALL 12
-#endif
-#ifndef GLINT_FSORT_PER_LARGE
-#define GLINT_FSORT_PER_LARGE 12
-#endif
-constexpr int kSTPB = GLINT_FSORT_TPB;
-constexpr int kSPerSmall = GLINT_FSORT_PER_SMALL, kSPerLarge = GLINT_FSORT_PER_LARGE;
 constexpr u32 kSItemMax = (u32)kSTPB * (kSPerSmall > kSPerLarge ? kSPerSmall : kSPerLarge);
 static_assert(kSItemMax <= 32768, "u16 slab offsets and the u16 staging of one item");
 constexpr u32 kUnitExcl = 1u;  // apply unit descriptor {slab, runs, records, flags}: the slab's only unit
@@ -1193,12 +1141,7 @@ constexpr int kPlanTPB = 1024;
 // and <= 128 slabs per bucket: cfg5's 641 items, nf = 128)
 constexpr u32 kPlanLds = 65536, kPlanPTab = 16640;
 constexpr u32 kPlanLdsFused = 32768, kPlanPTabFused = 8320;
-constexpr int kRunMax = 128;     // runs per apply unit at most
-#ifndef GLINT_UNIT_CAP
-#define GLINT_UNIT_CAP 4096
-#endif
-constexpr u32 kUnitCap = GLINT_UNIT_CAP;  // records per apply unit at most
-static_assert(kUnitCap <= 65535, "a unit's record prefix is staged as u16");
+// (kRunMax runs and kUnitCap records per apply unit at most: glint_bin_plan.h)
 #ifndef GLINT_GROUP_SLAB_AVG
 #define GLINT_GROUP_SLAB_AVG 512
 #endif
@@ -1983,28 +1926,6 @@ int resident_per_cu(K kernel, int tpb, size_t dyn_lds = 0) {
   return b;
 }
 
-// 128 coarse buckets (few enough that a partition chunk's records form runs per bucket, and a fine
-// item's runs per slab stay as long: 32 records each way for uniform keys into 2^28), more only when
-// the fine digit would exceed 10 bits (slabs < 2^20 for u32 addresses). Same box, two runs each
-// (profiles/r03/bench_binned_cb.txt): 2^7 against 2^8 buckets cfg5 0.418 -> 0.398 ms, cfg3 1.648 ->
-// 1.636 ms, cfg4b exchange 3.005 -> 3.005 ms; 2^6 slower on all
-#ifndef GLINT_BIN_CB
-#define GLINT_BIN_CB 7  // (build-time knob: coarse digit bits at least)
-#endif
-constexpr u32 kCoarseBitsMin = GLINT_BIN_CB;
-BinGeom bin_geometry(i64 elems, u32 cbmin) {
-  const i64 slabs = (elems + kSlab - 1) / kSlab;
-  u32 sb = 0;
-  while (((i64)1 << sb) < slabs) ++sb;
-  const u32 cb = std::min<u32>(sb, std::max<u32>(cbmin, sb > 10u ? sb - 10u : 0u));
-  BinGeom g;
-  g.fb = sb - cb;
-  g.nb = 1u << cb;
-  g.nf = 1u << g.fb;
-  g.nslab = g.nb * g.nf;
-  return g;
-}
-
 // u32 record indices and element addresses. (Then the chunk table -- nb <= 1024 rows of
 // ceil(n / 4096) + 1 u32 -- stays below 2^32 bytes: one buffer window in bin_part.)
 constexpr u64 kBinMaxRecs = (1ull << 32) - 2ull * kATPB * (kAPer > kAPerPlain ? kAPer : kAPerPlain);
@@ -2020,42 +1941,18 @@ int launch_validate_gate_binned(LaunchCtl* ctl, u64* gate, void* bc, u32* T, u32
   return GLINT_OK;
 }
 
-// Front end of a binned push (0 plain, 1 plain + hot split, 2 chunk dedup + hot split), from what the
-// last dedup push measured (the device reports m, the tail size and the cold records of each push
-// through host-mapped words, taken at the shard's last sync point, so the choice does not depend on
-// timing): chunk dedup when it kept < 80 % of the cold records it saw; otherwise the plain front end,
-// with the hot-element split when the hot elements took >= 25 % of the tail (cfg3 ~65 %; cfg5's ~10 %
-// does not pay for the sampling launch and the per-record check). A dedup push re-measures every 16
-// pushes (and the first one). GLINT_BIN_FRONT = dedup | hot | prep forces one (tests).
-int bin_front(glint_shard* s) {
-  {
-    const u64 w = s->hint_bin;
-    const u32 m = (u32)(w >> 32), tail = (u32)w;
-    const u32 cold = (u32)s->hint_bin_cold;
-    if (tail > 0 && s->hint_bin_front == 2) {
-      s->bin_chunk_ratio = cold ? (double)m / (double)cold : 1.0;
-      s->bin_hot_frac = 1.0 - (double)cold / (double)tail;
-    }
-  }
-  const bool probe = (s->bin_pushes++ & 15) == 0;
-  const int front = probe || s->bin_chunk_ratio < 0.8 ? 2 : (s->bin_hot_frac >= 0.25 ? 1 : 0);
+// GLINT_BIN_FRONT = dedup | hot | prep forces a front end (tests); -1 = bin_front_next's own choice
+int forced_front() {
   static EnvKnob front_knob("GLINT_BIN_FRONT");
-  const int forced = (int)front_knob.get([](const char* e) -> long long {
+  return (int)front_knob.get([](const char* e) -> long long {
     if (!e) return -1;
     if (!strcmp(e, "dedup")) return 2;
     if (!strcmp(e, "hot")) return 1;
     if (!strcmp(e, "prep")) return 0;
     return -1;
   });
-  return forced >= 0 ? forced : front;
 }
 
-// The wide hot table (front 1) is sampled every kHotEvery-th push and kept in between: a push's hot
-// set only decides how much work leaves the partition path (any set gives the same sums), and a
-// Zipf-like stream keeps its hot elements from push to push. A shard coming from another front end
-// samples at once. (tests/test_gpu_parity.py::test_binned_stream_of_batches pushes a stream of
-// different batches through the kept table.)
-constexpr u32 kHotEvery = 8;
 constexpr u32 kWideMin = 3;  // samples (of 262 144) that make an element hot in the wide table
 constexpr u32 kHotMin = 2;   // samples (of 16 384) that make an element hot in the dedup front end's table
 
@@ -2065,53 +1962,17 @@ int push_binned(glint_shard* s, const PushArgs<V>& a, bool from_break, hipStream
   typedef typename LdsAcc<V>::T A;
   const i64 n = a.n;
   if (!push_binnable(s, n)) return GLINT_EINVAL;
-  const int front = bin_front(s);
+  const BinFront fe = bin_front_next(s->bin_front, s->hint_bin, s->hint_bin_cold, s->hint_bin_front, forced_front());
+  const int front = fe.front;
   const bool dedup = front == 2;
-  bool hot_refresh = true;
-  if (front == 1) {
-    hot_refresh = s->bin_last_front != 1 || s->hot_age == 0 || s->hot_age >= kHotEvery;
-    s->hot_age = hot_refresh ? 1u : s->hot_age + 1u;
-  }
-  s->bin_last_front = front;
-  // a small push (at most ~4 fine items per CU, cfg5) plans its buckets inside bin_fsort
-  const bool small_push =
-      (i64)bin_geometry(s->elems, kCoarseBitsMin).nb + n / ((i64)kSTPB * kSPerSmall) + 1 <= (i64)4 * s->cus;
-  // records per thread of a partition chunk: 8 for a large push's plain front end, 4 otherwise (the hot
-  // and dedup tables share the LDS; a small push wants more chunks)
-  const int per = front == 0 && !small_push ? kAPerPlain : kAPer;
-  // Coarse buckets: 128 for chunks of 8 records per thread, 64 for chunks of 4 -- runs of ~64 records
-  // per bucket and chunk either way, which the fine sort gathers. Same box, 2 rounds
-  // (profiles/r06/ab_chunk_local.txt): 64 buckets for every push took cfg5 0.316 -> 0.303 ms and cfg3
-  // 0.965 -> 0.956, but cfg4b (8-record chunks) 1.85 -> 1.93.
-  const BinGeom g = bin_geometry(s->elems, per == kAPerPlain ? kCoarseBitsMin : kCoarseBitsMin - 1u);
-  const u32 kchunk = (u32)kATPB * (u32)per;
-  const i64 nchunks_max = (n + kchunk - 1) / kchunk;
-  // partition workgroups per CU: what fits at once (the hot front end's LDS table allows fewer)
+  // partition workgroups per CU of the hot front end: what fits at once beside its LDS table
   static const int hot_occ = resident_per_cu(bin_part_kernel<V, MAT, true, 0, false>, kATPB);
-  const int wpc = dedup ? kPartWgPerCuDedup : front == 1 ? std::min(kPartWgPerCuPlain, hot_occ) : kPartWgPerCuPlain;
-  const u32 G = (u32)std::max<i64>(1, std::min<i64>(nchunks_max, (i64)s->cus * wpc));
-  const u32 item = (u32)kSTPB * (small_push ? kSPerSmall : kSPerLarge);
-  const i64 max_fitems = (i64)g.nb + n / item + 1;
-  // apply units: a slab's units close at kUnitCap records or kRunMax runs, so at most
-  // floor(H / cap) + floor(runs / kRunMax) + 1 per non-empty slab
-  const i64 max_units = (i64)g.nslab + n / kUnitCap + std::min<i64>(n, max_fitems * g.nf) / kRunMax + 1;
-  // The chunk table (a spare row past the last chunk), the buckets' chunk prefixes P and places Q, Bb,
-  // Ib, the fine items and their first chunks, off2, the apply units, the dedup front end's hot tags and
-  // the record buffers (coarse: u32 address + A value; fine: u16 slab offset + A value). The
-  // [BinCtl | T] headers and the hot front end's tables live in buffers of their own (stable
-  // addresses: emptied by the kernels of the push before, not by memsets)
-  const u32 nstride = (u32)nchunks_max, ctstride = nstride + 1;  // (a spare column past the last chunk)
-  const size_t b_ct = pad256((size_t)ctstride * g.nb * 4);
-  const size_t b_pq = pad256((size_t)g.nb * (nstride + 1) * 4) + pad256((size_t)g.nb * nstride * 4);
-  const size_t b_nb = pad256((size_t)g.nb * 4);
-  const size_t b_fit = 2 * pad256((size_t)max_fitems * 8);
-  const size_t b_off2 = pad256((size_t)max_fitems * (g.nf + 1) * 4);
-  const size_t b_units = pad256((size_t)max_units * 16) + pad256((size_t)max_units * kRunMax * 8);
-  const size_t b_hot = pad256((size_t)kHotSlots * 4);
-  const size_t b_wpart = front == 1 ? pad256((size_t)G * kWideSlots * sizeof(A)) : 0;
-  const size_t b_a = pad256((size_t)n * 4), b_v = pad256((size_t)n * sizeof(A)), b_e = pad256((size_t)n * 2);
-  const size_t need = b_ct + b_pq + 2 * b_nb + b_fit + b_off2 + b_units + b_hot + b_wpart + b_a + 2 * b_v + b_e;
-  int rc = grow(&s->d_bin, &s->bin_bytes, need);
+  const BinLayout L = bin_layout(s->elems, n, s->cus, front, sizeof(A), hot_occ);
+  const BinGeom g = L.g;
+  const int per = L.per;
+  const u32 kchunk = L.kchunk, G = L.G, item = L.item, nstride = L.nstride, ctstride = L.ctstride;
+  const i64 max_fitems = L.max_fitems, max_units = L.max_units;
+  int rc = grow(&s->d_bin, &s->bin_bytes, L.need);
   if (rc) return rc;
   constexpr size_t kHdr = 12288;  // one [BinCtl (256 B) | T (<= kMaxDigit u32) | done (<= kMaxDigit u32)] header
   static_assert(256 + 8 * kMaxDigit <= kHdr && sizeof(BinCtl) <= 256, "header slot");
@@ -2139,121 +2000,120 @@ int push_binned(glint_shard* s, const PushArgs<V>& a, bool from_break, hipStream
   BinCtl* bc = (BinCtl*)hdr;
   u32* T = (u32*)(hdr + 256);
   u32* done = T + kMaxDigit;  // the fused plan: items of each bucket sorted so far
-  char* p = (char*)s->d_bin;
-  u32* ct = (u32*)p;
-  p += b_ct;
-  u32* P = (u32*)p;
-  u32* Q = (u32*)(p + pad256((size_t)g.nb * (nstride + 1) * 4));
-  p += b_pq;
-  u32* Bb = (u32*)p;
-  u32* Ib = (u32*)(p + b_nb);
-  p += 2 * b_nb;
-  uint2* fitems = (uint2*)p;
-  uint2* cwin = (uint2*)(p + pad256((size_t)max_fitems * 8));
-  p += b_fit;
-  u32* off2 = (u32*)p;
-  p += b_off2;
-  uint4* units = (uint4*)p;
-  uint2* runs = (uint2*)(p + pad256((size_t)max_units * 16));
-  p += b_units;
-  u32* hot_tags = (u32*)p;
-  p += b_hot;
+  char* const p = (char*)s->d_bin;  // (the [BinCtl | T] headers and the hot front end's tables have stable
+                                    // addresses of their own: emptied by the kernels of the push before)
+  u32* ct = (u32*)(p + L.ct);
+  u32* P = (u32*)(p + L.P);
+  u32* Q = (u32*)(p + L.Q);
+  u32* Bb = (u32*)(p + L.Bb);
+  u32* Ib = (u32*)(p + L.Ib);
+  uint2* fitems = (uint2*)(p + L.fitems);
+  uint2* cwin = (uint2*)(p + L.cwin);
+  u32* off2 = (u32*)(p + L.off2);
+  uint4* units = (uint4*)(p + L.units);
+  uint2* runs = (uint2*)(p + L.runs);
+  u32* hot_tags = (u32*)(p + L.hot_tags);
   u32* wkey = front == 1 ? (u32*)s->d_hot : nullptr;
   u32* wcnt = front == 1 ? (u32*)((char*)s->d_hot + b_wk) : nullptr;
   unsigned long long* wbest = front == 1 ? (unsigned long long*)((char*)s->d_hot + 2 * b_wk) : nullptr;
-  A* wpart = (A*)p;
-  p += b_wpart;
-  u32* addr_a = (u32*)p;
-  A* val_a = (A*)(p + b_a);
-  A* val_b = (A*)(p + b_a + b_v);
-  uint16_t* e_b = (uint16_t*)(p + b_a + 2 * b_v);
+  A* wpart = (A*)(p + L.wpart);
+  u32* addr_a = (u32*)(p + L.addr_a);
+  A* val_a = (A*)(p + L.val_a);
+  A* val_b = (A*)(p + L.val_b);
+  uint16_t* e_b = (uint16_t*)(p + L.e_b);
 
-  ProfScope ps(s, GLINT_K_PUSH_BINNED, st);
-  const int fb = from_break ? 1 : (hook && whole_next ? 2 : 0);
-  if (front == 1 && hot_refresh) {  // the wide hot table: sample, count, pick (the count table starts empty)
-    HIPCHK(hipMemsetAsync(wbest, 0, b_wbest, st));  // the picks of the pushes before (kept for reuse)
-    bin_hot_sample_kernel<MAT><<<kWideSampleWgs, 256, 0, st>>>(a.keys, a.cols, n, a.part, a.ctl, a.ntiles, fb, wkey,
-                                                                wcnt);
+  // the pipeline, timed as one GLINT_K_PUSH_BINNED entry however it ends
+  const auto pipeline = [&]() -> int {
+    const int fb = from_break ? 1 : (hook && whole_next ? 2 : 0);
+    if (front == 1 && fe.hot_refresh) {  // the wide hot table: sample, count, pick (the count table starts empty)
+      HIPCHK(hipMemsetAsync(wbest, 0, b_wbest, st));  // the picks of the pushes before (kept for reuse)
+      bin_hot_sample_kernel<MAT><<<kWideSampleWgs, 256, 0, st>>>(a.keys, a.cols, n, a.part, a.ctl, a.ntiles, fb, wkey,
+                                                                  wcnt);
+      HIPCHK(hipGetLastError());
+      bin_hot_select_kernel<<<(1u << kWideHashBits) / 256u, 256, 0, st>>>(wkey, wcnt, kWideMin, wbest);
+      HIPCHK(hipGetLastError());
+    }
+    // (a validating push's dedup front end sums no hot elements: they would reach the shard before its
+    // verdict)
+    const bool dedup_hot = dedup && !hook;
+    if (dedup_hot) {
+      bin_hot_pick_kernel<MAT><<<1, kHotTPB, 0, st>>>(a.keys, a.cols, n, a.part, a.ctl, a.ntiles, fb, kHotMin, hot_tags);
+      HIPCHK(hipGetLastError());
+    }
+    BinCtl* const nbc = (BinCtl*)nhdr;
+    u32* const nT = (u32*)(nhdr + 256);
+    LaunchCtl* const vctl = hook ? a.ctl : nullptr;
+    // (hook: a validating gated push, whose partition validates the tail records)
+    if (dedup) {
+      auto kern = a.part.kind == 0 ? (hook ? bin_part_dedup_kernel<V, MAT, 0, true> : bin_part_dedup_kernel<V, MAT, 0, false>)
+                                   : (hook ? bin_part_dedup_kernel<V, MAT, -1, true> : bin_part_dedup_kernel<V, MAT, -1, false>);
+      kern<<<G, kATPB, 0, st>>>(a.keys, a.cols, a.vals, n, a.part, a.ctl, a.ntiles, fb, g, addr_a, val_a, a.err, bc, ct, ctstride,
+                                dedup_hot ? hot_tags : nullptr, a.data, nbc, nT, vctl, whole_next);
+    } else {
+      auto pick = [&](auto pp, auto vv) {
+        constexpr int PP = decltype(pp)::value;
+        constexpr bool VV = decltype(vv)::value;
+        return a.part.kind == 0 ? (front == 1 ? bin_part_kernel<V, MAT, true, 0, VV> : bin_part_kernel<V, MAT, false, 0, VV, PP>)
+                                : (front == 1 ? bin_part_kernel<V, MAT, true, -1, VV> : bin_part_kernel<V, MAT, false, -1, VV, PP>);
+      };
+      auto pick2 = [&](auto vv) {
+        return per == kAPerPlain ? pick(std::integral_constant<int, kAPerPlain>{}, vv) : pick(std::integral_constant<int, kAPer>{}, vv);
+      };
+      auto kern = hook ? pick2(std::true_type{}) : pick2(std::false_type{});
+      kern<<<G, kATPB, 0, st>>>(a.keys, a.cols, a.vals, n, a.part, a.ctl, a.ntiles, fb, g, addr_a, val_a, a.err, bc, ct, ctstride,
+                                wbest, wpart, nbc, nT, vctl, whole_next);
+    }
     HIPCHK(hipGetLastError());
-    bin_hot_select_kernel<<<(1u << kWideHashBits) / 256u, 256, 0, st>>>(wkey, wcnt, kWideMin, wbest);
+    s->bin_par ^= 1;  // this push's header is [hdr]; bin_part zeroed the other one for the next push
+    if (hook) {  // the verdict (and a rejected batch's cancel) and the head's apply, before anything is applied
+      rc = (*hook)(bc, T, g.nb);
+      if (rc) return rc;
+    }
+    // (front 1: the hot split's sums added by the same launch's workgroups past the buckets)
+    const u32 red = front == 1 ? (u32)(kWideSlots / kRedSlots) : 0u;
+    bin_scan_kernel<V><<<g.nb + red, kScanTPB, 0, st>>>(g, ct, ctstride, n, a.ctl, a.ntiles, fb, kchunk, nstride, bc, T,
+                                                        Bb, Ib, fitems, cwin, P, Q, item, wbest, G, wpart, a.data, vctl);
     HIPCHK(hipGetLastError());
-  }
-  // (a validating push's dedup front end sums no hot elements: they would reach the shard before its
-  // verdict)
-  const bool dedup_hot = dedup && !hook;
-  if (dedup_hot) {
-    bin_hot_pick_kernel<MAT><<<1, kHotTPB, 0, st>>>(a.keys, a.cols, n, a.part, a.ctl, a.ntiles, fb, kHotMin, hot_tags);
+    // Groups of sparse slabs for vector shards; a matrix shard's sparse slabs stay units of their own: its
+    // records cluster in a slab's few hot rows, and grouping cost cfg5 0.309 -> 0.337 ms while it takes
+    // cfg3 1.077 -> 1.038 (profiles/r05/ab_group_unitcap.txt).
+    const int group_on = MAT ? 0 : 1;
+    // The plan fused into bin_fsort for a push of at most ~4 items per CU (cfg5's 641), where the plan
+    // launch and its tail are a real share of the push; with many items per CU every item's wait for its
+    // stores before counting itself in costs more: cfg3 1.067 -> 1.078, cfg4b 2.375 -> 2.44 ms, cfg5
+    // 0.347 -> 0.335 (profiles/r05/ab_fused_plan.txt)
+    // (fused for every push, with the fine sort at two workgroups per CU: cfg4b 2.15 -> 2.50 ms, cfg3 1.02
+    // -> 1.04, profiles/r06/ab_fuse_all.txt; again with 16-record items at two per CU: cfg4b 2.14 -> 2.35,
+    // cfg3 1.029 -> 1.028)
+    const bool fused = L.small_push;
+    u64* const bhint = s->d_hint ? s->d_hint + 1 : nullptr;
+    u64* const whint = whole_next ? s->d_hint : nullptr;
+    if (fused) {
+      bin_fsort_kernel<A, true, kSPerSmall><<<(unsigned)max_fitems, kSTPB, 0, st>>>(g, fitems, bc, T, Bb, addr_a, val_a, e_b, val_b,
+                                                                        off2, bhint, whint, (u32)n, Ib, done, units, runs,
+                                                                        group_on, item, cwin, P, Q, nstride);
+      HIPCHK(hipGetLastError());
+    } else {
+      bin_fsort_kernel<A, false, kSPerLarge><<<(unsigned)max_fitems, kSTPB, 0, st>>>(g, fitems, bc, T, Bb, addr_a, val_a, e_b, val_b,
+                                                                         off2, bhint, whint, (u32)n, Ib, done, units, runs,
+                                                                         group_on, item, cwin, P, Q, nstride);
+      HIPCHK(hipGetLastError());
+      bin_plan_kernel<<<g.nb * GLINT_PLAN_SPLIT, kPlanTPB, 0, st>>>(g, T, Bb, Ib, off2, bc, units, runs, group_on, item);
+      HIPCHK(hipGetLastError());
+    }
+    // a persistent grid of the resident workgroups: each pipelines its units two deep, in XCD-grouped
+    // order (see bin_apply2_kernel)
+    static const int apply2_occ = resident_per_cu(bin_apply2_kernel<V>, kCTPB);
+    const unsigned apply2_grid = (unsigned)std::min<i64>(max_units, (i64)s->cus * apply2_occ);
+    bin_apply2_kernel<V><<<apply2_grid, kCTPB, 0, st>>>(e_b, val_b, units, runs, bc, s->elems, a.data,
+                                                        apply2_grid % 8 == 0 ? 1 : 0, g.nf);
     HIPCHK(hipGetLastError());
-  }
-  BinCtl* const nbc = (BinCtl*)nhdr;
-  u32* const nT = (u32*)(nhdr + 256);
-  LaunchCtl* const vctl = hook ? a.ctl : nullptr;
-  // (hook: a validating gated push, whose partition validates the tail records)
-  if (dedup) {
-    auto kern = a.part.kind == 0 ? (hook ? bin_part_dedup_kernel<V, MAT, 0, true> : bin_part_dedup_kernel<V, MAT, 0, false>)
-                                 : (hook ? bin_part_dedup_kernel<V, MAT, -1, true> : bin_part_dedup_kernel<V, MAT, -1, false>);
-    kern<<<G, kATPB, 0, st>>>(a.keys, a.cols, a.vals, n, a.part, a.ctl, a.ntiles, fb, g, addr_a, val_a, a.err, bc, ct, ctstride,
-                              dedup_hot ? hot_tags : nullptr, a.data, nbc, nT, vctl, whole_next);
-  } else {
-    auto pick = [&](auto pp, auto vv) {
-      constexpr int PP = decltype(pp)::value;
-      constexpr bool VV = decltype(vv)::value;
-      return a.part.kind == 0 ? (front == 1 ? bin_part_kernel<V, MAT, true, 0, VV> : bin_part_kernel<V, MAT, false, 0, VV, PP>)
-                              : (front == 1 ? bin_part_kernel<V, MAT, true, -1, VV> : bin_part_kernel<V, MAT, false, -1, VV, PP>);
-    };
-    auto pick2 = [&](auto vv) {
-      return per == kAPerPlain ? pick(std::integral_constant<int, kAPerPlain>{}, vv) : pick(std::integral_constant<int, kAPer>{}, vv);
-    };
-    auto kern = hook ? pick2(std::true_type{}) : pick2(std::false_type{});
-    kern<<<G, kATPB, 0, st>>>(a.keys, a.cols, a.vals, n, a.part, a.ctl, a.ntiles, fb, g, addr_a, val_a, a.err, bc, ct, ctstride,
-                              wbest, wpart, nbc, nT, vctl, whole_next);
-  }
-  HIPCHK(hipGetLastError());
-  s->bin_par ^= 1;  // this push's header is [hdr]; bin_part zeroed the other one for the next push
-  if (hook) {  // the verdict (and a rejected batch's cancel) and the head's apply, before anything is applied
-    rc = (*hook)(bc, T, g.nb);
-    if (rc) return rc;
-  }
-  // (front 1: the hot split's sums added by the same launch's workgroups past the buckets)
-  const u32 red = front == 1 ? (u32)(kWideSlots / kRedSlots) : 0u;
-  bin_scan_kernel<V><<<g.nb + red, kScanTPB, 0, st>>>(g, ct, ctstride, n, a.ctl, a.ntiles, fb, kchunk, nstride, bc, T,
-                                                      Bb, Ib, fitems, cwin, P, Q, item, wbest, G, wpart, a.data, vctl);
-  HIPCHK(hipGetLastError());
-  // Groups of sparse slabs for vector shards; a matrix shard's sparse slabs stay units of their own: its
-  // records cluster in a slab's few hot rows, and grouping cost cfg5 0.309 -> 0.337 ms while it takes
-  // cfg3 1.077 -> 1.038 (profiles/r05/ab_group_unitcap.txt).
-  const int group_on = MAT ? 0 : 1;
-  // The plan fused into bin_fsort for a push of at most ~4 items per CU (cfg5's 641), where the plan
-  // launch and its tail are a real share of the push; with many items per CU every item's wait for its
-  // stores before counting itself in costs more: cfg3 1.067 -> 1.078, cfg4b 2.375 -> 2.44 ms, cfg5
-  // 0.347 -> 0.335 (profiles/r05/ab_fused_plan.txt)
-  // (fused for every push, with the fine sort at two workgroups per CU: cfg4b 2.15 -> 2.50 ms, cfg3 1.02
-  // -> 1.04, profiles/r06/ab_fuse_all.txt; again with 16-record items at two per CU: cfg4b 2.14 -> 2.35,
-  // cfg3 1.029 -> 1.028)
-  const bool fused = small_push;
-  u64* const bhint = s->d_hint ? s->d_hint + 1 : nullptr;
-  u64* const whint = whole_next ? s->d_hint : nullptr;
-  if (fused) {
-    bin_fsort_kernel<A, true, kSPerSmall><<<(unsigned)max_fitems, kSTPB, 0, st>>>(g, fitems, bc, T, Bb, addr_a, val_a, e_b, val_b,
-                                                                      off2, bhint, whint, (u32)n, Ib, done, units, runs,
-                                                                      group_on, item, cwin, P, Q, nstride);
-    HIPCHK(hipGetLastError());
-  } else {
-    bin_fsort_kernel<A, false, kSPerLarge><<<(unsigned)max_fitems, kSTPB, 0, st>>>(g, fitems, bc, T, Bb, addr_a, val_a, e_b, val_b,
-                                                                       off2, bhint, whint, (u32)n, Ib, done, units, runs,
-                                                                       group_on, item, cwin, P, Q, nstride);
-    HIPCHK(hipGetLastError());
-    bin_plan_kernel<<<g.nb * GLINT_PLAN_SPLIT, kPlanTPB, 0, st>>>(g, T, Bb, Ib, off2, bc, units, runs, group_on, item);
-    HIPCHK(hipGetLastError());
-  }
-  // a persistent grid of the resident workgroups: each pipelines its units two deep, in XCD-grouped
-  // order (see bin_apply2_kernel)
-  static const int apply2_occ = resident_per_cu(bin_apply2_kernel<V>, kCTPB);
-  const unsigned apply2_grid = (unsigned)std::min<i64>(max_units, (i64)s->cus * apply2_occ);
-  bin_apply2_kernel<V><<<apply2_grid, kCTPB, 0, st>>>(e_b, val_b, units, runs, bc, s->elems, a.data,
-                                                      apply2_grid % 8 == 0 ? 1 : 0, g.nf);
-  HIPCHK(hipGetLastError());
-  return GLINT_OK;
+    return GLINT_OK;
+  };
+  const ProfSpan span = span_begin(s, st);
+  rc = pipeline();
+  span_end(s, GLINT_K_PUSH_BINNED, st, span);
+  return rc;
 }
 
 #define GLINT_INST(V, MAT) \

@@ -772,8 +772,8 @@ int binned_mode() {
     return atoi(e) != 0 ? 1 : 0;
   });
 }
-constexpr i64 kBinMin = (i64)1 << 20;  // records: below this the LDS-hash scatter wins
-// ... and below this many records per 4096-element slab of the shard (GLINT_BIN_DENSITY): the binned
+// GLINT_BIN_DENSITY: a push of kBinMin records or more (below them the LDS-hash scatter wins) is binned
+// from this many records per 4096-element slab of the shard: the binned
 // pipeline's passes cost about the same whatever the density, the atomic scatter's time grows with
 // the records. Measured crossover (tools/tail_ab.py, profiles/r05/tail_ab.jsonl, uniform keys into a
 // 2^28-element shard): scatter 0.55 / 1.02 / 1.98 / 3.83 ms against binned 0.88 / 1.27 / 1.99 / 2.24 ms
@@ -783,9 +783,34 @@ i64 bin_density() {
   static EnvKnob k("GLINT_BIN_DENSITY");
   return k.get([](const char* e) -> long long { return e ? std::max(0ll, atoll(e)) : 512ll; });
 }
-// records: up to this many, a (non-deterministic) push is the single scatter launch
-constexpr i64 kSmallPushMax = 4096;
+// GLINT_BIN_WHOLE=0: no whole-push bin or scatter, every push that is not small is checked
+bool whole_on() {
+  static EnvKnob k("GLINT_BIN_WHOLE");
+  return k.get([](const char* e) -> long long { return e ? atoi(e) != 0 : 1; }) != 0;
+}
 
+// the scatter of a push: mode 0 the records from the break, 1 every record, 2 every record of a
+// whole-push scatter (which writes the hint words itself)
+template <typename V, bool MAT>
+int launch_scatter(glint_shard* s, const PushArgs<V>& a, int mode, hipStream_t st) {
+  const unsigned g2 = grid_for(a.n, kScatterChunk, (i64)s->cus * 2);
+  HIPCHK(launch_k(s, GLINT_K_PUSH_SCATTER, push_scatter_kernel<V, MAT>, g2, kTPB, st, a, mode));
+  return GLINT_OK;
+}
+
+// push_check over the whole push, zeroing `next` (the other LaunchCtl slot) for the push after; vmode:
+// 0 no validation, 1 validate, 2 validate with the verdict left to the binned tail's count
+// (one launch: the key stream alone lost 3-6 % when windowed -- each short launch ramps up and drains)
+template <typename V, bool MAT>
+int launch_check(glint_shard* s, const PushArgs<V>& a, LaunchCtl* next, i64* desc, int vmode, hipStream_t st) {
+  const unsigned gc = grid_for(a.ntiles, kTPB / 64, (i64)s->cus * blocks_per_cu<push_check_kernel<MAT, 0>>(2));
+  HIPCHK(launch_k(s, GLINT_K_PUSH_CHECK, a.part.kind == 0 ? push_check_kernel<MAT, 0> : push_check_kernel<MAT, 1>, gc,
+                  kTPB, st, a.keys, a.cols, a.n, a.part, a.ctl, next, desc, a.ntiles, 0u, a.ntiles, vmode));
+  return GLINT_OK;
+}
+
+// Which kernels a push takes is push_route's decision (glint_push_plan.h); this fills in what it asks,
+// sets up the control region and launches.
 template <typename V, bool MAT>
 int launch_push(glint_shard* s, const i64* keys, const int32_t* cols, const void* vals, i64 n, int flags,
                 hipStream_t st) {
@@ -806,22 +831,26 @@ int launch_push(glint_shard* s, const i64* keys, const int32_t* cols, const void
   const i64 ntiles = (n + kTile - 1) / kTile;
   if (ntiles >= (i64)0xFFFFFFF0ll) return GLINT_EINVAL;
   a.ntiles = (u32)ntiles;
-  const bool vec_ok = aligned(keys, 16) && aligned(vals, 2 * sizeof(V)) && (!MAT || aligned(cols, 8));
-  const bool fp = s->dtype == GLINT_F32 || s->dtype == GLINT_F64;
-  const bool det = (flags & GLINT_PUSH_DETERMINISTIC) && fp;
-  const bool unordered = (flags & GLINT_PUSH_UNORDERED) != 0;
-  // Message-sized Float/Double pushes that must keep the reference's summation order -- every
-  // deterministic one, and host-pointer / wire pushes unless the caller said UNORDERED -- are one
-  // launch of the order-preserving fold (glint_ordered.hip). Int/Long sums are exact in any order.
-  const bool seq = det || (fp && (flags & kPushHostSequential) && !unordered);
-  // a gated push takes check + apply (+ its tail from the break): those kernels read the gate's
-  // verdict from the LaunchCtl (the ordered fold, the unordered hint and the one-launch small push
-  // have no such step)
-  const bool gated = s->gate != nullptr;
-  if (gated && (det || !vec_ok)) return GLINT_EINVAL;
-  // a ring launch (one workgroup that signals its own completion) is always the ordered fold: for
-  // Int/Long it is one more exact summation order
-  if (a.sig.done || (seq && n <= kOrderedMax && s->elems < ((i64)1 << 32))) return push_ordered<V, MAT>(s, a, st);
+
+  PushQuery q;
+  q.n = n;
+  q.flags = flags;
+  q.fp = s->dtype == GLINT_F32 || s->dtype == GLINT_F64;
+  q.vec_ok = aligned(keys, 16) && aligned(vals, 2 * sizeof(V)) && (!MAT || aligned(cols, 8));
+  q.gated = s->gate != nullptr;
+  q.ring = a.sig.done != nullptr;
+  q.elems = s->elems;
+  q.binnable = push_binnable(s, n);
+  q.hint_tail = s->hint_tail;  // the previous push's unordered tail, as of the last sync point
+  q.hint_head = s->hint_head;
+  q.whole_probe = s->whole_probe;
+  q.binned_mode = binned_mode();
+  q.bin_density = bin_density();
+  q.whole_on = whole_on();
+  const PushRoute r = push_route(q);
+  if (r.kind == PushKind::Invalid) return GLINT_EINVAL;
+  if (r.kind == PushKind::Ordered) return push_ordered<V, MAT>(s, a, st);
+
   // control region: [LaunchCtl slot 0 | slot 1 | pad to 256][tile descriptors i64 x ntiles]. An
   // ordered push uses one slot while its push_check zeroes the other for the next push, so no
   // memset runs per push (pushes on one shard are stream-ordered, as the actor's messages are).
@@ -835,76 +864,36 @@ int launch_push(glint_shard* s, const i64* keys, const int32_t* cols, const void
   }
   LaunchCtl* const slots = (LaunchCtl*)s->d_ctl;
   a.ctl = slots + s->ctl_par;
+  LaunchCtl* const next = slots + (s->ctl_par ^ 1);
   i64* desc = (i64*)((char*)s->d_ctl + 256);
+  if (r.probe_consumed) ++s->whole_probe;
 
-  const int bmode = binned_mode();
-  const i64 last_tail = (i64)s->hint_tail;  // the previous push's unordered tail, as of the last sync point
-  const i64 slabs = (s->elems + 4095) / 4096;
-  const bool binned = !det && vec_ok && push_binnable(s, n) && bmode != 0 &&
-                      (unordered || (n >= kBinMin && (bmode == 1 || (last_tail >= kBinMin &&
-                                                                     last_tail >= bin_density() * slabs))));
-  if (binned && unordered && !gated) return push_binned<V, MAT>(s, a, false, st);
-  const bool validate = gated && (flags & GLINT_PUSH_VALIDATE) != 0;
-  // Whole-push bin: when the last push (as of the last sync point) broke order in its first tile, the
-  // binned pipeline takes this one from record 0 with no push_check (the unordered push's check found
-  // only that, at one contended atomic per wave tile) and no head. Sums are the same in any order (this
-  // is not a deterministic push); bin_count validates every record of a validating push, zeroes the
-  // next push's LaunchCtl slot as push_check does, and notes whether two adjacent records were ever out
-  // of order, so an ordered push is followed by the checked path again. GLINT_BIN_WHOLE=0: always check.
-  static EnvKnob whole_knob("GLINT_BIN_WHOLE");
-  const bool whole = binned && (!gated || validate) && s->hint_tail > 0 && s->hint_head == 0 &&
-                     whole_knob.get([](const char* e) -> long long { return e ? atoi(e) != 0 : 1; }) != 0;
-  if (whole) {
-    LaunchCtl* const next = slots + (s->ctl_par ^ 1);
-    const BinHook hook = [&](void* bc, u32* T, u32 nb) -> int {
-      return launch_validate_gate_binned(a.ctl, s->gate, bc, T, nb, st);
-    };
-    rc = push_binned<V, MAT>(s, a, false, st, validate ? &hook : nullptr, next);
-    if (rc == GLINT_OK) s->ctl_par ^= 1;  // bin_count zeroed the other slot
-    return rc;
+  switch (r.kind) {
+    case PushKind::BinnedAll: return push_binned<V, MAT>(s, a, false, st);
+    case PushKind::WholeBin: {
+      const BinHook hook = [&](void* bc, u32* T, u32 nb) -> int {
+        return launch_validate_gate_binned(a.ctl, s->gate, bc, T, nb, st);
+      };
+      rc = push_binned<V, MAT>(s, a, false, st, r.validate ? &hook : nullptr, next);
+      if (rc == GLINT_OK) s->ctl_par ^= 1;  // bin_count zeroed the other slot
+      return rc;
+    }
+    case PushKind::DetAll: return push_det_tail<V, MAT>(s, a, false, st);
+    case PushKind::ScatterAll: return launch_scatter<V, MAT>(s, a, r.scatter_mode, st);
+    default: break;  // Checked
   }
-  // Small pushes (an Akka message is ~1000 records, GranularBigVectorSpec.scala:21) are one launch:
-  // the scatter handles every record, instead of check + apply + scatter. Launch latency is the
-  // whole cost at this size, so two fewer launches is the win; results are those of the scatter
-  // path (bit-exact for unique keys and for Int/Long, unordered sums otherwise).
-  const bool small = !det && !gated && n <= kSmallPushMax;
-  // Whole-push scatter: the sparse counterpart of the whole-push bin. When the last checked push broke
-  // order in its first tile and this one stays below the binned density, the scatter takes every record
-  // from 0 with no push_check / push_apply in front (they found only that). Its hint words say so (the
-  // push's size, a tail from record 0) without looking, so every 8th such push is checked again (its
-  // push_apply writes the measured words: an ordered push returns the shard to the checked path).
-  const bool whole_scatter = !binned && !det && !gated && vec_ok && !small && s->hint_tail > 0 &&
-                             s->hint_head == 0 && (s->whole_probe++ & 7u) != 7u &&
-                             whole_knob.get([](const char* e) -> long long { return e ? atoi(e) != 0 : 1; }) != 0;
-  if (!vec_ok || small || whole_scatter) {  // unaligned caller pointers or a small push: the scatter for everything
-    if (det) return push_det_tail<V, MAT>(s, a, false, st);
-    const unsigned g2 = grid_for(n, kScatterChunk, (i64)s->cus * 2);
-    HIPCHK(launch_k(s, GLINT_K_PUSH_SCATTER, push_scatter_kernel<V, MAT>, g2, kTPB, st, a, whole_scatter ? 2 : 1));
-    return GLINT_OK;
+  if (r.gate_kernel) {
+    push_gate_kernel<<<1, 64, 0, st>>>(s->gate, a.ctl);
+    HIPCHK(hipGetLastError());
   }
+  rc = launch_check<V, MAT>(s, a, next, desc, r.validate ? (r.fuse ? 2 : 1) : 0, st);
+  if (rc) return rc;
+  if (r.validate && !r.fuse) {
+    push_validate_gate_kernel<<<1, 64, 0, st>>>(a.ctl, s->gate);
+    HIPCHK(hipGetLastError());
+  }
+  s->ctl_par ^= 1;  // only once the check that zeroes the other slot is on the stream
   const u64 win = std::min<u64>(kSweepWindowTiles, a.ntiles);
-  // a validating push whose tail is binned reads its keys once: push_check validates the records up to
-  // the break, the tail's count pass the rest, and the verdict comes after that count (BinHook)
-  const bool fuse = validate && binned && !det;
-  {
-    LaunchCtl* const next = slots + (s->ctl_par ^ 1);
-    if (gated && !validate) {
-      push_gate_kernel<<<1, 64, 0, st>>>(s->gate, a.ctl);
-      HIPCHK(hipGetLastError());
-    }
-    // one launch: the key stream alone lost 3-6 % when windowed (each short launch ramps up and drains)
-    const unsigned gc =
-        grid_for(a.ntiles, kTPB / 64, (i64)s->cus * blocks_per_cu<push_check_kernel<MAT, 0>>(2));
-    HIPCHK(a.part.kind == 0 ? launch_k(s, GLINT_K_PUSH_CHECK, push_check_kernel<MAT, 0>, gc, kTPB, st, keys, cols, n,
-                                       a.part, a.ctl, next, desc, a.ntiles, 0u, a.ntiles, validate ? (fuse ? 2 : 1) : 0)
-                            : launch_k(s, GLINT_K_PUSH_CHECK, push_check_kernel<MAT, 1>, gc, kTPB, st, keys, cols, n,
-                                       a.part, a.ctl, next, desc, a.ntiles, 0u, a.ntiles, validate ? (fuse ? 2 : 1) : 0));
-    if (validate && !fuse) {
-      push_validate_gate_kernel<<<1, 64, 0, st>>>(a.ctl, s->gate);
-      HIPCHK(hipGetLastError());
-    }
-    s->ctl_par ^= 1;  // only once the check that zeroes the other slot is on the stream
-  }
   auto apply_head = [&]() -> int {  // the records before the break (every record of an ordered push)
     const i64 bpc = blocks_per_cu<push_apply_kernel<V, MAT>>(2);
     for (u64 t0 = 0; t0 < a.ntiles; t0 += win) {
@@ -915,7 +904,7 @@ int launch_push(glint_shard* s, const i64* keys, const int32_t* cols, const void
     }
     return GLINT_OK;
   };
-  if (fuse) {  // verdict, cancel and the head, behind the tail's validating count
+  if (r.fuse) {  // verdict, cancel and the head, behind the tail's validating count
     const BinHook hook = [&](void* bc, u32* T, u32 nb) -> int {
       const int rc2 = launch_validate_gate_binned(a.ctl, s->gate, bc, T, nb, st);
       return rc2 ? rc2 : apply_head();
@@ -924,11 +913,11 @@ int launch_push(glint_shard* s, const i64* keys, const int32_t* cols, const void
   }
   rc = apply_head();
   if (rc) return rc;
-  if (det) return push_det_tail<V, MAT>(s, a, true, st);
-  if (binned) return push_binned<V, MAT>(s, a, true, st);
-  const unsigned g2 = grid_for(n, kScatterChunk, (i64)s->cus * 2);
-  HIPCHK(launch_k(s, GLINT_K_PUSH_SCATTER, push_scatter_kernel<V, MAT>, g2, kTPB, st, a, 0));
-  return GLINT_OK;
+  switch (r.tail) {
+    case PushTail::Det: return push_det_tail<V, MAT>(s, a, true, st);
+    case PushTail::Binned: return push_binned<V, MAT>(s, a, true, st);
+    default: return launch_scatter<V, MAT>(s, a, 0, st);
+  }
 }
 
 // ---- pulls ------------------------------------------------------------------------------------
@@ -1213,6 +1202,63 @@ inline int pull_sparse_args(const glint_shard* s, const void* rows, int64_t n, c
   return GLINT_OK;
 }
 
+// argument check of the element-wise device-resident calls: a vector (matrix) shard, n >= 0
+inline int elem_args(const glint_shard* s, bool mat, int64_t n) {
+  if (!s || n < 0) return GLINT_EINVAL;
+  return mat == (s->part.cols != 0) ? GLINT_OK : GLINT_EINVAL;
+}
+
+// A device-resident call whose argument check gave args_rc: under the shard's lock and on its device,
+// after the shard's host-pointer work, body(st) launches on the caller's stream.
+template <typename F>
+int dev_call(glint_shard* s, int args_rc, void* stream, F body) {
+  if (args_rc) return args_rc;
+  ShardLock lk(s);
+  DeviceGuard g(s->device);
+  if (int rc = dev_order_after_host(s, (hipStream_t)stream)) return rc;
+  return body(pick(s, stream));
+}
+
+// What a host-pointer call does first, under the shard's lock: a slab with views is refused, the open
+// ring batch is launched and the shard's stream is ordered after the last device-resident call's.
+enum class HostEntry { Order, FlushOrder, OrderFlush };  // (Order: the call may append to the open batch)
+inline int host_enter(glint_shard* s, HostEntry e) {
+  int rc = refuse_slab(s);
+  if (rc == GLINT_OK && e == HostEntry::FlushOrder) rc = ring_flush_locked(s);
+  if (rc == GLINT_OK) rc = order_after_dev(s);
+  if (rc == GLINT_OK && e == HostEntry::OrderFlush) rc = ring_flush_locked(s);
+  return rc;
+}
+
+// a host-pointer call whose launch failed with rc: its staging buffers stay busy until the stream drains
+inline int launch_failed(glint_shard* s, int rc) {
+  (void)hipStreamSynchronize(s->stream);
+  return rc;
+}
+
+// glint_vec_push_dev_gated / glint_mat_push_dev_gated
+int push_dev_gated(glint_shard* s, bool mat, const int64_t* keys, const int32_t* cols, const void* vals, int64_t n,
+                   int flags, uint64_t* gate, void* stream) {
+  return dev_call(s, gate ? elem_args(s, mat, n) : GLINT_EINVAL, stream, [&](hipStream_t st) -> int {
+    struct Gate {
+      glint_shard* s;
+      ~Gate() { s->gate = nullptr; }
+    } reset{s};
+    // a gate word in glint_host_alloc memory is read / written by the kernels through its device
+    // address, and the caller reads the verdict straight from host memory after its wait
+    u64* gd = (u64*)host_dev_ptr(gate, sizeof(u64), sizeof(u64));
+    s->gate = gd ? gd : (u64*)gate;
+    if (n == 0 && (flags & GLINT_PUSH_VALIDATE)) {  // nothing to check: the verdict is "none rejected"
+      HIPCHK(hipMemsetAsync(s->gate, 0, sizeof(u64), st));
+      return GLINT_OK;
+    }
+    if (mat) {
+      GLINT_DISPATCH(s->dtype, push_mat_t, s, (const i64*)keys, cols, vals, n, flags, st);
+    }
+    GLINT_DISPATCH(s->dtype, push_vec_t, s, (const i64*)keys, nullptr, vals, n, flags, st);
+  });
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -1339,9 +1385,7 @@ int glint_shard_zero(glint_shard_t s) {
   if (!s) return GLINT_EINVAL;
   ShardLock lk(s);
   DeviceGuard g(s->device);
-  int rc = refuse_slab(s);
-  if (rc == GLINT_OK) rc = ring_flush_locked(s);  // the restart comes after every message enqueued before it
-  if (rc == GLINT_OK) rc = order_after_dev(s);
+  int rc = host_enter(s, HostEntry::FlushOrder);  // (the restart comes after every message enqueued before it)
   if (rc) return rc;
   HIPCHK(hipMemsetAsync(s->data, 0, (size_t)s->elems * s->vsize, s->stream));
   HIPCHK(hipMemsetAsync(s->d_err, 0, sizeof(ErrState), s->stream));
@@ -1487,66 +1531,26 @@ int glint_shard_sync(glint_shard_t s, void* stream, int64_t* first_bad) {
 
 // ---- device-resident ---------------------------------------------------------------------------
 int glint_vec_push_dev(glint_shard_t s, const int64_t* keys, const void* vals, int64_t n, int flags, void* stream) {
-  if (!s || n < 0) return GLINT_EINVAL;
-  if (s->part.cols != 0) return GLINT_EINVAL;
-  ShardLock lk(s);
-  DeviceGuard g(s->device);
-  if (int rc = dev_order_after_host(s, (hipStream_t)stream)) return rc;
-  GLINT_DISPATCH(s->dtype, push_vec_t, s, (const i64*)keys, nullptr, vals, n, flags, pick(s, stream));
+  return dev_call(s, elem_args(s, false, n), stream, [&](hipStream_t st) -> int {
+    GLINT_DISPATCH(s->dtype, push_vec_t, s, (const i64*)keys, nullptr, vals, n, flags, st);
+  });
 }
 
 int glint_mat_push_dev(glint_shard_t s, const int64_t* rows, const int32_t* cols, const void* vals, int64_t n,
                        int flags, void* stream) {
-  if (!s || n < 0) return GLINT_EINVAL;
-  if (s->part.cols == 0) return GLINT_EINVAL;
-  ShardLock lk(s);
-  DeviceGuard g(s->device);
-  if (int rc = dev_order_after_host(s, (hipStream_t)stream)) return rc;
-  GLINT_DISPATCH(s->dtype, push_mat_t, s, (const i64*)rows, cols, vals, n, flags, pick(s, stream));
+  return dev_call(s, elem_args(s, true, n), stream, [&](hipStream_t st) -> int {
+    GLINT_DISPATCH(s->dtype, push_mat_t, s, (const i64*)rows, cols, vals, n, flags, st);
+  });
 }
 
 int glint_vec_push_dev_gated(glint_shard_t s, const int64_t* keys, const void* vals, int64_t n, int flags,
                              uint64_t* gate, void* stream) {
-  if (!s || n < 0 || !gate) return GLINT_EINVAL;
-  if (s->part.cols != 0) return GLINT_EINVAL;
-  ShardLock lk(s);
-  DeviceGuard g(s->device);
-  if (int rc = dev_order_after_host(s, (hipStream_t)stream)) return rc;
-  struct Gate {
-    glint_shard* s;
-    ~Gate() { s->gate = nullptr; }
-  } reset{s};
-  // a gate word in glint_host_alloc memory is read / written by the kernels through its device
-  // address, and the caller reads the verdict straight from host memory after its wait
-  u64* gd = (u64*)host_dev_ptr(gate, sizeof(u64), sizeof(u64));
-  s->gate = gd ? gd : (u64*)gate;
-  if (n == 0 && (flags & GLINT_PUSH_VALIDATE)) {  // nothing to check: the verdict is "none rejected"
-    HIPCHK(hipMemsetAsync(s->gate, 0, sizeof(u64), pick(s, stream)));
-    return GLINT_OK;
-  }
-  GLINT_DISPATCH(s->dtype, push_vec_t, s, (const i64*)keys, nullptr, vals, n, flags, pick(s, stream));
+  return push_dev_gated(s, false, keys, nullptr, vals, n, flags, gate, stream);
 }
 
 int glint_mat_push_dev_gated(glint_shard_t s, const int64_t* rows, const int32_t* cols, const void* vals, int64_t n,
                              int flags, uint64_t* gate, void* stream) {
-  if (!s || n < 0 || !gate) return GLINT_EINVAL;
-  if (s->part.cols == 0) return GLINT_EINVAL;
-  ShardLock lk(s);
-  DeviceGuard g(s->device);
-  if (int rc = dev_order_after_host(s, (hipStream_t)stream)) return rc;
-  struct Gate {
-    glint_shard* s;
-    ~Gate() { s->gate = nullptr; }
-  } reset{s};
-  // a gate word in glint_host_alloc memory is read / written by the kernels through its device
-  // address, and the caller reads the verdict straight from host memory after its wait
-  u64* gd = (u64*)host_dev_ptr(gate, sizeof(u64), sizeof(u64));
-  s->gate = gd ? gd : (u64*)gate;
-  if (n == 0 && (flags & GLINT_PUSH_VALIDATE)) {  // nothing to check: the verdict is "none rejected"
-    HIPCHK(hipMemsetAsync(s->gate, 0, sizeof(u64), pick(s, stream)));
-    return GLINT_OK;
-  }
-  GLINT_DISPATCH(s->dtype, push_mat_t, s, (const i64*)rows, cols, vals, n, flags, pick(s, stream));
+  return push_dev_gated(s, true, rows, cols, vals, n, flags, gate, stream);
 }
 
 int glint_vec_push_dev_shards(glint_shard_t* shards, int m, const int64_t* keys, const void* vals, int64_t n,
@@ -1593,53 +1597,40 @@ int glint_vec_push_dev_shards(glint_shard_t* shards, int m, const int64_t* keys,
 }
 
 int glint_vec_pull_dev(glint_shard_t s, const int64_t* keys, void* out, int64_t n, void* stream) {
-  if (!s || n < 0) return GLINT_EINVAL;
-  if (s->part.cols != 0) return GLINT_EINVAL;
-  ShardLock lk(s);
-  DeviceGuard g(s->device);
-  if (int rc = dev_order_after_host(s, (hipStream_t)stream)) return rc;
-  GLINT_DISPATCH(s->dtype, launch_vec_pull, s, (const i64*)keys, out, n, pick(s, stream));
+  return dev_call(s, elem_args(s, false, n), stream, [&](hipStream_t st) -> int {
+    GLINT_DISPATCH(s->dtype, launch_vec_pull, s, (const i64*)keys, out, n, st);
+  });
 }
 
 int glint_mat_pull_dev(glint_shard_t s, const int64_t* rows, const int32_t* cols, void* out, int64_t n,
                        void* stream) {
-  if (!s || n < 0) return GLINT_EINVAL;
-  if (s->part.cols == 0) return GLINT_EINVAL;
-  ShardLock lk(s);
-  DeviceGuard g(s->device);
-  if (int rc = dev_order_after_host(s, (hipStream_t)stream)) return rc;
-  GLINT_DISPATCH(s->dtype, launch_mat_pull, s, (const i64*)rows, cols, out, n, pick(s, stream));
+  return dev_call(s, elem_args(s, true, n), stream, [&](hipStream_t st) -> int {
+    GLINT_DISPATCH(s->dtype, launch_mat_pull, s, (const i64*)rows, cols, out, n, st);
+  });
 }
 
 int glint_mat_pull_rows_dev(glint_shard_t s, const int64_t* rows, void* out, int64_t n, void* stream) {
-  if (!s || n < 0) return GLINT_EINVAL;
-  if (s->part.cols == 0) return GLINT_EINVAL;
-  ShardLock lk(s);
-  DeviceGuard g(s->device);
-  if (int rc = dev_order_after_host(s, (hipStream_t)stream)) return rc;
-  GLINT_DISPATCH(s->dtype, launch_mat_pull_rows, s, (const i64*)rows, out, n, pick(s, stream));
+  return dev_call(s, elem_args(s, true, n), stream, [&](hipStream_t st) -> int {
+    GLINT_DISPATCH(s->dtype, launch_mat_pull_rows, s, (const i64*)rows, out, n, st);
+  });
 }
 
 int glint_mat_push_rows_dev(glint_shard_t s, const int64_t* rows, const void* vals, int64_t n, int flags,
                             void* stream) {
-  if (int rc = push_rows_args(s, rows, vals, n, flags)) return rc;
-  if (n == 0) return GLINT_OK;
-  ShardLock lk(s);
-  DeviceGuard g(s->device);
-  if (int rc = dev_order_after_host(s, (hipStream_t)stream)) return rc;
-  GLINT_DISPATCH(s->dtype, push_rows, s, (const i64*)rows, vals, n, flags, pick(s, stream));
+  const int args_rc = push_rows_args(s, rows, vals, n, flags);
+  if (args_rc == GLINT_OK && n == 0) return GLINT_OK;
+  return dev_call(s, args_rc, stream, [&](hipStream_t st) -> int {
+    GLINT_DISPATCH(s->dtype, push_rows, s, (const i64*)rows, vals, n, flags, st);
+  });
 }
 
 int glint_mat_pull_rows_sparse_dev(glint_shard_t s, const int64_t* rows, int64_t n, int64_t* row_ptr,
                                    int32_t* out_cols, void* out_vals, int64_t cap, void* stream) {
-  if (int rc = pull_sparse_args(s, rows, n, row_ptr, out_cols, out_vals, cap)) return rc;
-  ShardLock lk(s);
-  DeviceGuard g(s->device);
-  if (int rc = dev_order_after_host(s, (hipStream_t)stream)) return rc;
-  hipStream_t st = pick(s, stream);
-  int rc = [&]() -> int { GLINT_DISPATCH(s->dtype, sparse_count_scan, s, (const i64*)rows, n, (i64*)row_ptr, st); }();
-  if (rc) return rc;
-  GLINT_DISPATCH(s->dtype, sparse_emit, s, (const i64*)rows, n, (const i64*)row_ptr, out_cols, out_vals, cap, st);
+  return dev_call(s, pull_sparse_args(s, rows, n, row_ptr, out_cols, out_vals, cap), stream, [&](hipStream_t st) -> int {
+    int rc = [&]() -> int { GLINT_DISPATCH(s->dtype, sparse_count_scan, s, (const i64*)rows, n, (i64*)row_ptr, st); }();
+    if (rc) return rc;
+    GLINT_DISPATCH(s->dtype, sparse_emit, s, (const i64*)rows, n, (const i64*)row_ptr, out_cols, out_vals, cap, st);
+  });
 }
 
 }  // extern "C"
@@ -2370,8 +2361,7 @@ int host_push(glint_shard* s, bool mat, const int64_t* keys, const int32_t* cols
   if (n == 0) return GLINT_OK;
   ShardLock lk(s);
   DeviceGuard g(s->device);
-  int rc = refuse_slab(s);
-  if (rc == GLINT_OK) rc = order_after_dev(s);
+  int rc = host_enter(s, HostEntry::Order);
   if (rc) return rc;
   if (batchable(s, n)) {  // Akka-sized: into the open batch (read in place by the kernel), then wait
     u64 ticket = 0;
@@ -2398,10 +2388,7 @@ int host_push(glint_shard* s, bool mat, const int64_t* keys, const int32_t* cols
       GLINT_DISPATCH(s->dtype, push_vec_t, s, (const i64*)st.p[0], nullptr, st.p[1], n, hflags, s->stream);
     }();
   }
-  if (rc) {
-    (void)hipStreamSynchronize(s->stream);  // the staging buffers stay busy until the stream drains
-    return rc;
-  }
+  if (rc) return launch_failed(s, rc);
   return finish(s);
 }
 
@@ -2412,9 +2399,7 @@ int host_pull(glint_shard* s, int kind, const int64_t* keys, const int32_t* cols
   if (n == 0) return GLINT_OK;
   ShardLock lk(s);
   DeviceGuard g(s->device);
-  int rc = refuse_slab(s);
-  if (rc == GLINT_OK) rc = ring_flush_locked(s);
-  if (rc == GLINT_OK) rc = order_after_dev(s);
+  int rc = host_enter(s, HostEntry::FlushOrder);
   if (rc) return rc;
   if (n <= GLINT_ZERO_COPY_MAX && pull_bytes(s, kind, n) <= kRingAnswerMax) {
     // Akka-sized: one workgroup reads the keys from a mapped pinned ring slot, writes the answer into
@@ -2425,7 +2410,7 @@ int host_pull(glint_shard* s, int kind, const int64_t* keys, const int32_t* cols
     if (rc) return rc;
     return ring_wait_locked(s, ticket, nullptr);
   }
-  const size_t out_bytes = (size_t)n * s->vsize * (kind == 2 ? (size_t)s->part.cols : 1);
+  const size_t out_bytes = pull_bytes(s, kind, n);
   Staged st;
   const void* src[2] = {keys, cols};
   size_t bytes[2] = {(size_t)n * 8, kind == 1 ? (size_t)n * 4 : 0};
@@ -2445,10 +2430,7 @@ int host_pull(glint_shard* s, int kind, const int64_t* keys, const int32_t* cols
       GLINT_DISPATCH(s->dtype, launch_mat_pull_rows, s, (const i64*)st.p[0], d_out, n, s->stream);
     }();
   }
-  if (rc) {
-    (void)hipStreamSynchronize(s->stream);
-    return rc;
-  }
+  if (rc) return launch_failed(s, rc);
   if (st.pinned) {  // answer into the pinned block behind the inputs, then one CPU copy out
     char* h_out = (char*)s->h_stage + st.in_bytes;
     HIPCHK(hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, s->stream));
@@ -2466,9 +2448,7 @@ int host_pull(glint_shard* s, int kind, const int64_t* keys, const int32_t* cols
 int host_push_rows(glint_shard* s, const int64_t* rows, const void* vals, int64_t n, int flags) {
   ShardLock lk(s);
   DeviceGuard g(s->device);
-  int rc = refuse_slab(s);
-  if (rc == GLINT_OK) rc = order_after_dev(s);
-  if (rc == GLINT_OK) rc = ring_flush_locked(s);
+  int rc = host_enter(s, HostEntry::OrderFlush);
   if (rc == GLINT_OK) rc = reject_if_bad(s, rows, nullptr, n);
   if (rc) return rc;
   Staged st;
@@ -2480,10 +2460,7 @@ int host_push_rows(glint_shard* s, const int64_t* rows, const void* vals, int64_
   rc = [&]() -> int {
     GLINT_DISPATCH(s->dtype, push_rows, s, (const i64*)st.p[0], st.p[1], n, flags | kPushHostSequential, s->stream);
   }();
-  if (rc) {
-    (void)hipStreamSynchronize(s->stream);  // the staging buffers stay busy until the stream drains
-    return rc;
-  }
+  if (rc) return launch_failed(s, rc);
   return finish(s);
 }
 
@@ -2495,9 +2472,7 @@ int host_pull_rows_sparse(glint_shard* s, const int64_t* rows, int64_t n, int64_
                           void* out_vals, int64_t cap, int64_t* nnz) {
   ShardLock lk(s);
   DeviceGuard g(s->device);
-  int rc = refuse_slab(s);
-  if (rc == GLINT_OK) rc = order_after_dev(s);
-  if (rc == GLINT_OK) rc = ring_flush_locked(s);
+  int rc = host_enter(s, HostEntry::OrderFlush);
   if (rc == GLINT_OK) rc = reject_if_bad(s, rows, nullptr, n);
   if (rc) return rc;
   if (n == 0) {
@@ -2514,10 +2489,7 @@ int host_pull_rows_sparse(glint_shard* s, const int64_t* rows, int64_t n, int64_
   HostCall hc(s);  // (every row was checked: nothing is recorded)
   const i64* d_rows = (const i64*)st.p[0];
   rc = [&]() -> int { GLINT_DISPATCH(s->dtype, sparse_count_scan, s, d_rows, n, (i64*)d_ptr, s->stream); }();
-  if (rc) {
-    (void)hipStreamSynchronize(s->stream);  // the staging buffers stay busy until the stream drains
-    return rc;
-  }
+  if (rc) return launch_failed(s, rc);
   HIPCHK(hipMemcpyAsync(row_ptr, d_ptr, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s->stream));
   HIPCHK(hipStreamSynchronize(s->stream));
   const i64 total = row_ptr[n];
@@ -2532,10 +2504,7 @@ int host_pull_rows_sparse(glint_shard* s, const int64_t* rows, int64_t n, int64_
   rc = [&]() -> int {
     GLINT_DISPATCH(s->dtype, sparse_emit, s, d_rows, n, (const i64*)d_ptr, d_cols, (void*)d_vals, m, s->stream);
   }();
-  if (rc) {
-    (void)hipStreamSynchronize(s->stream);
-    return rc;
-  }
+  if (rc) return launch_failed(s, rc);
   HIPCHK(hipMemcpyAsync(out_cols, d_cols, (size_t)m * 4, hipMemcpyDeviceToHost, s->stream));
   HIPCHK(hipMemcpyAsync(out_vals, d_vals, (size_t)m * s->vsize, hipMemcpyDeviceToHost, s->stream));
   return finish(s);

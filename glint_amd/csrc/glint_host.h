@@ -87,18 +87,9 @@ struct glint_shard {
   // bin_hot_reduce) for the next push instead of by memsets; initialised once when allocated
   void* d_hot = nullptr;
   size_t bin_bytes = 0;
-  // binned front end (glint_bin.hip push_binned): 0 plain, 1 plain + hot-element split, 2 chunk dedup
-  // (+ hot split). What the last dedup push measured decides: chunk_ratio = records it kept of the cold
-  // records that entered its hash table (1.0 = dedup merged nothing), hot_frac = share of the tail
-  // taken by the hot elements. A dedup push re-measures every 16 pushes. The measurements reach the
-  // host only at sync points (latch_hints), so a device-resident caller that never calls
-  // glint_shard_sync keeps the no-history default: the plain front end (ratio 1.0: dedup merged
-  // nothing), with a dedup probe every 16 pushes.
-  double bin_chunk_ratio = 1.0;
-  double bin_hot_frac = 0.0;
-  uint32_t bin_pushes = 0;
-  int bin_last_front = 0;        // the front end of the last binned push
-  u32 hot_age = 0;               // binned pushes since the wide hot table was last sampled (0: never)
+  // binned front end (glint_bin.hip push_binned): what its choice between the plain, hot-split and
+  // dedup front ends goes by (glint_push_plan.h; advanced by bin_front_next, glint_bin_plan.h)
+  BinFrontState bin_front;
   // pinned host staging for host-pointer calls (grow-only, <= pinned_stage_max()): the caller's
   // arrays are memcpy'd in and cross PCIe in one DMA; pull answers come back the same way
   void* h_stage = nullptr;
@@ -290,7 +281,6 @@ struct DeviceGuard {
   } while (0)
 
 inline size_t dtype_size(int dt) { return (dt == GLINT_I32 || dt == GLINT_F32) ? 4 : 8; }
-inline size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
 inline bool aligned(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
 
 inline int grow(void** buf, size_t* cap, size_t need) {
@@ -355,28 +345,6 @@ inline int order_after_dev(glint_shard* s) {
   return GLINT_OK;
 }
 
-// Brackets one kernel launch with events on its stream when profiling is on.
-struct ProfScope {
-  glint_shard* s;
-  int id;
-  hipStream_t st;
-  hipEvent_t b = nullptr, e = nullptr;
-  ProfScope(glint_shard* s_, int id_, hipStream_t st_) : s(s_), id(id_), st(st_) {
-    if (!s->prof) return;
-    if (hipEventCreate(&b) != hipSuccess || hipEventCreate(&e) != hipSuccess) {
-      (void)hipGetLastError();
-      b = e = nullptr;
-      return;
-    }
-    (void)hipEventRecord(b, st);
-  }
-  ~ProfScope() {
-    if (!b) return;
-    (void)hipEventRecord(e, st);
-    s->prof_ev[id].emplace_back(b, e);
-  }
-};
-
 // Launches one kernel. With profiling on, its start/stop events ride on the kernel's own dispatch
 // packet (hipExtLaunchKernel), so timing adds no marker packets and no gaps to the stream; a
 // bracketing hipEventRecord pair costs ~8 us of stream time per kernel here.
@@ -397,6 +365,25 @@ inline hipError_t launch_k(glint_shard* s, int id, void (*kernel)(KArgs...), uns
   }
   if (b) s->prof_ev[id].emplace_back(b, e);
   return err;
+}
+
+// A run of launches timed as one entry of `id` (the binned pipeline): with profiling on, span_begin
+// records an event on the stream in front of the run and span_end one behind it.
+typedef std::pair<hipEvent_t, hipEvent_t> ProfSpan;
+inline ProfSpan span_begin(glint_shard* s, hipStream_t st) {
+  ProfSpan p(nullptr, nullptr);
+  if (!s->prof) return p;
+  if (hipEventCreate(&p.first) != hipSuccess || hipEventCreate(&p.second) != hipSuccess) {
+    (void)hipGetLastError();
+    return ProfSpan(nullptr, nullptr);
+  }
+  (void)hipEventRecord(p.first, st);
+  return p;
+}
+inline void span_end(glint_shard* s, int id, hipStream_t st, const ProfSpan& p) {
+  if (!p.first) return;
+  (void)hipEventRecord(p.second, st);
+  s->prof_ev[id].push_back(p);
 }
 
 inline void prof_drain(glint_shard* s) {
@@ -423,7 +410,7 @@ inline void latch_hints(glint_shard* s) {
   s->hint_bin = __atomic_load_n(s->h_hint + 1, __ATOMIC_ACQUIRE);
   s->hint_bin_cold = __atomic_load_n(s->h_hint + 2, __ATOMIC_ACQUIRE);
   s->hint_head = __atomic_load_n(s->h_hint + 3, __ATOMIC_ACQUIRE);
-  s->hint_bin_front = s->bin_last_front;  // the stream has drained: the hint is the last binned push's
+  s->hint_bin_front = s->bin_front.last_front;  // the stream has drained: the hint is the last binned push's
 }
 
 // The error state a launch of this call records into: a host-pointer call's own, or the one
