@@ -11,6 +11,8 @@ Mirrors the reference's client factory and asynchronous models, minus the Akka t
 * ``BigMatrix.push/pull`` -- AsyncBigMatrix (AsyncBigMatrix.scala:53-170), including the row pull.
 * ``BigMatrix.pushRows`` -- an extension with no AsyncBigMatrix counterpart: the row pull's write
   side, whole rows added without expanding them into (row, col, value) triplets.
+* ``BigMatrix.pullSum`` -- an extension: the sums of groups of rows, reduced on the shards
+  (PartialMatrix.getRowsSum) and combined per group in partition-index order.
 
 Out-of-range keys raise ``IndexOutOfBoundsException`` before any shard is touched, as the
 reference's ``partitioner.partition`` does synchronously inside ``mapPartitions``.
@@ -170,6 +172,44 @@ class BigMatrix:
         # entry e of the answer belongs to request i = its row; it is entry e - indptr[i] of that request
         take = np.repeat(src0 - indptr[:-1], counts) + np.arange(base, dtype=np.int64)
         return indptr, np.concatenate(part_cols)[take], np.concatenate(part_vals)[take]
+
+    def pullSum(self, rows, offsets) -> np.ndarray:
+        """The sums of groups of rows (an extension): ``offsets`` has g + 1 entries, non-decreasing from
+        0 to len(rows); row k of the (g, cols) answer is the sum of ``rows[offsets[k]:offsets[k+1]]``, an
+        empty group zeros. Bucketed by partition as ``pull``; each non-empty partition answers one
+        PartialMatrix.getRowsSum over the sub-groups of its own rows, each in the caller's order.
+
+        Order of the additions: inside a partition strictly the caller's, left to right from the first
+        row's stored bits; then, per group, the partials of the partitions that hold at least one of its
+        rows are added in partition-index order, starting from the first such partial (not from zero).
+        With one partition that is the strict caller order; with several it is partition-major, caller's
+        order inside a partition. Deterministic either way; Int/Long wrap."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        if offsets.size < 1 or offsets[0] != 0 or offsets[-1] != rows.size or (np.diff(offsets) < 0).any():
+            raise ValueError("offsets must be non-decreasing from 0 to len(rows)")
+        g = offsets.size - 1
+        owner = self.partitioner.partition_indices(rows)
+        order, off = bucket(owner, len(self.shards))
+        group = np.repeat(np.arange(g, dtype=np.int64), np.diff(offsets))  # the group of every record
+        out = np.zeros((g, self.cols), dtype=self.shards[0].np_dtype)
+        started = np.zeros(g, dtype=bool)  # groups that already hold a partition's partial
+        for p, sh in enumerate(self.shards):
+            idx = order[off[p]:off[p + 1]]  # caller's order, so its groups are non-decreasing
+            if idx.size:
+                sub = np.zeros(g + 1, dtype=np.int64)
+                np.cumsum(np.bincount(group[idx], minlength=g), out=sub[1:])
+                part = np.asarray(sh.getRowsSum(rows[idx], sub), dtype=out.dtype)
+                has = np.diff(sub) > 0
+                first, more = has & ~started, has & started
+                out[first] = part[first]
+                out[more] = out[more] + part[more]
+                started |= has
+        return out
+
+    def pullAverage(self, rows, offsets) -> np.ndarray:
+        """pullSum over each group's length (1 for an empty group); Float/Double models."""
+        return self.pullSum(rows, offsets) / np.maximum(np.diff(offsets), 1).astype(self.shards[0].np_dtype)[:, None]
 
     def destroy(self) -> bool:
         for sh in self.shards:

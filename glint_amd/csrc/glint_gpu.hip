@@ -1202,6 +1202,16 @@ inline int pull_sparse_args(const glint_shard* s, const void* rows, int64_t n, c
   return GLINT_OK;
 }
 
+// argument checks of glint_mat_pull_rows_sum / _dev: a matrix shard, 31-bit row and group counts, the
+// arrays present when they have elements (grp_ptr always: it has g + 1)
+inline int pull_sum_args(const glint_shard* s, const void* rows, int64_t n, const void* grp_ptr, int64_t g,
+                         const void* out) {
+  if (!s || s->part.cols == 0) return GLINT_EINVAL;
+  if (n < 0 || g < 0 || n >= ((i64)1 << 31) || g >= ((i64)1 << 31)) return GLINT_EINVAL;
+  if (!grp_ptr || (n > 0 && !rows) || (g > 0 && !out)) return GLINT_EINVAL;
+  return GLINT_OK;
+}
+
 // argument check of the element-wise device-resident calls: a vector (matrix) shard, n >= 0
 inline int elem_args(const glint_shard* s, bool mat, int64_t n) {
   if (!s || n < 0) return GLINT_EINVAL;
@@ -1268,7 +1278,7 @@ std::atomic<unsigned> g_env_gen{1};
 
 extern "C" {
 
-int glint_version(void) { return 300; }  // 0.3.0: glint_mat_pull_rows_sparse / _dev, GLINT_K_PULL_ROWS_SPARSE
+int glint_version(void) { return 400; }  // 0.4.0: glint_mat_pull_rows_sum / _dev, GLINT_K_PULL_ROWS_SUM
 
 int glint_reload_env(void) {
   g_env_gen.fetch_add(1, std::memory_order_acq_rel);
@@ -1630,6 +1640,15 @@ int glint_mat_pull_rows_sparse_dev(glint_shard_t s, const int64_t* rows, int64_t
     int rc = [&]() -> int { GLINT_DISPATCH(s->dtype, sparse_count_scan, s, (const i64*)rows, n, (i64*)row_ptr, st); }();
     if (rc) return rc;
     GLINT_DISPATCH(s->dtype, sparse_emit, s, (const i64*)rows, n, (const i64*)row_ptr, out_cols, out_vals, cap, st);
+  });
+}
+
+int glint_mat_pull_rows_sum_dev(glint_shard_t s, const int64_t* rows, int64_t n, const int64_t* grp_ptr, int64_t g,
+                                void* out, void* stream) {
+  const int args_rc = pull_sum_args(s, rows, n, grp_ptr, g, out);
+  if (args_rc == GLINT_OK && g == 0) return GLINT_OK;
+  return dev_call(s, args_rc, stream, [&](hipStream_t st) -> int {
+    GLINT_DISPATCH(s->dtype, pull_rows_sum, s, (const i64*)rows, n, (const i64*)grp_ptr, g, out, st);
   });
 }
 
@@ -2510,6 +2529,36 @@ int host_pull_rows_sparse(glint_shard* s, const int64_t* rows, int64_t n, int64_
   return finish(s);
 }
 
+// glint_mat_pull_rows_sum: grp_ptr and every row are checked before anything is staged (a rejected call
+// writes nothing), then rows and grp_ptr are staged, the one kernel sums into device scratch (the
+// shard's deterministic-path scratch) and g * cols values come back -- never n * cols.
+int host_pull_rows_sum(glint_shard* s, const int64_t* rows, int64_t n, const int64_t* grp_ptr, int64_t g, void* out) {
+  if (grp_ptr[0] != 0 || grp_ptr[g] != n) return GLINT_EINVAL;
+  for (i64 k = 0; k < g; ++k)
+    if (grp_ptr[k + 1] < grp_ptr[k]) return GLINT_EINVAL;
+  if (g == 0) return GLINT_OK;
+  ShardLock lk(s);
+  DeviceGuard dg(s->device);
+  int rc = host_enter(s, HostEntry::OrderFlush);
+  if (rc == GLINT_OK) rc = reject_if_bad(s, rows, nullptr, n);
+  if (rc) return rc;
+  Staged st;
+  const void* src[2] = {rows, grp_ptr};
+  size_t bytes[2] = {(size_t)n * 8, (size_t)(g + 1) * 8};
+  rc = stage(s, src, bytes, 2, st, 0, nullptr);
+  if (rc) return rc;
+  const size_t out_bytes = (size_t)g * (size_t)s->part.cols * s->vsize;
+  rc = grow(&s->d_det, &s->det_bytes, out_bytes);
+  if (rc) return launch_failed(s, rc);
+  HostCall hc(s);  // (every row was checked: nothing is recorded)
+  rc = [&]() -> int {
+    GLINT_DISPATCH(s->dtype, pull_rows_sum, s, (const i64*)st.p[0], n, (const i64*)st.p[1], g, s->d_det, s->stream);
+  }();
+  if (rc) return launch_failed(s, rc);
+  HIPCHK(hipMemcpyAsync(out, s->d_det, out_bytes, hipMemcpyDeviceToHost, s->stream));
+  return finish(s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2550,6 +2599,12 @@ int glint_mat_pull_rows_sparse(glint_shard_t s, const int64_t* rows, int64_t n, 
                                void* out_vals, int64_t cap, int64_t* nnz) {
   if (int rc = pull_sparse_args(s, rows, n, row_ptr, out_cols, out_vals, cap)) return rc;
   return host_pull_rows_sparse(s, rows, n, row_ptr, out_cols, out_vals, cap, nnz);
+}
+
+int glint_mat_pull_rows_sum(glint_shard_t s, const int64_t* rows, int64_t n, const int64_t* grp_ptr, int64_t g,
+                            void* out) {
+  if (int rc = pull_sum_args(s, rows, n, grp_ptr, g, out)) return rc;
+  return host_pull_rows_sum(s, rows, n, grp_ptr, g, out);
 }
 
 // RequestSerializer.fromBinary (RequestSerializer.scala:59-130) for the push messages, applied

@@ -487,4 +487,9 @@ int sparse_count_scan(glint_shard* s, const i64* rows, i64 n, i64* row_ptr, hipS
 template <typename V>
 int sparse_emit(glint_shard* s, const i64* rows, i64 n, const i64* row_ptr, int32_t* out_cols, void* out_vals,
                 i64 cap, hipStream_t st);
+// grouped row-sum pull (glint_rowsum.hip), instantiated for the same V: out[k] (g x cols, dense) = the
+// left-to-right sum of rows[grp_ptr[k] .. grp_ptr[k+1]), device pointers; rows outside the partition
+// count as zeros and are recorded in err_of(s). One launch on st, no host synchronisation.
+template <typename V>
+int pull_rows_sum(glint_shard* s, const i64* rows, i64 n, const i64* grp_ptr, i64 g, void* out, hipStream_t st);
 }  // namespace glint

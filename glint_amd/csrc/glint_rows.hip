@@ -73,41 +73,6 @@ __global__ __launch_bounds__(kTPB) void rows_runs_kernel(const u32* __restrict__
   }
 }
 
-// A lane's part of a row slice: VPL values. WIDE: one 16-B access at column c (VPL * sizeof(V) == 16,
-// cols a multiple of VPL, the row 16-B aligned); else element k at column c + 64 k, so that each
-// wave instruction covers 64 consecutive elements.
-template <typename V, int VPL, bool WIDE>
-__device__ __forceinline__ void slice_load(V (&x)[VPL], const V* __restrict__ row, i64 c, i64 cols) {
-  typedef __attribute__((ext_vector_type(4))) unsigned int U4;
-  if (WIDE) {
-    U4 q = {0u, 0u, 0u, 0u};
-    if (c < cols) q = *reinterpret_cast<const U4*>(row + c);
-    __builtin_memcpy(x, &q, 16);
-  } else {
-#pragma unroll
-    for (int k = 0; k < VPL; ++k) {
-      const i64 cc = c + (i64)k * 64;
-      x[k] = cc < cols ? row[cc] : V(0);
-    }
-  }
-}
-
-template <typename V, int VPL, bool WIDE>
-__device__ __forceinline__ void slice_store(const V (&x)[VPL], V* row, i64 c, i64 cols) {
-  typedef __attribute__((ext_vector_type(4))) unsigned int U4;
-  if (WIDE) {
-    U4 q;
-    __builtin_memcpy(&q, x, 16);
-    if (c < cols) *reinterpret_cast<U4*>(row + c) = q;
-  } else {
-#pragma unroll
-    for (int k = 0; k < VPL; ++k) {
-      const i64 cc = c + (i64)k * 64;
-      if (cc < cols) row[cc] = x[k];
-    }
-  }
-}
-
 // Records [start, start + len) of the sorted list, folded in list order into one slice of row `drow`.
 // ATOMIC (a chunk of a split run): the chunk's partial sum is added with device-scope atomics, each
 // wave instruction over 64 consecutive elements; every chunk of that run does the same, so no plain

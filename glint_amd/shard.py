@@ -535,6 +535,43 @@ class PartialMatrix(_Shard):
             cols, vals = cols[:nnz.value].copy(), vals[:nnz.value].copy()
         return indptr, cols, vals
 
+    def getRowsSum(self, rows, offsets, out=None, sync: bool = True):
+        """The sums of groups of requested rows as one (g, cols) array (an extension;
+        glint_mat_pull_rows_sum*): ``offsets`` has g + 1 int64 entries, non-decreasing from 0 to
+        len(rows), and group k is ``rows[offsets[k]:offsets[k+1]]``. Row k of the answer is the
+        left-to-right sum of the group's rows in the shard's type, ``((r0 + r1) + r2) + ...`` in the
+        caller's order, starting from the first row's stored bits: a group of one row is getRows of
+        that row bit for bit, an empty group is zeros, Int/Long wrap. Rows may repeat.
+
+        Host arrays: only the (g, cols) sums cross the link; a row outside the partition raises and
+        nothing is written. Device tensors: one stream-ordered launch on the current stream; a row
+        outside the partition counts as zeros and is raised by the sync (``sync=True``, or a later
+        ``sync()``); ``offsets`` values are clamped to [0, len(rows)] by the kernel."""
+        if _is_torch_cuda(rows):
+            import torch
+            n = rows.numel()
+            if not _is_torch_cuda(offsets) or offsets.dtype != torch.int64 or not offsets.is_contiguous() \
+                    or offsets.device != rows.device or offsets.numel() < 1:
+                raise TypeError("offsets: expected a contiguous int64 CUDA tensor of g + 1 entries on rows' device")
+            g = offsets.numel() - 1
+            if out is None:
+                out = torch.empty((g, self.cols), dtype=self.torch_dtype, device=rows.device)
+            self._check_dev(n, rows, out=out, out_elems=g * self.cols)
+            rc = self.lib.glint_mat_pull_rows_sum_dev(self.handle, rows.data_ptr(), n, offsets.data_ptr(), g,
+                                                      out.data_ptr(), self._stream_of(rows))
+            check(rc, self.handle)
+            if sync:
+                self.sync(self._stream_of(rows))
+            return out
+        r = _host(rows, np.int64).reshape(-1)
+        o = _host(offsets, np.int64).reshape(-1)
+        if o.size < 1:
+            raise ValueError("offsets needs g + 1 entries")
+        res = self._host_out(out, (o.size - 1, self.cols))
+        check(self.lib.glint_mat_pull_rows_sum(self.handle, r.ctypes.data, r.size, o.ctypes.data, o.size - 1,
+                                               res.ctypes.data), self.handle)
+        return res
+
     def push_wire(self, payload: bytes, deterministic: bool = False) -> int:
         buf = (C.c_uint8 * len(payload)).from_buffer_copy(payload)
         mid = C.c_int32()

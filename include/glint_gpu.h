@@ -189,6 +189,27 @@ int glint_mat_pull_rows_sparse(glint_shard_t shard, const int64_t* rows, int64_t
  * more requests scans in two levels, of more than its square in three (tests size their cases by it). */
 #define GLINT_SPARSE_SCAN_TILE 1024
 
+/* Grouped row-sum pull (an extension: later forks of the reference grew pullSum / pullAverage over row
+ * groups; this version has none): the sums of groups of requested rows, reduced next to the data so that
+ * g x cols values answer a request that names n rows.
+ *   grp_ptr   g + 1 int64, non-decreasing, grp_ptr[0] = 0 and grp_ptr[g] = n: group k is
+ *             rows[grp_ptr[k] .. grp_ptr[k+1]);
+ *   out       g x cols values of the shard's type, dense row-major (NO pitch).
+ * out[k][c] is the left-to-right sum of element c of the group's rows, in the shard's type and in the
+ * caller's order: ((r0 + r1) + r2) + ... The first row's stored bits are the first term, not 0 + r0, so a
+ * group of one row is glint_mat_pull_rows bit for bit (-0.0, a NaN's payload and sign and subnormals come
+ * back unchanged); an empty group is all +0 / 0; Int and Long wrap. A row may occur several times in a
+ * group, and in several groups. The answer is deterministic: no atomics, and no group is split. There
+ * are no flags: the order is strict in every mode.
+ * GLINT_EINVAL: a NULL or vector shard, n < 0, g < 0, n >= 2^31, g >= 2^31, a NULL grp_ptr, NULL rows
+ * with n > 0, NULL out with g > 0 and -- in this host call only, before anything is staged -- a grp_ptr
+ * that breaks the rule above. g == 0 writes nothing and returns GLINT_OK. Every row is checked first: a
+ * row outside the partition returns GLINT_EOUTOFRANGE (its index in `rows` in glint_shard_last_error) with
+ * nothing written to out. Staged to the device: rows and grp_ptr; copied back: g * cols values -- never
+ * n * cols. */
+int glint_mat_pull_rows_sum(glint_shard_t shard, const int64_t* rows, int64_t n, const int64_t* grp_ptr,
+                            int64_t g, void* out);
+
 /* After GLINT_EOUTOFRANGE: index (within the failing call) of the first rejected record. */
 int glint_shard_last_error(glint_shard_t shard, int64_t* first_bad_record);
 
@@ -220,6 +241,16 @@ int glint_mat_push_rows_dev(glint_shard_t shard, const int64_t* rows, const void
  * answered. Scratch is the shard's growable device scratch. */
 int glint_mat_pull_rows_sparse_dev(glint_shard_t shard, const int64_t* rows, int64_t n, int64_t* row_ptr,
                                    int32_t* out_cols, void* out_vals, int64_t cap, void* stream);
+
+/* glint_mat_pull_rows_sum, device-resident: the same sums, stream-ordered on `stream` with no host
+ * synchronisation, one launch. A row outside the partition contributes a row of zeros (as
+ * glint_mat_pull_rows_dev answers such a row with zeros) and is reported by glint_shard_sync as the
+ * lowest such index in `rows`; every other row is summed. grp_ptr is not checked on the host: the kernel
+ * clamps every grp_ptr value it reads to [0, n] and treats end < start as an empty group, so a malformed
+ * grp_ptr can never index outside `rows`. `out` 16-B aligned takes the 16-B path when cols allow;
+ * any element-aligned `out` gives the same bits. */
+int glint_mat_pull_rows_sum_dev(glint_shard_t shard, const int64_t* rows, int64_t n, const int64_t* grp_ptr,
+                                int64_t g, void* out, void* stream);
 
 /* glint_vec_push_dev / glint_mat_push_dev behind a device-side gate: the push is enqueued at once,
  * and when it runs it applies NOTHING if the 64-bit device word *gate is nonzero (a route status word,
@@ -398,7 +429,8 @@ enum glint_kernel_id {
   /* the sparse row pull (glint_mat_pull_rows_sparse*): its emit kernel, and under the same id its
    * count kernel and the launches of its scan, so the sum is the pull's whole device time */
   GLINT_K_PULL_ROWS_SPARSE = 9,
-  GLINT_K_COUNT = 10
+  GLINT_K_PULL_ROWS_SUM = 10, /* the grouped row-sum pull (glint_mat_pull_rows_sum*): one launch per call */
+  GLINT_K_COUNT = 11
 };
 int glint_prof_enable(glint_shard_t shard, int on);
 int glint_prof_read(glint_shard_t shard, int kernel_id, double* total_ms, int64_t* launches);

@@ -3,9 +3,11 @@ device-resident rates from HIP events around each kernel (glint_prof_*), and hos
 ("end-to-end": pageable host memory -> H2D -> kernels -> D2H) rates by wall clock, which is what
 the JNI shim sees. One JSON line per measurement on stdout.
 
-    python tools/measure_paths.py [--quick] [--sparse]
+    python tools/measure_paths.py [--quick] [--sparse] [--rowsum]
 
 --sparse runs only the sparse-row-pull leg (dense getRows against getRowsSparse on a cfg5 shard).
+--rowsum runs only the grouped row-sum leg (getRowsSum against a dense row pull plus a reduction by the
+caller, on a cfg5 shard).
 """
 import ctypes as C
 import json
@@ -134,9 +136,96 @@ def sparse_leg(rng):
     msh.destroy()
 
 
+def rowsum_leg(rng):
+    """cfg5 per GPU: a 2^17 x 512 Double shard, 2^14 Zipf(1.0) rows in groups of 1, 16 and 128 rows, and
+    as one group of all of them (the known limit: one dependent chain per column slice). Host:
+    glint_mat_pull_rows_sum against glint_mat_pull_rows into a reused buffer + np.add.reduceat, wall time.
+    Device: glint_mat_pull_rows_sum_dev against glint_mat_pull_rows_dev into an n x cols buffer +
+    torch.index_add_ into g x cols, HIP events around each call. The baselines never run the code under
+    test."""
+    shard_rows, cols, n = 1 << 17, 512, 1 << 14
+    msh = glint_amd.PartialMatrix(glint_amd.RangePartition(0, 0, shard_rows), cols, "double", 0)
+    h = msh.handle
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(7)
+    all_rows = torch.arange(shard_rows, dtype=torch.int64, device=dev)
+    for r0 in range(0, shard_rows, 1 << 14):  # fill in slices of whole rows
+        vv = torch.rand((1 << 14, cols), dtype=torch.float64, device=dev, generator=gen) + 0.5
+        msh.updateRows(all_rows[r0:r0 + (1 << 14)].contiguous(), vv)
+    del vv
+    rows = zipf_keys(rng, shard_rows, n, 1.0)
+    qr = torch.from_numpy(rows).to(dev)
+    dense_out = np.empty((n, cols), np.float64)
+    d_dense = torch.empty((n, cols), dtype=torch.float64, device=dev)
+
+    def dev_ms(fn, reps=10):
+        fn()
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / reps
+
+    for glen in (1, 16, 128, n):
+        g = n // glen
+        offsets = np.arange(g + 1, dtype=np.int64) * glen
+        d_off = torch.from_numpy(offsets).to(dev)
+        group = torch.arange(g, dtype=torch.int64, device=dev).repeat_interleave(glen)
+        sum_out = np.empty((g, cols), np.float64)
+        base_out = np.empty((g, cols), np.float64)
+        d_sum = torch.empty((g, cols), dtype=torch.float64, device=dev)
+        d_base = torch.empty((g, cols), dtype=torch.float64, device=dev)
+        reps = 5
+
+        def host_base():
+            assert lib.glint_mat_pull_rows(h, rows.ctypes.data, dense_out.ctypes.data, n) == 0
+            np.add.reduceat(dense_out, offsets[:-1], axis=0, out=base_out)
+
+        def host_sum():
+            assert lib.glint_mat_pull_rows_sum(h, rows.ctypes.data, n, offsets.ctypes.data, g, sum_out.ctypes.data) == 0
+
+        def dev_base():
+            lib.glint_mat_pull_rows_dev(h, qr.data_ptr(), d_dense.data_ptr(), n, stream)
+            d_base.zero_()
+            d_base.index_add_(0, group, d_dense)
+
+        def dev_sum():
+            lib.glint_mat_pull_rows_sum_dev(h, qr.data_ptr(), n, d_off.data_ptr(), g, d_sum.data_ptr(), stream)
+
+        t_base = wall(host_base, reps)
+        t_pull_only = wall(lambda: lib.glint_mat_pull_rows(h, rows.ctypes.data, dense_out.ctypes.data, n), reps)
+        t_sum = wall(host_sum, reps)
+        ms_base = dev_ms(dev_base)
+        ms_pull_only = dev_ms(lambda: lib.glint_mat_pull_rows_dev(h, qr.data_ptr(), d_dense.data_ptr(), n, stream))
+        ms_sum = dev_ms(dev_sum)
+        timed(dev_sum, 10, h)
+        k_sum = kernel_ms(h, N.GLINT_K_PULL_ROWS_SUM)
+        msh.sync(stream)
+        # the two answers agree up to the order of the additions (reduceat and index_add_ choose their own)
+        err_host = float(np.max(np.abs(sum_out - base_out) / np.abs(base_out)))
+        err_dev = float(torch.max(torch.abs(d_sum - d_base) / torch.abs(d_base)).item())
+        same = bool(np.array_equal(d_sum.cpu().numpy(), sum_out))
+        emit(op="mat_pull_rows_sum", pattern="zipf1.0 rows", shape=[shard_rows, cols], rows=n, group_len=glen, groups=g,
+             host_baseline_ms=t_base * 1e3, host_baseline_pull_only_ms=t_pull_only * 1e3, host_sum_ms=t_sum * 1e3,
+             host_speedup=t_base / t_sum, host_baseline_bytes_back=n * cols * 8, host_sum_bytes_back=g * cols * 8,
+             dev_baseline_ms=ms_base, dev_baseline_pull_only_ms=ms_pull_only, dev_sum_ms=ms_sum,
+             dev_speedup=ms_base / ms_sum, dev_sum_kernel_ms=k_sum,
+             max_rel_diff_host=err_host, max_rel_diff_dev=err_dev, host_and_device_sums_identical=same,
+             note="host_*: C calls into reused pageable numpy buffers, synchronous, mean of 5; baseline = "
+                  "glint_mat_pull_rows + np.add.reduceat. dev_*: HIP events around 10 calls, mean; baseline = "
+                  "glint_mat_pull_rows_dev + zero_ + torch.index_add_. dev_sum_kernel_ms: the kernel alone (glint_prof)")
+    msh.destroy()
+
+
 def main():
     if "--sparse" in sys.argv:
         sparse_leg(np.random.default_rng(42))
+        return
+    if "--rowsum" in sys.argv:
+        rowsum_leg(np.random.default_rng(42))
         return
     lg = 26 if QUICK else 28
     n = 1 << lg
