@@ -13,6 +13,9 @@ Mirrors the reference's client factory and asynchronous models, minus the Akka t
   side, whole rows added without expanding them into (row, col, value) triplets.
 * ``BigMatrix.pullSum`` -- an extension: the sums of groups of rows, reduced on the shards
   (PartialMatrix.getRowsSum) and combined per group in partition-index order.
+* ``BigMatrix.pullDot`` -- an extension: the dot products of rows with caller vectors (or with
+  themselves), reduced over the columns on the shards (PartialMatrix.getRowsDot); a row lives in one
+  partition, so the answers are only scattered back.
 
 Out-of-range keys raise ``IndexOutOfBoundsException`` before any shard is touched, as the
 reference's ``partitioner.partition`` does synchronously inside ``mapPartitions``.
@@ -210,6 +213,31 @@ class BigMatrix:
     def pullAverage(self, rows, offsets) -> np.ndarray:
         """pullSum over each group's length (1 for an empty group); Float/Double models."""
         return self.pullSum(rows, offsets) / np.maximum(np.diff(offsets), 1).astype(self.shards[0].np_dtype)[:, None]
+
+    def pullDot(self, rows, x=None) -> np.ndarray:
+        """The dot products of rows with caller vectors (an extension), reduced on the shards: ``x`` of
+        shape (cols,) gives (n,), ``x`` of shape (q, cols) gives (n, q) with ``out[i, j] = dot(row
+        rows[i], x[j])``, and ``x=None`` the (n,) squared norms. Bucketed by partition as ``pull``; one
+        PartialMatrix.getRowsDot per non-empty partition, each with the same ``x``, and the answers
+        scattered back to the caller's positions. A row lives in one partition, so nothing is combined
+        here: the bits are the shard's."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        dtype = self.shards[0].np_dtype
+        shape = (rows.size,)
+        if x is not None:
+            x = np.ascontiguousarray(x, dtype=dtype)
+            if x.shape != (self.cols,) and not (x.ndim == 2 and x.shape[1] == self.cols and x.shape[0] >= 1):
+                raise ValueError(f"x: shape {x.shape}, expected ({self.cols},) or (q, {self.cols})")
+            if x.ndim == 2:
+                shape = (rows.size, x.shape[0])
+        owner = self.partitioner.partition_indices(rows)
+        order, off = bucket(owner, len(self.shards))
+        out = np.zeros(shape, dtype=dtype)
+        for p, sh in enumerate(self.shards):
+            idx = order[off[p]:off[p + 1]]
+            if idx.size:
+                out[idx] = sh.getRowsDot(rows[idx], x)
+        return out
 
     def destroy(self) -> bool:
         for sh in self.shards:

@@ -1212,6 +1212,17 @@ inline int pull_sum_args(const glint_shard* s, const void* rows, int64_t n, cons
   return GLINT_OK;
 }
 
+// argument checks of glint_mat_pull_rows_dot / _dev: a matrix shard, a 31-bit request count, 1 to
+// GLINT_DOT_MAX_QUERIES queries, x present unless it is the self-dot (q == 1), the arrays present when
+// they have elements
+inline int pull_dot_args(const glint_shard* s, const void* rows, int64_t n, const void* x, int64_t q, const void* out) {
+  if (!s || s->part.cols == 0) return GLINT_EINVAL;
+  if (n < 0 || n >= ((i64)1 << 31)) return GLINT_EINVAL;
+  if (q < 1 || q > GLINT_DOT_MAX_QUERIES || (!x && q != 1)) return GLINT_EINVAL;
+  if (n > 0 && (!rows || !out)) return GLINT_EINVAL;
+  return GLINT_OK;
+}
+
 // argument check of the element-wise device-resident calls: a vector (matrix) shard, n >= 0
 inline int elem_args(const glint_shard* s, bool mat, int64_t n) {
   if (!s || n < 0) return GLINT_EINVAL;
@@ -1278,7 +1289,7 @@ std::atomic<unsigned> g_env_gen{1};
 
 extern "C" {
 
-int glint_version(void) { return 400; }  // 0.4.0: glint_mat_pull_rows_sum / _dev, GLINT_K_PULL_ROWS_SUM
+int glint_version(void) { return 500; }  // 0.5.0: glint_mat_pull_rows_dot / _dev, GLINT_K_PULL_ROWS_DOT
 
 int glint_reload_env(void) {
   g_env_gen.fetch_add(1, std::memory_order_acq_rel);
@@ -1649,6 +1660,15 @@ int glint_mat_pull_rows_sum_dev(glint_shard_t s, const int64_t* rows, int64_t n,
   if (args_rc == GLINT_OK && g == 0) return GLINT_OK;
   return dev_call(s, args_rc, stream, [&](hipStream_t st) -> int {
     GLINT_DISPATCH(s->dtype, pull_rows_sum, s, (const i64*)rows, n, (const i64*)grp_ptr, g, out, st);
+  });
+}
+
+int glint_mat_pull_rows_dot_dev(glint_shard_t s, const int64_t* rows, int64_t n, const void* x, int64_t q, void* out,
+                                void* stream) {
+  const int args_rc = pull_dot_args(s, rows, n, x, q, out);
+  if (args_rc == GLINT_OK && n == 0) return GLINT_OK;
+  return dev_call(s, args_rc, stream, [&](hipStream_t st) -> int {
+    GLINT_DISPATCH(s->dtype, pull_rows_dot, s, (const i64*)rows, n, x, q, out, st);
   });
 }
 
@@ -2559,6 +2579,33 @@ int host_pull_rows_sum(glint_shard* s, const int64_t* rows, int64_t n, const int
   return finish(s);
 }
 
+// glint_mat_pull_rows_dot: every row is checked before anything is staged (a rejected call writes
+// nothing), then rows and x are staged in one block, the one kernel writes its n * q dots into device
+// scratch (the shard's deterministic-path scratch) and those come back -- never n * cols values.
+int host_pull_rows_dot(glint_shard* s, const int64_t* rows, int64_t n, const void* x, int64_t q, void* out) {
+  ShardLock lk(s);
+  DeviceGuard dg(s->device);
+  int rc = host_enter(s, HostEntry::OrderFlush);
+  if (rc == GLINT_OK) rc = reject_if_bad(s, rows, nullptr, n);
+  if (rc) return rc;
+  Staged st;
+  const void* src[2] = {rows, x};
+  size_t bytes[2] = {(size_t)n * 8, x ? (size_t)q * (size_t)s->part.cols * s->vsize : 0};
+  rc = stage(s, src, bytes, 2, st, 0, nullptr);
+  if (rc) return rc;
+  const size_t out_bytes = (size_t)n * (size_t)q * s->vsize;
+  rc = grow(&s->d_det, &s->det_bytes, out_bytes);
+  if (rc) return launch_failed(s, rc);
+  HostCall hc(s);  // (every row was checked: nothing is recorded)
+  rc = [&]() -> int {
+    GLINT_DISPATCH(s->dtype, pull_rows_dot, s, (const i64*)st.p[0], n, x ? (const void*)st.p[1] : nullptr, q, s->d_det,
+                   s->stream);
+  }();
+  if (rc) return launch_failed(s, rc);
+  HIPCHK(hipMemcpyAsync(out, s->d_det, out_bytes, hipMemcpyDeviceToHost, s->stream));
+  return finish(s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2605,6 +2652,12 @@ int glint_mat_pull_rows_sum(glint_shard_t s, const int64_t* rows, int64_t n, con
                             void* out) {
   if (int rc = pull_sum_args(s, rows, n, grp_ptr, g, out)) return rc;
   return host_pull_rows_sum(s, rows, n, grp_ptr, g, out);
+}
+
+int glint_mat_pull_rows_dot(glint_shard_t s, const int64_t* rows, int64_t n, const void* x, int64_t q, void* out) {
+  if (int rc = pull_dot_args(s, rows, n, x, q, out)) return rc;
+  if (n == 0) return GLINT_OK;
+  return host_pull_rows_dot(s, rows, n, x, q, out);
 }
 
 // RequestSerializer.fromBinary (RequestSerializer.scala:59-130) for the push messages, applied

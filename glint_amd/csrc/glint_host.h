@@ -492,4 +492,10 @@ int sparse_emit(glint_shard* s, const i64* rows, i64 n, const i64* row_ptr, int3
 // count as zeros and are recorded in err_of(s). One launch on st, no host synchronisation.
 template <typename V>
 int pull_rows_sum(glint_shard* s, const i64* rows, i64 n, const i64* grp_ptr, i64 g, void* out, hipStream_t st);
+// row dot-product pull (glint_rowdot.hip), instantiated for the same V: out[i*q + j] (n x q, dense) = the
+// dot of row rows[i] with x[j] (q x cols, dense; nullptr with q == 1: the row with itself), device
+// pointers, in the order include/glint_gpu.h fixes; rows outside the partition answer zeros and are
+// recorded in err_of(s). One launch on st, no host synchronisation.
+template <typename V>
+int pull_rows_dot(glint_shard* s, const i64* rows, i64 n, const void* x, i64 q, void* out, hipStream_t st);
 }  // namespace glint

@@ -92,8 +92,8 @@ __device__ __forceinline__ int32_t g2l(const PartDesc& p, i64 key) {
   return (int32_t)((key - (i64)p.cidx) / (i64)p.cparts);
 }
 
-// Row slices, shared by the row push's fold (glint_rows.hip) and the grouped row-sum pull
-// (glint_rowsum.hip).
+// Row slices, shared by the row push's fold (glint_rows.hip), the grouped row-sum pull
+// (glint_rowsum.hip) and the row dot pull (glint_rowdot.hip).
 // A lane's part of a row slice: VPL values. WIDE: one 16-B access at column c (VPL * sizeof(V) == 16,
 // cols a multiple of VPL, the row 16-B aligned); else element k at column c + 64 k, so that each
 // wave instruction covers 64 consecutive elements.

@@ -572,6 +572,58 @@ class PartialMatrix(_Shard):
                                                res.ctypes.data), self.handle)
         return res
 
+    def getRowsDot(self, rows, x=None, out=None, sync: bool = True):
+        """The dot products of the requested rows with caller vectors (an extension;
+        glint_mat_pull_rows_dot*), reduced over the columns on the shard: ``x`` of shape (cols,) gives an
+        (n,) array, ``x`` of shape (q, cols) an (n, q) array with ``out[i, j] = dot(row rows[i], x[j])``,
+        and ``x=None`` the (n,) squared norms ``dot(row, row)``. All arithmetic is in the shard's type:
+        Int/Long wrap; Float/Double products are rounded before they are added (no fused multiply-add)
+        and added in the fixed order include/glint_gpu.h states, which depends on the type and cols
+        only. Rows may repeat; answers keep the caller's order.
+
+        Host arrays: only the n x q dots cross the link; a row outside the partition raises and
+        nothing is written. Device tensors: one stream-ordered launch on the current stream; a row
+        outside the partition answers zeros and is raised by the sync (``sync=True``, or a later
+        ``sync()``)."""
+        if _is_torch_cuda(rows):
+            import torch
+            n = rows.numel()
+            q, shape = 1, (n,)
+            if x is not None:
+                if not _is_torch_cuda(x) or x.dtype != self.torch_dtype or not x.is_contiguous() \
+                        or x.device != rows.device:
+                    raise TypeError(f"x: expected a contiguous {self.torch_dtype} CUDA tensor on rows' device")
+                q, shape = self._dot_shape(tuple(x.shape), n)
+            if out is None:
+                out = torch.empty(shape, dtype=self.torch_dtype, device=rows.device)
+            self._check_dev(n, rows, out=out, out_elems=n * q)
+            rc = self.lib.glint_mat_pull_rows_dot_dev(self.handle, rows.data_ptr(), n,
+                                                      x.data_ptr() if x is not None else None, q, out.data_ptr(),
+                                                      self._stream_of(rows))
+            check(rc, self.handle)
+            if sync:
+                self.sync(self._stream_of(rows))
+            return out
+        r = _host(rows, np.int64).reshape(-1)
+        q, shape = 1, (r.size,)
+        if x is not None:
+            x = _host(x, self.np_dtype)
+            q, shape = self._dot_shape(x.shape, r.size)
+        res = self._host_out(out, shape)
+        check(self.lib.glint_mat_pull_rows_dot(self.handle, r.ctypes.data, r.size,
+                                               x.ctypes.data if x is not None else None, q, res.ctypes.data),
+              self.handle)
+        return res
+
+    def _dot_shape(self, xshape, n: int):
+        """(q, answer shape) of getRowsDot for query vectors of shape ``xshape``."""
+        if xshape == (self.cols,):
+            return 1, (n,)
+        if len(xshape) == 2 and xshape[1] == self.cols and 1 <= xshape[0] <= N.GLINT_DOT_MAX_QUERIES:
+            return xshape[0], (n, xshape[0])
+        raise ValueError(f"x: shape {tuple(xshape)}, expected ({self.cols},) or (q, {self.cols}) with "
+                         f"1 <= q <= {N.GLINT_DOT_MAX_QUERIES}")
+
     def push_wire(self, payload: bytes, deterministic: bool = False) -> int:
         buf = (C.c_uint8 * len(payload)).from_buffer_copy(payload)
         mid = C.c_int32()

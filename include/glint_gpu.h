@@ -210,6 +210,37 @@ int glint_mat_pull_rows_sparse(glint_shard_t shard, const int64_t* rows, int64_t
 int glint_mat_pull_rows_sum(glint_shard_t shard, const int64_t* rows, int64_t n, const int64_t* grp_ptr,
                             int64_t g, void* out);
 
+/* Row dot-product pull (an extension: the reference has no such message): the requested rows times
+ * vectors the caller sends, reduced over the columns next to the data, so that n x q values answer a
+ * request that names n rows -- scores of candidate rows against query vectors, or row norms.
+ *   x     q x cols values of the shard's type, dense row-major; NULL only with q == 1: the self-dot,
+ *         out[i] = sum over c of row[c] * row[c], the squared norm;
+ *   out   n x q values of the shard's type, dense: out[i*q + j] = dot(row rows[i], x[j]).
+ * Requests keep the caller's order; a row requested twice is answered twice. x must not overlap out.
+ * There are no flags and no atomics: the answer is deterministic.
+ * Arithmetic, all in the shard's type. Int/Long: products and sums wrap (low 32 / 64 bits), so every
+ * order gives the same bits. Float/Double: the order is part of the contract, and it is a function of
+ * (type, cols) only -- never of pointer alignment, q, how the queries are spread over waves, or the
+ * grid. Let E = 16 / sizeof(V) when cols * sizeof(V) is a multiple of 16, else E = 1. Column c belongs to
+ * lane L = (c / E) % 64. Each of the 64 lanes starts from +0 and adds its columns' products in ascending
+ * c, acc = acc + (row[c] * x[c]), the product rounded before the add (no fused multiply-add). The 64
+ * lane sums are then combined by the xor butterfly: for d in 32, 16, 8, 4, 2, 1: acc[L] = acc[L] +
+ * acc[L ^ d] (IEEE addition commutes, so every lane ends with the same value: the answer). Subnormal
+ * products and sums are kept; infinities and NaN follow IEEE (inf * 0 is NaN; a NaN's payload and sign
+ * are unspecified); a zero result's sign is what that order gives.
+ * Only `cols` elements of a row are read, never the pitch padding.
+ * GLINT_EINVAL: a NULL or vector shard, n < 0, n >= 2^31, q < 1, q > GLINT_DOT_MAX_QUERIES, a NULL x with
+ * q != 1, NULL rows or NULL out with n > 0. n == 0 writes nothing and returns GLINT_OK. Every row is
+ * checked first: a row outside the partition returns GLINT_EOUTOFRANGE (its index in
+ * glint_shard_last_error) with nothing staged and nothing written to out. Staged to the device: rows and
+ * x; copied back: n * q values -- never n * cols. */
+#define GLINT_DOT_MAX_QUERIES 1024
+/* Queries one wave answers for its row when q > 1 (tests size their cases by it; the bits do not
+ * depend on it). */
+#define GLINT_DOT_QUERY_TILE 4
+int glint_mat_pull_rows_dot(glint_shard_t shard, const int64_t* rows, int64_t n, const void* x, int64_t q,
+                            void* out);
+
 /* After GLINT_EOUTOFRANGE: index (within the failing call) of the first rejected record. */
 int glint_shard_last_error(glint_shard_t shard, int64_t* first_bad_record);
 
@@ -251,6 +282,15 @@ int glint_mat_pull_rows_sparse_dev(glint_shard_t shard, const int64_t* rows, int
  * any element-aligned `out` gives the same bits. */
 int glint_mat_pull_rows_sum_dev(glint_shard_t shard, const int64_t* rows, int64_t n, const int64_t* grp_ptr,
                                 int64_t g, void* out, void* stream);
+
+/* glint_mat_pull_rows_dot, device-resident: the same dots in the same order, stream-ordered on `stream`
+ * with no host synchronisation, one launch. A row outside the partition answers q zeros without a load
+ * (as glint_mat_pull_rows_dev answers such a row with zeros) and is reported by glint_shard_sync as the
+ * lowest such request index; every other row is answered. x is read by 16 B when it is 16-B aligned
+ * (and cols allow), else element by element: the same bits either way. out is written element by
+ * element. */
+int glint_mat_pull_rows_dot_dev(glint_shard_t shard, const int64_t* rows, int64_t n, const void* x, int64_t q,
+                                void* out, void* stream);
 
 /* glint_vec_push_dev / glint_mat_push_dev behind a device-side gate: the push is enqueued at once,
  * and when it runs it applies NOTHING if the 64-bit device word *gate is nonzero (a route status word,
@@ -430,7 +470,8 @@ enum glint_kernel_id {
    * count kernel and the launches of its scan, so the sum is the pull's whole device time */
   GLINT_K_PULL_ROWS_SPARSE = 9,
   GLINT_K_PULL_ROWS_SUM = 10, /* the grouped row-sum pull (glint_mat_pull_rows_sum*): one launch per call */
-  GLINT_K_COUNT = 11
+  GLINT_K_PULL_ROWS_DOT = 11, /* the row dot-product pull (glint_mat_pull_rows_dot*): one launch per call */
+  GLINT_K_COUNT = 12
 };
 int glint_prof_enable(glint_shard_t shard, int on);
 int glint_prof_read(glint_shard_t shard, int kernel_id, double* total_ms, int64_t* launches);

@@ -3,10 +3,12 @@ device-resident rates from HIP events around each kernel (glint_prof_*), and hos
 ("end-to-end": pageable host memory -> H2D -> kernels -> D2H) rates by wall clock, which is what
 the JNI shim sees. One JSON line per measurement on stdout.
 
-    python tools/measure_paths.py [--quick] [--sparse] [--rowsum]
+    python tools/measure_paths.py [--quick] [--sparse] [--rowsum] [--dot]
 
 --sparse runs only the sparse-row-pull leg (dense getRows against getRowsSparse on a cfg5 shard).
 --rowsum runs only the grouped row-sum leg (getRowsSum against a dense row pull plus a reduction by the
+caller, on a cfg5 shard).
+--dot runs only the row dot-product leg (getRowsDot against a dense row pull plus a matrix product by the
 caller, on a cfg5 shard).
 """
 import ctypes as C
@@ -60,6 +62,19 @@ def wall(fn, reps):
     for _ in range(reps):
         fn()
     return (time.perf_counter() - t0) / reps
+
+
+def dev_ms(fn, reps=10):
+    """Mean device time of fn: HIP events around `reps` calls, after one warm-up."""
+    fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps
 
 
 def emit(**kw):
@@ -158,17 +173,6 @@ def rowsum_leg(rng):
     dense_out = np.empty((n, cols), np.float64)
     d_dense = torch.empty((n, cols), dtype=torch.float64, device=dev)
 
-    def dev_ms(fn, reps=10):
-        fn()
-        torch.cuda.synchronize()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(reps):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        return a.elapsed_time(b) / reps
-
     for glen in (1, 16, 128, n):
         g = n // glen
         offsets = np.arange(g + 1, dtype=np.int64) * glen
@@ -220,7 +224,88 @@ def rowsum_leg(rng):
     msh.destroy()
 
 
+def dot_leg(rng):
+    """cfg5 per GPU: a 2^17 x 512 Double shard, 2^14 Zipf(1.0) rows against q = 1, 8 and 64 query vectors.
+    Host: glint_mat_pull_rows_dot into a reused buffer against glint_mat_pull_rows into a reused buffer +
+    rows @ x.T in numpy, wall time; the dense pull alone for scale. Device: glint_mat_pull_rows_dot_dev
+    against glint_mat_pull_rows_dev + torch.matmul, HIP events around each call; the dot kernel alone by its
+    prof id. The baselines never run the code under test; the answers are checked against them within
+    1e-9 of each element's sum of |products|."""
+    shard_rows, cols, n = 1 << 17, 512, 1 << 14
+    msh = glint_amd.PartialMatrix(glint_amd.RangePartition(0, 0, shard_rows), cols, "double", 0)
+    h = msh.handle
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(7)
+    all_rows = torch.arange(shard_rows, dtype=torch.int64, device=dev)
+    for r0 in range(0, shard_rows, 1 << 14):  # fill in slices of whole rows
+        vv = torch.rand((1 << 14, cols), dtype=torch.float64, device=dev, generator=gen) - 0.5
+        msh.updateRows(all_rows[r0:r0 + (1 << 14)].contiguous(), vv)
+    del vv
+    rows = zipf_keys(rng, shard_rows, n, 1.0)
+    qr = torch.from_numpy(rows).to(dev)
+    dense_out = np.empty((n, cols), np.float64)
+    d_dense = torch.empty((n, cols), dtype=torch.float64, device=dev)
+
+    for q in (1, 8, 64):
+        x = rng.standard_normal((q, cols))
+        d_x = torch.from_numpy(x).to(dev)
+        dot_out = np.empty((n, q), np.float64)
+        base_out = np.empty((n, q), np.float64)
+        d_dot = torch.empty((n, q), dtype=torch.float64, device=dev)
+        d_base = torch.empty((n, q), dtype=torch.float64, device=dev)
+        d_xt = d_x.t()
+        reps = 5
+
+        def host_base():
+            assert lib.glint_mat_pull_rows(h, rows.ctypes.data, dense_out.ctypes.data, n) == 0
+            np.matmul(dense_out, x.T, out=base_out)
+
+        def host_dot():
+            assert lib.glint_mat_pull_rows_dot(h, rows.ctypes.data, n, x.ctypes.data, q, dot_out.ctypes.data) == 0
+
+        def dev_base():
+            lib.glint_mat_pull_rows_dev(h, qr.data_ptr(), d_dense.data_ptr(), n, stream)
+            torch.matmul(d_dense, d_xt, out=d_base)
+
+        def dev_dot():
+            lib.glint_mat_pull_rows_dot_dev(h, qr.data_ptr(), n, d_x.data_ptr(), q, d_dot.data_ptr(), stream)
+
+        t_base = wall(host_base, reps)
+        t_pull_only = wall(lambda: lib.glint_mat_pull_rows(h, rows.ctypes.data, dense_out.ctypes.data, n), reps)
+        t_dot = wall(host_dot, reps)
+        ms_base = dev_ms(dev_base)
+        ms_pull_only = dev_ms(lambda: lib.glint_mat_pull_rows_dev(h, qr.data_ptr(), d_dense.data_ptr(), n, stream))
+        ms_dot = dev_ms(dev_dot)
+        timed(dev_dot, 10, h)
+        k_dot = kernel_ms(h, N.GLINT_K_PULL_ROWS_DOT)
+        msh.sync(stream)
+        # the answers agree up to the order of the additions: 1e-9 of each element's sum of |products|
+        bound = 1e-9 * np.matmul(np.abs(dense_out), np.abs(x.T))
+        d_dot_h = d_dot.cpu().numpy()
+        ok_host = bool((np.abs(dot_out - base_out) <= bound).all())
+        ok_dev = bool((np.abs(d_dot_h - d_base.cpu().numpy()) <= bound).all())
+        assert ok_host and ok_dev
+        emit(op="mat_pull_rows_dot", pattern="zipf1.0 rows", shape=[shard_rows, cols], rows=n, queries=q,
+             host_baseline_ms=t_base * 1e3, host_baseline_pull_only_ms=t_pull_only * 1e3, host_dot_ms=t_dot * 1e3,
+             host_speedup=t_base / t_dot, host_speedup_over_pull_only=t_pull_only / t_dot,
+             host_baseline_bytes_up=n * 8, host_baseline_bytes_back=n * cols * 8,
+             host_dot_bytes_up=n * 8 + q * cols * 8, host_dot_bytes_back=n * q * 8,
+             dev_baseline_ms=ms_base, dev_baseline_pull_only_ms=ms_pull_only, dev_dot_ms=ms_dot,
+             dev_speedup=ms_base / ms_dot, dev_dot_kernel_ms=k_dot,
+             dev_dot_row_bytes_read=n * cols * 8, dev_baseline_bytes=3 * n * cols * 8,
+             within_bound_host=ok_host, within_bound_dev=ok_dev,
+             host_and_device_dots_identical=bool(np.array_equal(d_dot_h, dot_out)),
+             note="host_*: C calls into reused pageable numpy buffers, synchronous, mean of 5; baseline = "
+                  "glint_mat_pull_rows + np.matmul(rows, x.T). dev_*: HIP events around 10 calls, mean; baseline = "
+                  "glint_mat_pull_rows_dev + torch.matmul (n x cols read, written and read again). "
+                  "dev_dot_kernel_ms: the kernel alone (glint_prof)")
+    msh.destroy()
+
+
 def main():
+    if "--dot" in sys.argv:
+        dot_leg(np.random.default_rng(42))
+        return
     if "--sparse" in sys.argv:
         sparse_leg(np.random.default_rng(42))
         return
