@@ -462,7 +462,7 @@ __device__ __forceinline__ u32 part_emit(const u32 (&ad)[P], const A (&va)[P], u
         dcnt[d] = excl;
       });
   ph.mark(pb + 1);
-  static_assert(kATPB <= kMaxDigit, "one chunk-table entry per thread");
+  static_assert(kMaxDigit <= kATPB, "one chunk-table entry per thread, for up to kMaxDigit buckets");
   // the chunk's column of the table (bucket-major rows of ctstride): one counted store per thread
   bput(ctb, ((u32)tid * ctstride + ctcol) * 4u, (u32)tid < g.nb, dcnt[tid] | (gcnt[tid] << 16));
 #pragma unroll
@@ -1475,6 +1475,8 @@ __global__ __launch_bounds__(kSTPB) __attribute__((amdgpu_waves_per_eu(8))) void
     if (t1 <= sp) Pw[t1] = p1;
     if (t0 < sp) Qw[t0] = q0;
     if (t1 < sp) Qw[t1] = q1;
+    // (an item of exactly kFWin chunks has kFWin + 1 prefixes: the last one is a third entry)
+    if (tid == 0 && sp == kFWin) Pw[kFWin] = Pb[cw.x + kFWin];
   }
   const u32 s0 = Bb[b] + d.y * item, s1 = Bb[b] + min(T[b], (d.y + 1) * item);
   const u32 nf1 = g.nf + 1;

@@ -20,7 +20,7 @@ constexpr int kMaxDigit = 1024;        // coarse buckets and fine slabs per buck
 #ifndef GLINT_PART_TPB
 #define GLINT_PART_TPB 1024
 #endif
-constexpr int kATPB = GLINT_PART_TPB;  // partition workgroup size (build-time knob: 1024 or 512)
+constexpr int kATPB = GLINT_PART_TPB;  // partition workgroup size (a knob in name: >= kMaxDigit, see part_emit)
 #ifndef GLINT_PART_PER
 #define GLINT_PART_PER 4
 #endif
