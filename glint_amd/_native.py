@@ -23,8 +23,10 @@ GLINT_K_PUSH_ROWS = 8
 GLINT_K_PULL_ROWS_SPARSE = 9
 GLINT_K_PULL_ROWS_SUM = 10
 GLINT_K_PULL_ROWS_DOT = 11
-GLINT_K_COUNT = 12
+GLINT_K_PUSH_ROWS_AXPY = 12
+GLINT_K_COUNT = 13
 GLINT_DOT_MAX_QUERIES, GLINT_DOT_QUERY_TILE = 1024, 4
+GLINT_AXPY_MAX_VECTORS = 64
 GLINT_ROUTE_RANGE, GLINT_ROUTE_CYCLIC = 0, 1
 GLINT_RING_SLOTS, GLINT_ZERO_COPY_MAX = 16, 4096
 GLINT_SPARSE_SCAN_TILE = 1024
@@ -56,6 +58,8 @@ SIGNATURES = {
     "glint_mat_pull_rows_sum_dev": (_I, [_P, _P, _I64, _P, _I64, _P, _P]),
     "glint_mat_pull_rows_dot": (_I, [_P, _P, _I64, _P, _I64, _P]),
     "glint_mat_pull_rows_dot_dev": (_I, [_P, _P, _I64, _P, _I64, _P, _P]),
+    "glint_mat_push_rows_axpy": (_I, [_P, _P, _I64, _P, _P, _I64, _I]),
+    "glint_mat_push_rows_axpy_dev": (_I, [_P, _P, _I64, _P, _P, _I64, _I, _P]),
     "glint_shard_last_error": (_I, [_P, C.POINTER(_I64)]),
     "glint_vec_push_dev": (_I, [_P, _P, _P, _I64, _I, _P]),
     "glint_vec_push_dev_gated": (_I, [_P, _P, _P, _I64, _I, _P, _P]),

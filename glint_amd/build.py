@@ -25,7 +25,7 @@ ORACLE_LIB = ORACLE_DIR / "build" / "libglint_oracle.so"
 CSRC = PKG / "csrc"
 HIP_SOURCES = [CSRC / "glint_gpu.hip", CSRC / "glint_sort.hip", CSRC / "glint_route.hip", CSRC / "glint_ordered.hip", CSRC / "glint_bin.hip",
                CSRC / "glint_exchange.hip", CSRC / "glint_rows.hip", CSRC / "glint_sparse.hip",
-               CSRC / "glint_rowsum.hip", CSRC / "glint_rowdot.hip"]
+               CSRC / "glint_rowsum.hip", CSRC / "glint_rowdot.hip", CSRC / "glint_rowaxpy.hip"]
 PLAN_HEADERS = [CSRC / "glint_push_plan.h", CSRC / "glint_bin_plan.h"]  # plain C++: the push planners
 HIP_HEADERS = [CSRC / "glint_kernels.h", CSRC / "glint_device.h", CSRC / "glint_host.h", ROOT / "include" / "glint_gpu.h",
                *PLAN_HEADERS]

@@ -11,6 +11,8 @@ Mirrors the reference's client factory and asynchronous models, minus the Akka t
 * ``BigMatrix.push/pull`` -- AsyncBigMatrix (AsyncBigMatrix.scala:53-170), including the row pull.
 * ``BigMatrix.pushRows`` -- an extension with no AsyncBigMatrix counterpart: the row pull's write
   side, whole rows added without expanding them into (row, col, value) triplets.
+* ``BigMatrix.pushAxpy`` -- an extension: rows += coefficients times caller vectors, the contribution
+  rows rebuilt on the shards (PartialMatrix.updateRowsAxpy) instead of sent.
 * ``BigMatrix.pullSum`` -- an extension: the sums of groups of rows, reduced on the shards
   (PartialMatrix.getRowsSum) and combined per group in partition-index order.
 * ``BigMatrix.pullDot`` -- an extension: the dot products of rows with caller vectors (or with
@@ -122,6 +124,29 @@ class BigMatrix:
             idx = order[off[p]:off[p + 1]]
             if idx.size:
                 sh.updateRows(rows[idx], values[idx], deterministic=deterministic)
+        return True
+
+    def pushAxpy(self, rows, coef, x, deterministic: bool = False) -> bool:
+        """Row axpy push (an extension): row rows[i] += sum over j of ``coef[i, j] * x[j]``, in the
+        caller's order -- ``pushRows`` of those contribution rows without building or sending them. ``x``
+        is (cols,) or (q, cols), ``coef`` (n,) (only with q == 1) or (n, q). Bucketed by partition as
+        ``pushRows``; one PartialMatrix.updateRowsAxpy per non-empty partition, with its rows and
+        coefficient rows in the caller's order and the same ``x``."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        dtype = self.shards[0].np_dtype
+        x = np.ascontiguousarray(x, dtype=dtype)
+        coef = np.ascontiguousarray(coef, dtype=dtype)
+        if x.shape != (self.cols,) and not (x.ndim == 2 and x.shape[1] == self.cols and x.shape[0] >= 1):
+            raise ValueError(f"x: shape {x.shape}, expected ({self.cols},) or (q, {self.cols})")
+        q = 1 if x.ndim == 1 else x.shape[0]
+        if coef.shape != (rows.size, q) and not (q == 1 and coef.shape == (rows.size,)):
+            raise ValueError(f"coef: shape {coef.shape}, expected ({rows.size}, {q})")
+        owner = self.partitioner.partition_indices(rows)
+        order, off = bucket(owner, len(self.shards))
+        for p, sh in enumerate(self.shards):
+            idx = order[off[p]:off[p + 1]]
+            if idx.size:
+                sh.updateRowsAxpy(rows[idx], coef[idx], x, deterministic=deterministic)
         return True
 
     def pull(self, rows, cols=None) -> np.ndarray:

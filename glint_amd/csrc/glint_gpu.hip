@@ -1191,6 +1191,15 @@ inline int push_rows_args(const glint_shard* s, const void* rows, const void* va
   return GLINT_OK;
 }
 
+// argument checks of glint_mat_push_rows_axpy / _dev: glint_mat_push_rows's, 1 to GLINT_AXPY_MAX_VECTORS
+// vectors, the three arrays present when there are records
+inline int push_axpy_args(const glint_shard* s, const void* rows, int64_t n, const void* coef, const void* x,
+                          int64_t q, int flags) {
+  if (int rc = push_rows_args(s, rows, coef, n, flags)) return rc;
+  if (q < 1 || q > GLINT_AXPY_MAX_VECTORS || (n > 0 && !x)) return GLINT_EINVAL;
+  return GLINT_OK;
+}
+
 // argument checks of glint_mat_pull_rows_sparse / _dev: a matrix shard, 31-bit request count, outputs
 // present unless the call only counts
 inline int pull_sparse_args(const glint_shard* s, const void* rows, int64_t n, const void* row_ptr,
@@ -1289,7 +1298,7 @@ std::atomic<unsigned> g_env_gen{1};
 
 extern "C" {
 
-int glint_version(void) { return 500; }  // 0.5.0: glint_mat_pull_rows_dot / _dev, GLINT_K_PULL_ROWS_DOT
+int glint_version(void) { return 600; }  // 0.6.0: glint_mat_push_rows_axpy / _dev, GLINT_K_PUSH_ROWS_AXPY
 
 int glint_reload_env(void) {
   g_env_gen.fetch_add(1, std::memory_order_acq_rel);
@@ -1669,6 +1678,15 @@ int glint_mat_pull_rows_dot_dev(glint_shard_t s, const int64_t* rows, int64_t n,
   if (args_rc == GLINT_OK && n == 0) return GLINT_OK;
   return dev_call(s, args_rc, stream, [&](hipStream_t st) -> int {
     GLINT_DISPATCH(s->dtype, pull_rows_dot, s, (const i64*)rows, n, x, q, out, st);
+  });
+}
+
+int glint_mat_push_rows_axpy_dev(glint_shard_t s, const int64_t* rows, int64_t n, const void* coef, const void* x,
+                                 int64_t q, int flags, void* stream) {
+  const int args_rc = push_axpy_args(s, rows, n, coef, x, q, flags);
+  if (args_rc == GLINT_OK && n == 0) return GLINT_OK;
+  return dev_call(s, args_rc, stream, [&](hipStream_t st) -> int {
+    GLINT_DISPATCH(s->dtype, push_rows_axpy, s, (const i64*)rows, n, coef, x, q, flags, st);
   });
 }
 
@@ -2606,9 +2624,41 @@ int host_pull_rows_dot(glint_shard* s, const int64_t* rows, int64_t n, const voi
   return finish(s);
 }
 
+// glint_mat_push_rows_axpy: every row is checked before anything is enqueued (a rejected message applies
+// nothing), then rows, coef and x are staged in one block -- n * 8 + (n * q + q * cols) values, never
+// n * cols -- and the push runs on the shard's stream in message order (kPushHostSequential). Nothing
+// comes back but the error state.
+int host_push_rows_axpy(glint_shard* s, const int64_t* rows, int64_t n, const void* coef, const void* x, int64_t q,
+                        int flags) {
+  ShardLock lk(s);
+  DeviceGuard g(s->device);
+  int rc = host_enter(s, HostEntry::OrderFlush);
+  if (rc == GLINT_OK) rc = reject_if_bad(s, rows, nullptr, n);
+  if (rc) return rc;
+  Staged st;
+  const void* src[3] = {rows, coef, x};
+  size_t bytes[3] = {(size_t)n * 8, (size_t)n * (size_t)q * s->vsize, (size_t)q * (size_t)s->part.cols * s->vsize};
+  rc = stage(s, src, bytes, 3, st, 0, nullptr);
+  if (rc) return rc;
+  HostCall hc(s);  // this call's rejected records are its own (d_err_host, read by finish)
+  rc = [&]() -> int {
+    GLINT_DISPATCH(s->dtype, push_rows_axpy, s, (const i64*)st.p[0], n, st.p[1], st.p[2], q,
+                   flags | kPushHostSequential, s->stream);
+  }();
+  if (rc) return launch_failed(s, rc);
+  return finish(s);
+}
+
 }  // namespace
 
 extern "C" {
+
+int glint_mat_push_rows_axpy(glint_shard_t s, const int64_t* rows, int64_t n, const void* coef, const void* x,
+                             int64_t q, int flags) {
+  if (int rc = push_axpy_args(s, rows, n, coef, x, q, flags)) return rc;
+  if (n == 0) return GLINT_OK;
+  return host_push_rows_axpy(s, rows, n, coef, x, q, flags);
+}
 
 int glint_vec_push(glint_shard_t s, const int64_t* keys, const void* vals, int64_t n, int flags) {
   if (!s) return GLINT_EINVAL;

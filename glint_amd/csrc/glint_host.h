@@ -478,6 +478,29 @@ int rs_sort(K* k0, V* v0, K* k1, V* v1, i64 m, int end_bit, u32* hist, u32* offs
 // whole-row matrix push (glint_rows.hip), instantiated for V in {int, long long, float, double}
 template <typename V>
 int push_rows(glint_shard* s, const i64* rows, const void* vals, i64 n, int flags, hipStream_t st);
+// The front end the row pushes share (glint_rows.hip): rows_prepare, rs_sort<u32, u32> and
+// rows_runs<SPLIT> over scratch laid out in s->d_det. Afterwards idx lists the records sorted by local
+// row, equal rows in push order, key their local rows, and items[0 .. *nitems) the work items {start,
+// length} over that list: one per distinct row, or per chunk of at most kRowsChunk records (marked
+// kRowsSplitBit in the length word) of a longer run when the sum's order is free (!strict). All device
+// pointers into s->d_det, valid until the shard's next call that uses that scratch.
+constexpr u32 kRowsChunk = 128;             // runs longer than this are split when the sum's order is free
+constexpr u32 kRowsSplitBit = 0x80000000u;  // item length word: a chunk of a split run
+struct RowsFront {
+  const u32* key;
+  const u32* idx;
+  const uint2* items;
+  const u32* nitems;
+  bool strict;  // message order kept: GLINT_PUSH_DETERMINISTIC, or a host call without GLINT_PUSH_UNORDERED
+};
+int rows_front(glint_shard* s, const i64* rows, i64 n, int flags, hipStream_t st, RowsFront* out);
+// row axpy push (glint_rowaxpy.hip), instantiated for the same V: row rows[i] += sum over j of
+// coef[i*q + j] * x[j] (coef n x q, x q x cols, dense, device pointers), in the order include/glint_gpu.h
+// fixes; rows outside the partition are skipped and recorded in err_of(s). The front end's launches and
+// one fold launch on st, no host synchronisation.
+template <typename V>
+int push_rows_axpy(glint_shard* s, const i64* rows, i64 n, const void* coef, const void* x, i64 q, int flags,
+                   hipStream_t st);
 // sparse row pull (glint_sparse.hip), instantiated for the same V. sparse_count_scan: row_ptr[0..n]
 // (device) = exclusive prefix of the requested rows' non-zero counts; rows outside the partition
 // count 0 and are recorded in err_of(s); the scan's scratch is s->d_det. sparse_emit: the entries

@@ -19,8 +19,7 @@
 namespace glint {
 
 constexpr int kRowsDepth = 8;     // contribution loads in flight per wave (the adds are the only chain)
-constexpr u32 kRowsChunk = 128;   // runs longer than this are split when the sum's order is free
-constexpr u32 kRowsSplitBit = 0x80000000u;  // item length word: a chunk of a split run
+// (kRowsChunk and kRowsSplitBit: glint_host.h, with rows_front)
 
 __global__ __launch_bounds__(kTPB) void rows_prepare_kernel(const i64* __restrict__ rows, i64 n, PartDesc part,
                                                             u32* __restrict__ key, u32* __restrict__ idx,
@@ -161,12 +160,9 @@ __global__ __launch_bounds__(kTPB) void rows_fold_kernel(const u32* __restrict__
 }
 
 // ---- host side ----------------------------------------------------------------------------------
-// Enqueues a row push of n records on st (no host synchronisation). Under the shard's lock.
-template <typename V>
-int push_rows(glint_shard* s, const i64* rows, const void* vals, i64 n, int flags, hipStream_t st) {
-  if (n <= 0) return GLINT_OK;
-  if (!rows || !vals) return GLINT_EINVAL;
-  if (n >= ((i64)1 << 32) - kSortTile) return GLINT_EINVAL;  // 32-bit record indices and sort offsets
+// The row pushes' shared front end (glint_host.h): scratch layout in s->d_det, then rows_prepare,
+// rs_sort and rows_runs on st. n > 0 and n < 2^32 - kSortTile (32-bit record indices and sort offsets).
+int rows_front(glint_shard* s, const i64* rows, i64 n, int flags, hipStream_t st, RowsFront* out) {
   const u32 sentinel = (u32)s->part.size;
   int end_bit = 1;
   while (end_bit < 32 && ((u64)1 << end_bit) <= (u64)sentinel) ++end_bit;
@@ -197,10 +193,23 @@ int push_rows(glint_shard* s, const i64* rows, const void* vals, i64 n, int flag
   rc = rs_sort<u32, u32>(key0, idx0, key1, idx1, n, end_bit, hist, offs, tot, st, &where);
   if (rc) return rc;
   const u32* key = where ? key1 : key0;
-  const u32* idx = where ? idx1 : idx0;
   if (strict) rows_runs_kernel<false><<<g, kTPB, 0, st>>>(key, n, sentinel, nitems, items);
   else rows_runs_kernel<true><<<g, kTPB, 0, st>>>(key, n, sentinel, nitems, items);
   HIPCHK(hipGetLastError());
+  *out = RowsFront{key, where ? idx1 : idx0, items, nitems, strict};
+  return GLINT_OK;
+}
+
+// Enqueues a row push of n records on st (no host synchronisation). Under the shard's lock.
+template <typename V>
+int push_rows(glint_shard* s, const i64* rows, const void* vals, i64 n, int flags, hipStream_t st) {
+  if (n <= 0) return GLINT_OK;
+  if (!rows || !vals) return GLINT_EINVAL;
+  if (n >= ((i64)1 << 32) - kSortTile) return GLINT_EINVAL;  // 32-bit record indices and sort offsets
+  RowsFront f;
+  int rc = rows_front(s, rows, n, flags, st, &f);
+  if (rc) return rc;
+  const bool strict = f.strict;
   const bool v16 = ((i64)s->part.cols * (i64)sizeof(V)) % 16 == 0 && aligned(vals, 16);
   const i64 slices = ((i64)s->part.cols * (i64)sizeof(V) + (v16 ? 1023 : 64 * (i64)sizeof(V) - 1)) /
                      (v16 ? 1024 : 64 * (i64)sizeof(V));
@@ -208,8 +217,8 @@ int push_rows(glint_shard* s, const i64* rows, const void* vals, i64 n, int flag
   void (*fold)(const u32*, const u32*, const uint2*, const u32*, const V*, V*, PartDesc) =
       v16 ? (strict ? rows_fold_kernel<V, true, false> : rows_fold_kernel<V, true, true>)
           : (strict ? rows_fold_kernel<V, false, false> : rows_fold_kernel<V, false, true>);
-  HIPCHK(launch_k(s, GLINT_K_PUSH_ROWS, fold, gf, kTPB, st, key, idx, (const uint2*)items, (const u32*)nitems,
-                  (const V*)vals, (V*)s->data, s->part));
+  HIPCHK(launch_k(s, GLINT_K_PUSH_ROWS, fold, gf, kTPB, st, f.key, f.idx, f.items, f.nitems, (const V*)vals,
+                  (V*)s->data, s->part));
   return GLINT_OK;
 }
 

@@ -437,6 +437,52 @@ class PartialMatrix(_Shard):
         check(self.lib.glint_mat_push_rows(self.handle, r.ctypes.data, v.ctypes.data, r.size, flags), self.handle)
         return True
 
+    def updateRowsAxpy(self, rows, coef, x, deterministic: bool = False, sync: bool = True,
+                       unordered: bool = False) -> bool:
+        """Row axpy push (an extension; glint_mat_push_rows_axpy*): row rows[i] += sum over j of
+        ``coef[i, j] * x[j]``, the contribution rows rebuilt on the shard instead of sent. ``x`` is
+        (cols,) or (q, cols); ``coef`` is (n,) (only with q == 1) or (n, q). It is ``updateRows`` with
+        ``values[i] = ((coef[i, 0] * x[0]) + (coef[i, 1] * x[1])) + ...`` in the shard's type, rounding for
+        rounding: every product is rounded before it is added (no fused multiply-add), j ascends, Int/Long
+        wrap. Order and errors as ``updateRows``: host arrays keep the push order for Float/Double unless
+        ``unordered`` and reject a message with a row outside the partition before anything is applied;
+        device tensors keep the order with ``deterministic``, skip such a row and raise at the sync."""
+        flags = _flags(deterministic, unordered)
+        if _is_torch_cuda(rows):
+            n = rows.numel()
+            for name, t in (("coef", coef), ("x", x)):
+                if not _is_torch_cuda(t) or t.dtype != self.torch_dtype or not t.is_contiguous() \
+                        or t.device != rows.device:
+                    raise TypeError(f"{name}: expected a contiguous {self.torch_dtype} CUDA tensor on rows' device")
+            q = self._axpy_q(tuple(x.shape), tuple(coef.shape), n)
+            self._check_dev(n, rows)
+            rc = self.lib.glint_mat_push_rows_axpy_dev(self.handle, rows.data_ptr(), n, coef.data_ptr(),
+                                                       x.data_ptr(), q, flags, self._stream_of(rows))
+            check(rc, self.handle)
+            if sync:
+                self.sync(self._stream_of(rows))
+            return True
+        r = _host(rows, np.int64).reshape(-1)
+        cf = _host(coef, self.np_dtype)
+        xs = _host(x, self.np_dtype)
+        q = self._axpy_q(xs.shape, cf.shape, r.size)
+        check(self.lib.glint_mat_push_rows_axpy(self.handle, r.ctypes.data, r.size, cf.ctypes.data, xs.ctypes.data, q,
+                                                flags), self.handle)
+        return True
+
+    def _axpy_q(self, xshape, cshape, n: int) -> int:
+        """q of updateRowsAxpy for vectors of shape ``xshape`` and coefficients of shape ``cshape``."""
+        if xshape == (self.cols,):
+            q = 1
+        elif len(xshape) == 2 and xshape[1] == self.cols and 1 <= xshape[0] <= N.GLINT_AXPY_MAX_VECTORS:
+            q = xshape[0]
+        else:
+            raise ValueError(f"x: shape {tuple(xshape)}, expected ({self.cols},) or (q, {self.cols}) with "
+                             f"1 <= q <= {N.GLINT_AXPY_MAX_VECTORS}")
+        if cshape != (n, q) and not (q == 1 and cshape == (n,)):
+            raise ValueError(f"coef: shape {tuple(cshape)}, expected ({n}, {q})" + (f" or ({n},)" if q == 1 else ""))
+        return q
+
     def get(self, rows, cols, out=None, sync: bool = True):
         """PartialMatrix.get (PartialMatrix.scala:55-65)."""
         if _is_torch_cuda(rows):

@@ -241,6 +241,31 @@ int glint_mat_pull_rows_sum(glint_shard_t shard, const int64_t* rows, int64_t n,
 int glint_mat_pull_rows_dot(glint_shard_t shard, const int64_t* rows, int64_t n, const void* x, int64_t q,
                             void* out);
 
+/* Row axpy push (an extension: the reference has no such message): the write half of a scoring step,
+ * whole rows += coefficients times vectors the caller sends, so that n*q + q*cols values cross the link
+ * instead of the n x cols outer product glint_mat_push_rows would need.
+ *   coef  n x q values of the shard's type, dense row-major;
+ *   x     q x cols values of the shard's type, dense row-major; 1 <= q <= GLINT_AXPY_MAX_VECTORS.
+ * For i in push order, for c in [0, cols): data[l(rows[i])][c] = data[l(rows[i])][c] + t_i[c], where
+ *   t_i[c] = ((coef[i][0] * x[0][c]) + (coef[i][1] * x[1][c])) + ... + (coef[i][q-1] * x[q-1][c]):
+ * j ascends, the first product is the first term (not 0 + product), every product is rounded before it is
+ * added (no fused multiply-add, neither inside t_i nor between t_i and the element), and all arithmetic is
+ * in the shard's type; Int/Long wrap. The call is therefore glint_mat_push_rows with vals[i] = t_i,
+ * rounding for rounding. That order is a function of the inputs only -- never of pointer alignment, q, how
+ * the vectors are tiled over registers, or the grid. Subnormal products and sums are kept; infinities and
+ * NaN follow IEEE (inf * 0 is NaN; a NaN's payload and sign are unspecified). Only `cols` elements of a
+ * row are read and written, never the pitch padding.
+ * Flags and errors are glint_mat_push_rows's: only GLINT_PUSH_DETERMINISTIC and GLINT_PUSH_UNORDERED are
+ * accepted; Float/Double sums of repeated rows keep the push order unless GLINT_PUSH_UNORDERED is given;
+ * every row is checked before anything is applied: on a row outside the partition nothing is applied
+ * (GLINT_EOUTOFRANGE, the record's index in glint_shard_last_error).
+ * GLINT_EINVAL: a NULL or vector shard, n < 0, n >= 2^32 - 2048, q < 1, q > GLINT_AXPY_MAX_VECTORS, any
+ * other flag, NULL rows, coef or x with n > 0. n == 0 launches nothing and returns GLINT_OK. Staged to the
+ * device: rows, coef and x in one block; nothing is copied back, and nothing of size n x cols exists. */
+#define GLINT_AXPY_MAX_VECTORS 64
+int glint_mat_push_rows_axpy(glint_shard_t shard, const int64_t* rows, int64_t n, const void* coef, const void* x,
+                             int64_t q, int flags);
+
 /* After GLINT_EOUTOFRANGE: index (within the failing call) of the first rejected record. */
 int glint_shard_last_error(glint_shard_t shard, int64_t* first_bad_record);
 
@@ -291,6 +316,16 @@ int glint_mat_pull_rows_sum_dev(glint_shard_t shard, const int64_t* rows, int64_
  * element. */
 int glint_mat_pull_rows_dot_dev(glint_shard_t shard, const int64_t* rows, int64_t n, const void* x, int64_t q,
                                 void* out, void* stream);
+
+/* glint_mat_push_rows_axpy, device-resident: the same contributions in the same order, stream-ordered on
+ * `stream` with no host synchronisation. A row outside the partition is skipped and reported by
+ * glint_shard_sync (the lowest such record index); the other rows are applied. Int/Long sums are exact.
+ * Float/Double: every t_i is bit-exact in every mode, and a row that occurs once in the push is bit-exact;
+ * sums of repeated rows keep the push order with GLINT_PUSH_DETERMINISTIC, else long lists may be split
+ * and their partial sums added unordered. x is read by 16 B when it is 16-B aligned (and cols allow), else
+ * element by element; coef element by element: the same bits either way. */
+int glint_mat_push_rows_axpy_dev(glint_shard_t shard, const int64_t* rows, int64_t n, const void* coef,
+                                 const void* x, int64_t q, int flags, void* stream);
 
 /* glint_vec_push_dev / glint_mat_push_dev behind a device-side gate: the push is enqueued at once,
  * and when it runs it applies NOTHING if the 64-bit device word *gate is nonzero (a route status word,
@@ -471,7 +506,9 @@ enum glint_kernel_id {
   GLINT_K_PULL_ROWS_SPARSE = 9,
   GLINT_K_PULL_ROWS_SUM = 10, /* the grouped row-sum pull (glint_mat_pull_rows_sum*): one launch per call */
   GLINT_K_PULL_ROWS_DOT = 11, /* the row dot-product pull (glint_mat_pull_rows_dot*): one launch per call */
-  GLINT_K_COUNT = 12
+  /* the fold of a row axpy push (glint_mat_push_rows_axpy*): one launch per non-empty call */
+  GLINT_K_PUSH_ROWS_AXPY = 12,
+  GLINT_K_COUNT = 13
 };
 int glint_prof_enable(glint_shard_t shard, int on);
 int glint_prof_read(glint_shard_t shard, int kernel_id, double* total_ms, int64_t* launches);

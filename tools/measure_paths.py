@@ -3,13 +3,15 @@ device-resident rates from HIP events around each kernel (glint_prof_*), and hos
 ("end-to-end": pageable host memory -> H2D -> kernels -> D2H) rates by wall clock, which is what
 the JNI shim sees. One JSON line per measurement on stdout.
 
-    python tools/measure_paths.py [--quick] [--sparse] [--rowsum] [--dot]
+    python tools/measure_paths.py [--quick] [--sparse] [--rowsum] [--dot] [--axpy [--out FILE]]
 
 --sparse runs only the sparse-row-pull leg (dense getRows against getRowsSparse on a cfg5 shard).
 --rowsum runs only the grouped row-sum leg (getRowsSum against a dense row pull plus a reduction by the
 caller, on a cfg5 shard).
 --dot runs only the row dot-product leg (getRowsDot against a dense row pull plus a matrix product by the
 caller, on a cfg5 shard).
+--axpy runs only the row axpy push leg (updateRowsAxpy against coef @ x by the caller plus a row push, on
+cfg5 shards) and appends its lines to profiles/axpy/axpy_push.jsonl (or FILE).
 """
 import ctypes as C
 import json
@@ -302,7 +304,134 @@ def dot_leg(rng):
     msh.destroy()
 
 
+def axpy_leg(rng, out_path):
+    """cfg5 per GPU: a 2^17 x 512 Double shard, 2^14 Zipf(1.0) rows, q = 1, 8 and 64 vectors. The leg under
+    test pushes into one shard, its baseline into another, on alternating rounds of one process.
+    Host: glint_mat_push_rows_axpy against coef @ x in numpy + glint_mat_push_rows, wall time; the
+    baseline's push alone on pre-expanded values (into a third shard) for scale; the bytes staged.
+    Device: glint_mat_push_rows_axpy_dev, default and deterministic, against torch.matmul +
+    glint_mat_push_rows_dev with the same flags, a HIP event pair around each call; the fold kernel alone
+    by its prof id. The baselines never run the code under test; after each q the two shards are compared
+    within 1e-9 of each element's sum of |contributions| so far. One JSON line per q, also appended to
+    out_path."""
+    shard_rows, cols, n, rounds = 1 << 17, 512, 1 << 14, 5
+    part = glint_amd.RangePartition(0, 0, shard_rows)
+    sh_a, sh_b, sh_c = (glint_amd.PartialMatrix(part, cols, "double", 0) for _ in range(3))
+    ha, hb, hc = sh_a.handle, sh_b.handle, sh_c.handle
+    rows = zipf_keys(rng, shard_rows, n, 1.0)
+    d_rows = torch.from_numpy(rows).to(dev)
+    all_rows = torch.arange(shard_rows, dtype=torch.int64, device=dev)
+    mag = torch.zeros((shard_rows, cols), dtype=torch.float64, device=dev)
+    vals = np.empty((n, cols), np.float64)
+    d_vals = torch.empty((n, cols), dtype=torch.float64, device=dev)
+    DET = N.GLINT_PUSH_DETERMINISTIC
+
+    def ev_ms(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b)
+
+    def wall_ms(fn):
+        t0 = time.perf_counter()
+        fn()
+        return (time.perf_counter() - t0) * 1e3
+
+    def stats(ms):
+        return {"mean": float(np.mean(ms)), "min": float(np.min(ms)), "max": float(np.max(ms))}
+
+    Path(out_path).parent.mkdir(parents=True, exist_ok=True)
+    for q in (1, 8, 64):
+        coef = rng.standard_normal((n, q))
+        x = rng.standard_normal((q, cols))
+        d_coef, d_x = torch.from_numpy(coef).to(dev), torch.from_numpy(x).to(dev)
+
+        def host_axpy():
+            assert lib.glint_mat_push_rows_axpy(ha, rows.ctypes.data, n, coef.ctypes.data, x.ctypes.data, q, 0) == 0
+
+        def host_base():
+            np.matmul(coef, x, out=vals)
+            assert lib.glint_mat_push_rows(hb, rows.ctypes.data, vals.ctypes.data, n, 0) == 0
+
+        def host_push_only():
+            assert lib.glint_mat_push_rows(hc, rows.ctypes.data, vals.ctypes.data, n, 0) == 0
+
+        def dev_axpy(flags):
+            assert lib.glint_mat_push_rows_axpy_dev(ha, d_rows.data_ptr(), n, d_coef.data_ptr(), d_x.data_ptr(), q,
+                                                    flags, stream) == 0
+
+        def dev_base(flags):
+            torch.matmul(d_coef, d_x, out=d_vals)
+            assert lib.glint_mat_push_rows_dev(hb, d_rows.data_ptr(), d_vals.data_ptr(), n, flags, stream) == 0
+
+        t = {k: [] for k in ("host_axpy", "host_base", "host_push_only", "dev_axpy", "dev_base", "dev_axpy_det",
+                             "dev_base_det")}
+        pushes = 0
+        for rnd in range(rounds + 1):  # round 0 warms up; the two legs alternate inside every round
+            got = {"host_base": wall_ms(host_base), "host_axpy": wall_ms(host_axpy),
+                   "host_push_only": wall_ms(host_push_only)}
+            torch.cuda.synchronize()
+            got["dev_base"] = ev_ms(lambda: dev_base(0))
+            got["dev_axpy"] = ev_ms(lambda: dev_axpy(0))
+            got["dev_base_det"] = ev_ms(lambda: dev_base(DET))
+            got["dev_axpy_det"] = ev_ms(lambda: dev_axpy(DET))
+            pushes += 3
+            if rnd:
+                for k, v in got.items():
+                    t[k].append(v)
+        kern = {}
+        for name, flags in (("default", 0), ("det", DET)):  # the fold alone, mirrored on the baseline's shard
+            lib.glint_prof_reset(ha)
+            lib.glint_prof_enable(ha, 1)
+            for _ in range(3):
+                dev_axpy(flags)
+                dev_base(flags)
+            torch.cuda.synchronize()
+            kern[name] = kernel_ms(ha, N.GLINT_K_PUSH_ROWS_AXPY)
+            lib.glint_prof_enable(ha, 0)
+            pushes += 3
+        sh_a.sync(stream)
+        sh_b.sync(stream)
+        mag.index_add_(0, d_rows, torch.matmul(d_coef.abs(), d_x.abs()), alpha=float(pushes))
+        diff = (sh_a.getRows(all_rows) - sh_b.getRows(all_rows)).abs()
+        ok = bool((diff <= 1e-9 * mag).all().item())
+        worst = float((diff / mag.clamp_min(1e-300)).max().item())
+        del diff
+        assert ok, worst
+        m = {k: stats(v) for k, v in t.items()}
+        line = dict(
+            op="mat_push_rows_axpy", pattern="zipf1.0 rows", shape=[shard_rows, cols], rows=n, vectors=q,
+            distinct_rows=int(np.unique(rows).size), rounds=rounds,
+            host_axpy_ms=m["host_axpy"], host_baseline_ms=m["host_base"],
+            host_baseline_push_only_ms=m["host_push_only"],
+            host_speedup=m["host_base"]["mean"] / m["host_axpy"]["mean"],
+            host_speedup_over_push_only=m["host_push_only"]["mean"] / m["host_axpy"]["mean"],
+            host_axpy_bytes_staged=n * 8 + n * q * 8 + q * cols * 8, host_baseline_bytes_staged=n * 8 + n * cols * 8,
+            dev_axpy_ms=m["dev_axpy"], dev_baseline_ms=m["dev_base"],
+            dev_speedup=m["dev_base"]["mean"] / m["dev_axpy"]["mean"],
+            dev_axpy_det_ms=m["dev_axpy_det"], dev_baseline_det_ms=m["dev_base_det"],
+            dev_det_speedup=m["dev_base_det"]["mean"] / m["dev_axpy_det"]["mean"],
+            dev_axpy_kernel_ms=kern["default"], dev_axpy_det_kernel_ms=kern["det"],
+            shards_within_bound=ok, worst_fraction_of_sum_abs=worst,
+            note="host_*: C calls on pageable numpy arrays, synchronous, wall ms; baseline = np.matmul(coef, x) + "
+                 "glint_mat_push_rows, push_only = that push alone on values already built. dev_*: one HIP event "
+                 "pair per call; baseline = torch.matmul + glint_mat_push_rows_dev, same flags. Legs alternate "
+                 "inside each of `rounds` rounds after one warm-up round. *_kernel_ms: the fold alone (glint_prof)")
+        emit(**line)
+        with open(out_path, "a") as f:
+            f.write(json.dumps(line) + "\n")
+    for sh in (sh_a, sh_b, sh_c):
+        sh.destroy()
+
+
 def main():
+    if "--axpy" in sys.argv:
+        out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
+            str(Path(__file__).resolve().parent.parent / "profiles" / "axpy" / "axpy_push.jsonl")
+        axpy_leg(np.random.default_rng(42), out)
+        return
     if "--dot" in sys.argv:
         dot_leg(np.random.default_rng(42))
         return
