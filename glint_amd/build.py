@@ -160,12 +160,34 @@ def build_plan_probe(force: bool = False, verbose: bool = False) -> Path:
     return PLAN_PROBE
 
 
+SWEEP_PROBE_SRC = ROOT / "tests" / "c" / "sweep_probe.cpp"
+SWEEP_PROBE = ROOT / "tests" / "c" / "build" / "libsweep_probe.so"
+
+
+def build_sweep_probe(force: bool = False, verbose: bool = False) -> Path:
+    """The affine sweep's ticket arithmetic (glint_push_plan.h sweep_ticket_count, sweep_ticket) as a
+    host-only library: what tests/test_sweep_tickets_cpu.py loads. Compiled by g++ alone."""
+    deps = [SWEEP_PROBE_SRC, *PLAN_HEADERS, ROOT / "include" / "glint_gpu.h"]
+    if not force and not _stale(SWEEP_PROBE, deps):
+        return SWEEP_PROBE
+    SWEEP_PROBE.parent.mkdir(parents=True, exist_ok=True)
+    tmp = SWEEP_PROBE.with_suffix(".so.tmp")
+    cxx = shutil.which("g++") or "c++"
+    cmd = [cxx, "-O2", "-std=c++17", "-Wall", "-Werror", "-fPIC", "-shared", "-o", str(tmp), str(SWEEP_PROBE_SRC)]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True, cwd=str(ROOT))
+    os.replace(tmp, SWEEP_PROBE)
+    return SWEEP_PROBE
+
+
 def build_all(force: bool = False, verbose: bool = False) -> None:
     build_gpu_lib(force=force, verbose=verbose)
     build_oracle(force=force, verbose=verbose)
     build_loopback(force=force, verbose=verbose)
     build_jni_driver(force=force, verbose=verbose)
     build_plan_probe(force=force, verbose=verbose)
+    build_sweep_probe(force=force, verbose=verbose)
 
 
 if __name__ == "__main__":

@@ -507,6 +507,7 @@ __device__ __forceinline__ void part_next_header(const BinGeom& g, BinCtl* next_
     next_ctl->brk_enc = 0u;
     next_ctl->nonaffine = 0u;
     next_ctl->cancel = 0u;
+    next_ctl->ticket = 0u;
     next_ctl->bad = 0ull;
   }
 }

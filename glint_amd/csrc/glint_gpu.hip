@@ -139,6 +139,7 @@ __global__ __launch_bounds__(kTPB) void push_check_kernel(const i64* __restrict_
     next->brk_enc = 0u;
     next->nonaffine = 0u;
     next->cancel = 0u;
+    next->ticket = 0u;
     next->bad = 0ull;
   }
   if (ctl->cancel) return;  // a cancelled gated push: brk_enc stays 0, so no tail either
@@ -250,63 +251,89 @@ __device__ __forceinline__ void apply_general(const PushArgs<V>& a, i64 pbase, i
   }
 }
 
-// The whole push is one affine run (element = record + delta): a grid-stride sweep over record
-// pairs, so the grid reads one compact window of the value and shard streams at a time and no
-// load depends on another (the keys were read once, by push_check). Only the first
+// The whole push is one affine run (element = record + delta): the value and shard streams are swept
+// with no load that depends on another (the keys were read once, by push_check). Only the first
 // a.sweep_blocks blocks take part (about one per CU): this 2-read + 1-write stream runs fastest
 // with ~16 KiB of loads in flight per CU and every access non-temporal (tools/microbench_stream.hip:
 // 6.2 TB/s, against 5.7 TB/s at twice the waves with cached shard accesses).
-constexpr int kSweepU = 2;  // record pairs per lane per iteration
+// The sweep is one launch whatever the push's size. Its blocks take tickets (sweep_ticket,
+// glint_push_plan.h): block b starts on ticket b, and every further ticket comes from the push's
+// counter (LaunchCtl.ticket, zeroed with the other control words), fetched before the block works on
+// the current ticket so that the atomic's latency hides behind that ticket's loads. The S tickets of a
+// super-window read it as a grid-stride loop would, and a block that runs ahead takes the next free
+// slot instead of drifting gigabytes away from the others, which is what a whole grid-stride launch
+// lost 6-11 % to and what a launch per 2^26-record window used to repair (mode 7 of the
+// microbenchmark, profiles/tickets/). No block ever waits on another: a block's progress needs only
+// its own atomicAdd to return. A push of no more tickets than blocks issues no atomic at all.
+constexpr int kSweepU = 2;  // record pairs per lane in flight
+static_assert(kSweepRowPairs == kTPB && kSweepTicketRows % kSweepU == 0, "a ticket row is one pair per thread");
 template <typename V, bool EVEN>
-__device__ __forceinline__ void apply_sweep(const PushArgs<V>& a, i64 delta, i64 p_begin, i64 p_end, bool last) {
+__device__ __forceinline__ void apply_sweep(const PushArgs<V>& a, i64 delta, u32* next_ticket) {
   typedef typename Vec2<V>::T V2;
   if (blockIdx.x >= a.sweep_blocks) return;
-  const i64 npairs = p_end;
-  const i64 stride = (i64)a.sweep_blocks * kTPB;
+  const u32 S = a.sweep_blocks;
+  const i64 npairs = a.n >> 1;
+  const u32 ntickets = (u32)sweep_ticket_count(a.n, S);
+  const bool counted = ntickets > S;  // block-uniform; else every ticket is some block's first
   const V2* vp = reinterpret_cast<const V2*>(a.vals);
-  i64 p = p_begin + (i64)blockIdx.x * kTPB + threadIdx.x;
-  if (EVEN) {
-    V2* dp = reinterpret_cast<V2*>(a.data + delta);  // pair p -> element pair delta + 2p
-    for (; p + (kSweepU - 1) * stride < npairs; p += kSweepU * stride) {
-      V2 v[kSweepU], d[kSweepU];
+  V2* dp = reinterpret_cast<V2*>(a.data + (EVEN ? delta : 0));  // EVEN: pair p -> element pair delta + 2p
+  u32 t = blockIdx.x;
+  for (int it = 0; t < ntickets; ++it) {
+    u32 nx = ntickets;
+    if (counted && threadIdx.x == 0) nx = S + atomicAdd(&a.ctl->ticket, 1u);
+    const SweepTicket k = sweep_ticket(t, S);
+    i64 p = k.first + threadIdx.x;
+    int r = 0;
+    if (EVEN && k.first + (kSweepTicketRows - 1) * k.stride + kSweepRowPairs <= npairs) {  // every row whole
+      for (; r < kSweepTicketRows; r += kSweepU, p += kSweepU * k.stride) {
+        V2 v[kSweepU], d[kSweepU];
 #pragma unroll
-      for (int j = 0; j < kSweepU; ++j) {
-        v[j] = __builtin_nontemporal_load(vp + p + j * stride);
-        d[j] = __builtin_nontemporal_load(dp + p + j * stride);
+        for (int j = 0; j < kSweepU; ++j) {
+          v[j] = __builtin_nontemporal_load(vp + p + j * k.stride);
+          d[j] = __builtin_nontemporal_load(dp + p + j * k.stride);
+        }
+#pragma unroll
+        for (int j = 0; j < kSweepU; ++j)
+          __builtin_nontemporal_store(as2<V>(vadd((V)d[j].x, (V)v[j].x), vadd((V)d[j].y, (V)v[j].y)), dp + p + j * k.stride);
       }
-#pragma unroll
-      for (int j = 0; j < kSweepU; ++j)
-        __builtin_nontemporal_store(as2<V>(vadd((V)d[j].x, (V)v[j].x), vadd((V)d[j].y, (V)v[j].y)), dp + p + j * stride);
     }
-    for (; p < npairs; p += stride) {
+    for (; r < kSweepTicketRows; ++r, p += k.stride) {
+      if (p >= npairs) break;
       const V2 v = __builtin_nontemporal_load(vp + p);
-      const V2 d = __builtin_nontemporal_load(dp + p);
-      __builtin_nontemporal_store(as2<V>(vadd((V)d.x, (V)v.x), vadd((V)d.y, (V)v.y)), dp + p);
+      if (EVEN) {
+        const V2 d = __builtin_nontemporal_load(dp + p);
+        __builtin_nontemporal_store(as2<V>(vadd((V)d.x, (V)v.x), vadd((V)d.y, (V)v.y)), dp + p);
+      } else {
+        const i64 e = 2 * p + delta;
+        const V d0 = a.data[e], d1 = a.data[e + 1];
+        a.data[e] = vadd(d0, (V)v.x);
+        a.data[e + 1] = vadd(d1, (V)v.y);
+      }
     }
-  } else {
-    for (; p < npairs; p += stride) {
-      const V2 v = __builtin_nontemporal_load(vp + p);
-      const i64 e = 2 * p + delta;
-      const V d0 = a.data[e], d1 = a.data[e + 1];
-      a.data[e] = vadd(d0, (V)v.x);
-      a.data[e + 1] = vadd(d1, (V)v.y);
-    }
+    if (!counted) break;
+    // the block's next ticket, from thread 0 to all (two slots: a wave still reading this one is not
+    // overtaken by the next write, which comes a barrier later)
+    if (threadIdx.x == 0) next_ticket[it & 1] = nx;
+    __syncthreads();
+    t = next_ticket[it & 1];
   }
-  // the odd record belongs to the last window only: with n = k * 2^26 + 1 an earlier window also
-  // ends at pair n >> 1 (its tiles cover every pair), so p_end alone cannot tell them apart
-  if ((a.n & 1) && last && blockIdx.x == 0 && threadIdx.x == 0) {
+  if ((a.n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {  // the odd last record, once per push
     const i64 e = a.n - 1 + delta;
     a.data[e] = vadd(a.data[e], a.vals[a.n - 1]);
   }
 }
 
-// One launch covers the wave tiles [t_begin, t_end) of the push (a window, see sweep_window_tiles).
+// One launch per push: the affine sweep, or -- for a push that is not one affine run -- the wave tiles
+// before the break, both by tickets from the push's counter. On the tile path a ticket is
+// kTileTicketRows rows of one wave tile per wave of the block (tile_ticket, glint_push_plan.h): the G
+// tickets of a super-window read it as the static wave stride did, and blocks stay within a
+// super-window of each other as they did when the apply was relaunched per window.
 template <typename V, bool MAT>
-__global__ __launch_bounds__(kTPB) void push_apply_kernel(PushArgs<V> a, const i64* __restrict__ desc, u32 t_begin,
-                                                          u32 t_end) {
+__global__ __launch_bounds__(kTPB) void push_apply_kernel(PushArgs<V> a, const i64* __restrict__ desc) {
+  __shared__ u32 next_ticket[2];  // the block's next ticket, from thread 0 to all
   if (a.ctl->cancel) return;  // a gated push whose gate was set applies nothing (and leaves the hint)
   const u32 brk = a.ctl->brk_enc;  // written by push_check; ordered by the kernel boundary
-  if (t_begin == 0 && blockIdx.x == 0 && threadIdx.x == 0 && a.hint) {  // for the host's next push: how unordered was this one?
+  if (blockIdx.x == 0 && threadIdx.x == 0 && a.hint) {  // for the host's next push: how unordered was this one?
     __hip_atomic_store(a.hint, brk == 0u ? 0ull : (u64)(a.n - (i64)(a.ntiles - brk) * kTile), __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_SYSTEM);
     __hip_atomic_store(a.hint + 3, brk == 0u ? (u64)a.n : (u64)(a.ntiles - brk) * kTile, __ATOMIC_RELAXED,
@@ -314,32 +341,44 @@ __global__ __launch_bounds__(kTPB) void push_apply_kernel(PushArgs<V> a, const i
   }
   if (brk == 0u && a.ctl->nonaffine == 0u) {
     const i64 delta = desc[0];  // tile 0 starts the run at record 0
-    const i64 p0 = (i64)t_begin * (kTile / 2), p1 = min((i64)t_end * (kTile / 2), a.n >> 1);
-    const bool last = t_end >= a.ntiles;
-    if ((delta & 1) == 0) apply_sweep<V, true>(a, delta, p0, p1, last);
-    else apply_sweep<V, false>(a, delta, p0, p1, last);
+    if ((delta & 1) == 0) apply_sweep<V, true>(a, delta, next_ticket);
+    else apply_sweep<V, false>(a, delta, next_ticket);
     return;
   }
-  const u32 tiles = min(t_end, brk == 0u ? a.ntiles : a.ntiles - brk);
+  static_assert(kTileRowTiles == kTPB / 64 && kTileTicketRows <= 64, "a ticket row is one tile per wave");
+  const i64 tiles = brk == 0u ? a.ntiles : a.ntiles - brk;
   const int lane = threadIdx.x & 63;
-  const u32 w0 = blockIdx.x * (kTPB / 64) + (threadIdx.x >> 6);
-  const u32 nw = gridDim.x * (kTPB / 64);
-  i64 dbatch = kNotAffine;  // descriptors of this wave's next 64 tiles, one per lane
-  for (u32 t = t_begin + w0, it = 0; t < tiles; t += nw, ++it) {
-    if ((it & 63) == 0) {  // one load per 64 tiles instead of a dependent load per tile
-      const i64 tt = (i64)t + (i64)lane * nw;
-      dbatch = tt < (i64)tiles ? desc[tt] : kNotAffine;
+  const u32 G = gridDim.x;
+  const u32 ntickets = (u32)tile_ticket_count(tiles, G);
+  const bool counted = ntickets > G;  // block-uniform; else every ticket is some block's first
+  u32 tk = blockIdx.x;
+  for (int it = 0; tk < ntickets; ++it) {
+    u32 nx = ntickets;
+    if (counted && threadIdx.x == 0) nx = G + atomicAdd(&a.ctl->ticket, 1u);
+    const SweepTicket k = tile_ticket(tk, G);
+    const i64 t0 = k.first + (threadIdx.x >> 6);  // this wave's tile of row 0
+    // the descriptors of this wave's tiles of the ticket, one per lane: one load per ticket instead of a
+    // dependent load per tile
+    const i64 tt = t0 + (i64)lane * k.stride;
+    const i64 dbatch = lane < kTileTicketRows && tt < tiles ? desc[tt] : kNotAffine;
+    for (int r = 0; r < kTileTicketRows; ++r) {
+      const i64 t = t0 + (i64)r * k.stride;
+      if (t >= tiles) break;  // wave-uniform
+      const i64 pbase = t * (kTile / 2);
+      const i64 base = __shfl(dbatch, r);  // wave-uniform
+      const bool full = 2 * pbase + kTile <= a.n;
+      if (base != kNotAffine) {
+        if (full) apply_affine<V, MAT, true>(a, pbase, base, lane);
+        else apply_affine<V, MAT, false>(a, pbase, base, lane);
+      } else {
+        if (full) apply_general<V, MAT, true>(a, pbase, lane);
+        else apply_general<V, MAT, false>(a, pbase, lane);
+      }
     }
-    const i64 pbase = (i64)t * (kTile / 2);
-    const i64 base = __shfl(dbatch, (int)(it & 63));  // wave-uniform
-    const bool full = 2 * pbase + kTile <= a.n;
-    if (base != kNotAffine) {
-      if (full) apply_affine<V, MAT, true>(a, pbase, base, lane);
-      else apply_affine<V, MAT, false>(a, pbase, base, lane);
-    } else {
-      if (full) apply_general<V, MAT, true>(a, pbase, lane);
-      else apply_general<V, MAT, false>(a, pbase, lane);
-    }
+    if (!counted) break;
+    if (threadIdx.x == 0) next_ticket[it & 1] = nx;  // (two slots, as in apply_sweep)
+    __syncthreads();
+    tk = next_ticket[it & 1];
   }
 }
 
@@ -756,11 +795,11 @@ namespace {
 // blocks per CU in the affine sweep (1 measured best on MI355X)
 constexpr int kSweepBlocksPerCu = 1;
 
-// The apply of a large push runs as one launch per window of 2^26 records. A grid-stride sweep over a
-// whole 2^30-record push lets its blocks drift apart across gigabytes, and the 2-read + 1-write stream
-// then runs 6-11 % slower than the same bytes swept window by window (tools/microbench_stream.hip mode
-// 6: 2^30 records whole 5.90 TB/s, in 2^26-record launches 6.56 TB/s; 2^28 whole 6.21 TB/s;
-// profiles/r03/micro_stream_2p30.txt).
+// Records per launch of a dense pull (launch_vec_pull): a grid-stride sweep over a whole 2^30-record
+// call lets its blocks drift apart across gigabytes, and relaunching per window re-aligns them
+// (tools/microbench_stream.hip mode 6: the push's 2-read + 1-write stream at 2^30 records whole
+// 5.90 TB/s, in 2^26-record launches 6.56 TB/s; profiles/r03/micro_stream_2p30.txt). The push's apply
+// swept in these windows too until its blocks took tickets in one launch (apply_sweep).
 constexpr u32 kSweepWindowTiles = ((u32)1 << 26) / kTile;
 
 // GLINT_BINNED: 0 = never bin, 1 = bin every large push, unset = bin when the previous push on the
@@ -893,15 +932,10 @@ int launch_push(glint_shard* s, const i64* keys, const int32_t* cols, const void
     HIPCHK(hipGetLastError());
   }
   s->ctl_par ^= 1;  // only once the check that zeroes the other slot is on the stream
-  const u64 win = std::min<u64>(kSweepWindowTiles, a.ntiles);
-  auto apply_head = [&]() -> int {  // the records before the break (every record of an ordered push)
-    const i64 bpc = blocks_per_cu<push_apply_kernel<V, MAT>>(2);
-    for (u64 t0 = 0; t0 < a.ntiles; t0 += win) {
-      const u32 t1 = (u32)std::min<u64>(a.ntiles, t0 + win);
-      const unsigned ga = grid_for(t1 - t0, kTPB / 64, (i64)s->cus * bpc);
-      a.sweep_blocks = std::min<u32>(ga, (u32)((i64)s->cus * kSweepBlocksPerCu));
-      HIPCHK(launch_k(s, GLINT_K_PUSH_APPLY, push_apply_kernel<V, MAT>, ga, kTPB, st, a, (const i64*)desc, (u32)t0, t1));
-    }
+  auto apply_head = [&]() -> int {  // the records before the break (every record of an ordered push), one launch
+    const unsigned ga = grid_for(a.ntiles, kTPB / 64, (i64)s->cus * blocks_per_cu<push_apply_kernel<V, MAT>>(2));
+    a.sweep_blocks = std::min<u32>(ga, (u32)((i64)s->cus * kSweepBlocksPerCu));
+    HIPCHK(launch_k(s, GLINT_K_PUSH_APPLY, push_apply_kernel<V, MAT>, ga, kTPB, st, a, (const i64*)desc));
     return GLINT_OK;
   };
   if (r.fuse) {  // verdict, cancel and the head, behind the tail's validating count
@@ -938,7 +972,7 @@ int launch_vec_pull(glint_shard* s, const i64* keys, void* out, i64 n, hipStream
   const bool pairs = aligned(keys, 16) && aligned(out, 2 * sizeof(V));
   if (pairs) {
     // 4 blocks per CU: the dense gather's best (tools/microbench_stream.hip mode 5); one launch per
-    // window of records, as the push's apply sweep (kSweepWindowTiles)
+    // window of records (kSweepWindowTiles)
     const i64 npairs = (n + 1) / 2;
     const i64 win = sig.done ? npairs : std::min<i64>(npairs, (i64)kSweepWindowTiles * (kTile / 2));
     for (i64 p0 = 0; p0 < npairs; p0 += win) {

@@ -44,7 +44,7 @@ struct LaunchCtl {
   u32 brk_enc;    // max over tiles that break the increasing order of (ntiles - t); 0 = none
   u32 nonaffine;  // some tile is not affine or does not continue its predecessor's affine run
   u32 cancel;     // a gated push whose gate word was set: it applies nothing (push_gate_kernel)
-  u32 pad_;
+  u32 ticket;     // push_apply's ticket counter (sweep_ticket / tile_ticket in glint_push_plan.h)
   u64 bad;        // a validating gated push: max of ~index over its out-of-range records (push_check)
 };
 

@@ -134,6 +134,54 @@ inline PushRoute push_route(const PushQuery& q) {
   return r;
 }
 
+// ---- the affine sweep's tickets (push_apply's apply_sweep, glint_gpu.hip) ----
+// A dense push is swept in one launch by S blocks that take tickets from a device counter. The record
+// pairs [0, n >> 1) are cut into rows of kSweepRowPairs pairs (one pair per thread of a block) and into
+// super-windows of kSweepTicketRows * S rows. Ticket t is slot t % S of super-window t / S: the rows
+// r * S + slot, r < kSweepTicketRows, of that super-window, so the S tickets of a super-window read it
+// exactly as a grid-stride loop of S blocks would. A ticket whose first row starts at or past the last
+// pair does not exist; a row may reach past the last pair and is cut there by the caller. Usable from
+// host and device code (tests/c/sweep_probe.cpp checks the cover on a CPU).
+#if defined(__HIPCC__)
+#define GLINT_HD __host__ __device__
+#else
+#define GLINT_HD
+#endif
+constexpr int kSweepRowPairs = 256;    // pairs per row: the block size of push_apply (kTPB)
+constexpr int kSweepTicketRows = 16;   // rows per ticket
+constexpr i64 kSweepTicketRecords = 2ll * kSweepTicketRows * kSweepRowPairs;  // 8192 records per full ticket
+
+struct SweepTicket {
+  i64 first;   // the first unit of row 0
+  i64 stride;  // units from one row's start to the next row's
+};
+
+// The arithmetic in units (record pairs for the sweep, wave tiles for the tile path below): rows of
+// `row` units, `rows` rows per ticket, S blocks.
+GLINT_HD inline u64 ticket_count(i64 units, i64 row, int rows, u32 S) {
+  const i64 sw = row * rows * (i64)S;                   // units per super-window
+  const i64 rem_rows = (units % sw + row - 1) / row;    // rows of the last, partial one
+  return (u64)(units / sw) * S + (u64)(rem_rows < (i64)S ? rem_rows : (i64)S);
+}
+GLINT_HD inline SweepTicket ticket_at(u64 t, i64 row, int rows, u32 S) {
+  SweepTicket k;
+  k.stride = (i64)S * row;
+  k.first = (i64)(t / S) * rows * k.stride + (i64)(t % S) * row;
+  return k;
+}
+
+// tickets of a push of n records swept by S blocks (S >= 1), and ticket t's rows of record pairs
+GLINT_HD inline u64 sweep_ticket_count(i64 n, u32 S) { return ticket_count(n >> 1, kSweepRowPairs, kSweepTicketRows, S); }
+GLINT_HD inline SweepTicket sweep_ticket(u64 t, u32 S) { return ticket_at(t, kSweepRowPairs, kSweepTicketRows, S); }
+
+// The tile path of push_apply (a push that is not one affine run) takes tickets the same way: a row is
+// the kTileRowTiles wave tiles of a block's waves, a ticket kTileTicketRows rows of a super-window of
+// G blocks' rows, so a super-window is read as the static wave stride reads it.
+constexpr int kTileRowTiles = 4;     // waves per block of push_apply (kTPB / 64)
+constexpr int kTileTicketRows = 8;   // rows per ticket
+GLINT_HD inline u64 tile_ticket_count(i64 tiles, u32 G) { return ticket_count(tiles, kTileRowTiles, kTileTicketRows, G); }
+GLINT_HD inline SweepTicket tile_ticket(u64 t, u32 G) { return ticket_at(t, kTileRowTiles, kTileTicketRows, G); }
+
 // ---- the binned front end's history (a member of glint_shard; bin_front_next in glint_bin_plan.h) ----
 // Front ends: 0 plain, 1 plain + hot-element split, 2 chunk dedup (+ hot split). What the last dedup
 // push measured decides: chunk_ratio = records it kept of the cold records that entered its hash table

@@ -1,6 +1,7 @@
 // Streaming-shape sweep for the dense push (push_check = 1 read stream, push_apply sweep = 2 reads +
 // 1 write stream): pairs per lane in flight, blocks per CU, grid-stride vs per-block chunking, and
-// the cache policy of each access. Not part of the product. Build:
+// the cache policy of each access; mode 7: the apply sweep in one launch with ticketed chunks against
+// its 2^26-record launches (argv: log2 records, timed launches, mode, repeats). Not part of the product. Build:
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -o tools/microbench_stream tools/microbench_stream.hip
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -165,8 +166,80 @@ __global__ __launch_bounds__(256) void k_copy(const D2* __restrict__ src, D2* __
   }
 }
 
+// mode 7: the sweep in ONE launch, blocks taking tickets from a device counter. A ticket is `rows` rows
+// of 256 pairs, `stride` pairs apart, from pair `first`:
+//   MAP 0 contiguous:  ticket t = pairs [t * rows * 256, (t + 1) * rows * 256)
+//   MAP 1 interleaved: ticket t = slot t % S of super-window t / S (S blocks): rows r * S + slot of the
+//                      super-window's rows * S rows -- a super-window is read as the grid-stride reads it
+// Block b starts on ticket b; each block fetches its next ticket before it works on the current one.
+// No block waits on another: the only shared word is the counter, and this launch zeroes the other
+// counter for the next one (as push_check zeroes the next push's control words).
+template <int MAP>
+__global__ __launch_bounds__(256) void k_ticket(const D2* __restrict__ vals, D2* __restrict__ data, i64 n2, int rows,
+                                                unsigned ntickets, unsigned* ctr, unsigned* next_ctr) {
+  __shared__ unsigned slot[2];
+  const unsigned S = gridDim.x;
+  if (blockIdx.x == 0 && threadIdx.x == 0) *next_ctr = 0u;
+  const bool counted = ntickets > S;  // else every ticket is some block's first: no atomic at all
+  unsigned t = blockIdx.x;
+  for (int it = 0; t < ntickets; ++it) {
+    unsigned nx = ntickets;
+    if (counted && threadIdx.x == 0) nx = S + __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    i64 first, stride;
+    if (MAP == 0) {
+      first = (i64)t * rows * 256;
+      stride = 256;
+    } else {
+      first = (i64)(t / S) * rows * S * 256 + (i64)(t % S) * 256;
+      stride = (i64)S * 256;
+    }
+    i64 p = first + threadIdx.x;
+    int r = 0;
+    if (first + (rows - 1) * stride + 256 <= n2) {
+      for (; r + 1 < rows; r += 2, p += 2 * stride) {
+        D2 v[2], d[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          v[j] = __builtin_nontemporal_load(vals + p + j * stride);
+          d[j] = __builtin_nontemporal_load(data + p + j * stride);
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) __builtin_nontemporal_store(d[j] + v[j], data + p + j * stride);
+      }
+    }
+    for (; r < rows; ++r, p += stride) {
+      if (p < n2) {
+        const D2 v = __builtin_nontemporal_load(vals + p);
+        const D2 d = __builtin_nontemporal_load(data + p);
+        __builtin_nontemporal_store(d + v, data + p);
+      }
+    }
+    if (!counted) break;
+    if (threadIdx.x == 0) slot[it & 1] = nx;
+    __syncthreads();
+    t = slot[it & 1];
+  }
+}
+
+// tickets of `rows` rows for n2 pairs and S blocks
+static unsigned ticket_count(int map, i64 n2, int rows, unsigned S) {
+  if (map == 0) return (unsigned)((n2 + (i64)rows * 256 - 1) / ((i64)rows * 256));
+  const i64 sw = (i64)rows * S * 256;
+  const i64 rem_rows = (n2 % sw + 255) / 256;
+  return (unsigned)(n2 / sw * S + std::min<i64>(S, rem_rows));
+}
+
 __global__ void k_iota(i64* keys, i64 n) {
   for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x) keys[i] = i + 5;
+}
+
+__global__ void k_fill(double* x, i64 n, double v) {
+  for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x) x[i] = v;
+}
+__global__ void k_count_ne(const double* x, i64 n, double v, unsigned long long* bad) {
+  unsigned long long c = 0;
+  for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x) c += x[i] != v;
+  if (c) atomicAdd(bad, c);
 }
 
 template <class F>
@@ -300,6 +373,60 @@ int main(int argc, char** argv) {
     for (int g : {cus / 2, cus, cus * 2}) {
       const float ms = timeit([&] { k_apply<4, 0, 1, 1, 1, 256><<<g, 256>>>((const D2*)v2, (D2*)d2, n2); }, reps);
       printf("sweep 2^%d U4 grid %d: %7.3f ms %6.0f GB/s\n", lg, g, ms, 24.0 * n / ms / 1e6);
+    }
+    printf("done\n");
+    return 0;
+  }
+  if (mode == 7) {
+    // One launch with ticketed chunks against today's 2^26-record launches and the whole grid-stride
+    // launch, on the same buffers, the whole comparison `outer` times (argv[4], default 3).
+    const int outer = argc > 4 ? atoi(argv[4]) : 3;
+    unsigned* ctr;  // two counters: each launch counts on one and zeroes the other
+    unsigned long long* bad;
+    CK(hipMalloc(&ctr, 8));
+    CK(hipMalloc(&bad, 8));
+    CK(hipMemset(ctr, 0, 8));
+    int par = 0;
+    auto ticketed = [&](int map, int rows) {
+      const unsigned nt = ticket_count(map, n2, rows, (unsigned)cus);
+      if (map == 0) k_ticket<0><<<cus, 256>>>(V, Dd, n2, rows, nt, ctr + par, ctr + (par ^ 1));
+      else k_ticket<1><<<cus, 256>>>(V, Dd, n2, rows, nt, ctr + par, ctr + (par ^ 1));
+      par ^= 1;
+    };
+    const i64 w2 = (1ll << 26) / 2;
+    auto windowed = [&] {
+      for (i64 o = 0; o < n2; o += w2) k_apply<2, 0, 1, 1, 1, 256><<<cus, 256>>>(V + o, Dd + o, std::min(w2, n2 - o));
+    };
+    auto whole = [&] { k_apply<2, 0, 1, 1, 1, 256><<<cus, 256>>>(V, Dd, n2); };
+    // every pair exactly once: vals = 1, data = 0, one launch, every element must read 1
+    k_fill<<<4096, 256>>>(vals, n, 1.0);
+    for (int map : {0, 1})
+      for (int rows : {8, 256}) {
+        CK(hipMemset(data, 0, n * 8));
+        CK(hipMemset(bad, 0, 8));
+        ticketed(map, rows);
+        k_count_ne<<<4096, 256>>>(data, n, 1.0, bad);
+        unsigned long long h = 0;
+        CK(hipMemcpy(&h, bad, 8, hipMemcpyDeviceToHost));
+        printf("verify map %d rows %d: %llu wrong elements\n", map, rows, h);
+        if (h) return 1;
+      }
+    CK(hipMemset(vals, 0, n * 8));
+    CK(hipMemset(data, 0, n * 8));
+    CK(hipDeviceSynchronize());
+    for (int rep = 0; rep < outer; ++rep) {
+      float ms = timeit(windowed, reps);
+      printf("rep %d 2^%d in 2^26 launches (%lld): %7.3f ms %6.0f GB/s\n", rep, lg, (long long)((n2 + w2 - 1) / w2), ms,
+             24.0 * n / ms / 1e6);
+      ms = timeit(whole, reps);
+      printf("rep %d 2^%d whole grid-stride: %7.3f ms %6.0f GB/s\n", rep, lg, ms, 24.0 * n / ms / 1e6);
+      for (int map : {0, 1})
+        for (int rows : {8, 16, 32, 64, 128, 256}) {
+          ms = timeit([&] { ticketed(map, rows); }, reps);
+          printf("rep %d 2^%d one launch %s rows %3d (%6u tickets of %5d pairs): %7.3f ms %6.0f GB/s\n", rep, lg,
+                 map ? "interleaved" : "contiguous ", rows, ticket_count(map, n2, rows, (unsigned)cus), rows * 256, ms,
+                 24.0 * n / ms / 1e6);
+        }
     }
     printf("done\n");
     return 0;
