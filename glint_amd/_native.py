@@ -27,6 +27,7 @@ GLINT_K_PUSH_ROWS_AXPY = 12
 GLINT_K_COUNT = 13
 GLINT_DOT_MAX_QUERIES, GLINT_DOT_QUERY_TILE = 1024, 4
 GLINT_AXPY_MAX_VECTORS = 64
+GLINT_TOPK_MAX_K, GLINT_TOPK_MAX_QUERIES, GLINT_TOPK_TILE = 1024, 64, 4096
 GLINT_ROUTE_RANGE, GLINT_ROUTE_CYCLIC = 0, 1
 GLINT_RING_SLOTS, GLINT_ZERO_COPY_MAX = 16, 4096
 GLINT_SPARSE_SCAN_TILE = 1024
@@ -60,6 +61,8 @@ SIGNATURES = {
     "glint_mat_pull_rows_dot_dev": (_I, [_P, _P, _I64, _P, _I64, _P, _P]),
     "glint_mat_push_rows_axpy": (_I, [_P, _P, _I64, _P, _P, _I64, _I]),
     "glint_mat_push_rows_axpy_dev": (_I, [_P, _P, _I64, _P, _P, _I64, _I, _P]),
+    "glint_mat_pull_topk": (_I, [_P, _P, _I64, _I64, _P, _P]),
+    "glint_mat_pull_topk_dev": (_I, [_P, _P, _I64, _I64, _P, _P, _P]),
     "glint_shard_last_error": (_I, [_P, C.POINTER(_I64)]),
     "glint_vec_push_dev": (_I, [_P, _P, _P, _I64, _I, _P]),
     "glint_vec_push_dev_gated": (_I, [_P, _P, _P, _I64, _I, _P, _P]),
@@ -88,6 +91,7 @@ SIGNATURES = {
     "glint_send_matrix_dev": (_I, [_P, _P, _I32, _I32, _P, _P, _P]),
     "glint_prof_enable": (_I, [_P, _I]),
     "glint_prof_read": (_I, [_P, _I, C.POINTER(C.c_double), C.POINTER(_I64)]),
+    "glint_prof_read_launches": (_I, [_P, _I, C.POINTER(C.c_double), _I64, C.POINTER(_I64)]),
     "glint_prof_reset": (_I, [_P]),
     "glint_strerror": (C.c_char_p, [_I]),
     "glint_device_count": (_I, []),

@@ -25,10 +25,12 @@ ORACLE_LIB = ORACLE_DIR / "build" / "libglint_oracle.so"
 CSRC = PKG / "csrc"
 HIP_SOURCES = [CSRC / "glint_gpu.hip", CSRC / "glint_sort.hip", CSRC / "glint_route.hip", CSRC / "glint_ordered.hip", CSRC / "glint_bin.hip",
                CSRC / "glint_exchange.hip", CSRC / "glint_rows.hip", CSRC / "glint_sparse.hip",
-               CSRC / "glint_rowsum.hip", CSRC / "glint_rowdot.hip", CSRC / "glint_rowaxpy.hip"]
-PLAN_HEADERS = [CSRC / "glint_push_plan.h", CSRC / "glint_bin_plan.h"]  # plain C++: the push planners
-HIP_HEADERS = [CSRC / "glint_kernels.h", CSRC / "glint_device.h", CSRC / "glint_host.h", ROOT / "include" / "glint_gpu.h",
-               *PLAN_HEADERS]
+               CSRC / "glint_rowsum.hip", CSRC / "glint_rowdot.hip", CSRC / "glint_rowaxpy.hip",
+               CSRC / "glint_topk.hip"]
+# plain C++: the push planners and the top-k pull's level plan
+PLAN_HEADERS = [CSRC / "glint_push_plan.h", CSRC / "glint_bin_plan.h", CSRC / "glint_topk_plan.h"]
+HIP_HEADERS = [CSRC / "glint_kernels.h", CSRC / "glint_device.h", CSRC / "glint_host.h", CSRC / "glint_dot.h",
+               ROOT / "include" / "glint_gpu.h", *PLAN_HEADERS]
 HIP_DEPS = HIP_SOURCES + HIP_HEADERS
 OBJ_DIR = ROOT / "build" / "obj"
 ORACLE_SOURCES = [ORACLE_DIR / "glint_oracle.c"]
@@ -181,6 +183,27 @@ def build_sweep_probe(force: bool = False, verbose: bool = False) -> Path:
     return SWEEP_PROBE
 
 
+TOPK_PROBE_SRC = ROOT / "tests" / "c" / "topk_probe.cpp"
+TOPK_PROBE = ROOT / "tests" / "c" / "build" / "libtopk_probe.so"
+
+
+def build_topk_probe(force: bool = False, verbose: bool = False) -> Path:
+    """The top-k pull's level plan (glint_topk_plan.h) as a host-only library: what
+    tests/test_topk_cpu.py loads. Compiled by g++ alone."""
+    deps = [TOPK_PROBE_SRC, *PLAN_HEADERS, ROOT / "include" / "glint_gpu.h"]
+    if not force and not _stale(TOPK_PROBE, deps):
+        return TOPK_PROBE
+    TOPK_PROBE.parent.mkdir(parents=True, exist_ok=True)
+    tmp = TOPK_PROBE.with_suffix(".so.tmp")
+    cxx = shutil.which("g++") or "c++"
+    cmd = [cxx, "-O2", "-std=c++17", "-Wall", "-Werror", "-fPIC", "-shared", "-o", str(tmp), str(TOPK_PROBE_SRC)]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True, cwd=str(ROOT))
+    os.replace(tmp, TOPK_PROBE)
+    return TOPK_PROBE
+
+
 def build_all(force: bool = False, verbose: bool = False) -> None:
     build_gpu_lib(force=force, verbose=verbose)
     build_oracle(force=force, verbose=verbose)
@@ -188,6 +211,7 @@ def build_all(force: bool = False, verbose: bool = False) -> None:
     build_jni_driver(force=force, verbose=verbose)
     build_plan_probe(force=force, verbose=verbose)
     build_sweep_probe(force=force, verbose=verbose)
+    build_topk_probe(force=force, verbose=verbose)
 
 
 if __name__ == "__main__":

@@ -18,6 +18,8 @@ Mirrors the reference's client factory and asynchronous models, minus the Akka t
 * ``BigMatrix.pullDot`` -- an extension: the dot products of rows with caller vectors (or with
   themselves), reduced over the columns on the shards (PartialMatrix.getRowsDot); a row lives in one
   partition, so the answers are only scattered back.
+* ``BigMatrix.pullTopK`` -- an extension: the rows that score highest against caller vectors, selected on
+  the shards (PartialMatrix.getTopK) and merged here, at most ``parts * k`` pairs per query.
 
 Out-of-range keys raise ``IndexOutOfBoundsException`` before any shard is touched, as the
 reference's ``partitioner.partition`` does synchronously inside ``mapPartitions``.
@@ -264,10 +266,56 @@ class BigMatrix:
                 out[idx] = sh.getRowsDot(rows[idx], x)
         return out
 
+    def pullTopK(self, x, k: int):
+        """The ``k`` rows of the matrix that score highest against caller vectors (an extension): ``x``
+        of shape (cols,) gives ``(rows[k], vals[k])``, ``x`` of shape (q, cols) two (q, k) arrays. Every
+        partition answers one PartialMatrix.getTopK with its own best ``k``; the -1 fill of partitions
+        with fewer rows is dropped, and the at most ``parts * k`` pairs per query are merged here by the
+        shards' order -- rank descending (every NaN below every number, -0 equal to +0), then global
+        row ascending -- and the first ``k`` kept. A matrix of fewer than ``k`` rows fills the rest with
+        row -1 and value 0. A score's bits depend on (type, cols) only and the order is total over
+        (rank, row), so the answer does not depend on how the matrix is partitioned."""
+        dtype = self.shards[0].np_dtype
+        x = np.ascontiguousarray(x, dtype=dtype)
+        if x.shape != (self.cols,) and not (x.ndim == 2 and x.shape[1] == self.cols and x.shape[0] >= 1):
+            raise ValueError(f"x: shape {x.shape}, expected ({self.cols},) or (q, {self.cols})")
+        k = int(k)
+        if k < 1:
+            raise ValueError(f"k: {k}, expected k >= 1")
+        x2 = x.reshape(-1, self.cols)
+        parts = [sh.getTopK(x2, k) for sh in self.shards]
+        rows = np.concatenate([np.asarray(r).reshape(x2.shape[0], k) for r, _ in parts], axis=1)
+        vals = np.concatenate([np.asarray(v).reshape(x2.shape[0], k) for _, v in parts], axis=1)
+        out_rows = np.full((x2.shape[0], k), -1, np.int64)
+        out_vals = np.zeros((x2.shape[0], k), dtype)
+        for j in range(x2.shape[0]):
+            real = rows[j] >= 0
+            r, v = rows[j][real], vals[j][real]
+            best = np.lexsort((r, ~topk_rank_key(v)))[:k]  # the last key is the primary one
+            out_rows[j, :best.size], out_vals[j, :best.size] = r[best], v[best]
+        if x.ndim == 1:
+            return out_rows[0], out_vals[0]
+        return out_rows, out_vals
+
     def destroy(self) -> bool:
         for sh in self.shards:
             sh.destroy()
         return True
+
+
+def topk_rank_key(vals: np.ndarray) -> np.ndarray:
+    """Unsigned keys whose order is the top-k pull's rank (include/glint_gpu.h): Int/Long the value with
+    its sign bit flipped; Float/Double the sign-flip key after -0 -> +0, with every NaN mapped to 0, below
+    -inf's key."""
+    vals = np.ascontiguousarray(vals)
+    bits = 8 * vals.dtype.itemsize
+    ut = np.dtype(f"uint{bits}").type
+    sign = ut(1 << (bits - 1))
+    if not np.issubdtype(vals.dtype, np.floating):
+        return vals.view(ut) ^ sign
+    u = np.where(vals == 0, ut(0), vals.view(ut))  # -0 -> +0
+    key = np.where((u & sign) != 0, ~u, u | sign)
+    return np.where(np.isnan(vals), ut(0), key).astype(ut)
 
 
 class Client:

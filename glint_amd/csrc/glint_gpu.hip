@@ -1266,6 +1266,16 @@ inline int pull_dot_args(const glint_shard* s, const void* rows, int64_t n, cons
   return GLINT_OK;
 }
 
+// argument checks of glint_mat_pull_topk / _dev: a matrix shard, x and both outputs present, 1 to
+// GLINT_TOPK_MAX_QUERIES queries, 1 <= k <= GLINT_TOPK_MAX_K
+inline int pull_topk_args(const glint_shard* s, const void* x, int64_t q, int64_t k, const void* out_rows,
+                          const void* out_vals) {
+  if (!s || s->part.cols == 0) return GLINT_EINVAL;
+  if (!x || !out_rows || !out_vals) return GLINT_EINVAL;
+  if (q < 1 || q > GLINT_TOPK_MAX_QUERIES || k < 1 || k > GLINT_TOPK_MAX_K) return GLINT_EINVAL;
+  return GLINT_OK;
+}
+
 // argument check of the element-wise device-resident calls: a vector (matrix) shard, n >= 0
 inline int elem_args(const glint_shard* s, bool mat, int64_t n) {
   if (!s || n < 0) return GLINT_EINVAL;
@@ -1332,7 +1342,7 @@ std::atomic<unsigned> g_env_gen{1};
 
 extern "C" {
 
-int glint_version(void) { return 600; }  // 0.6.0: glint_mat_push_rows_axpy / _dev, GLINT_K_PUSH_ROWS_AXPY
+int glint_version(void) { return 700; }  // 0.7.0: glint_mat_pull_topk / _dev
 
 int glint_reload_env(void) {
   g_env_gen.fetch_add(1, std::memory_order_acq_rel);
@@ -1505,12 +1515,27 @@ int glint_prof_read(glint_shard_t s, int kernel_id, double* total_ms, int64_t* l
   return GLINT_OK;
 }
 
+int glint_prof_read_launches(glint_shard_t s, int kernel_id, double* ms, int64_t cap, int64_t* launches) {
+  if (!s || kernel_id < 0 || kernel_id >= GLINT_K_COUNT || cap < 0 || (cap > 0 && !ms)) return GLINT_EINVAL;
+  ShardLock lk(s);
+  DeviceGuard g(s->device);
+  prof_drain(s);
+  const std::vector<float>& each = s->prof_each[kernel_id];
+  for (int64_t i = 0; i < cap && i < (int64_t)each.size(); ++i) ms[i] = each[(size_t)i];
+  if (launches) *launches = (int64_t)each.size();
+  return GLINT_OK;
+}
+
 int glint_prof_reset(glint_shard_t s) {
   if (!s) return GLINT_EINVAL;
   ShardLock lk(s);
   DeviceGuard g(s->device);
   prof_drain(s);
-  for (int k = 0; k < GLINT_K_COUNT; ++k) { s->prof_ms[k] = 0; s->prof_n[k] = 0; }
+  for (int k = 0; k < GLINT_K_COUNT; ++k) {
+    s->prof_ms[k] = 0;
+    s->prof_n[k] = 0;
+    s->prof_each[k].clear();
+  }
   return GLINT_OK;
 }
 
@@ -1712,6 +1737,13 @@ int glint_mat_pull_rows_dot_dev(glint_shard_t s, const int64_t* rows, int64_t n,
   if (args_rc == GLINT_OK && n == 0) return GLINT_OK;
   return dev_call(s, args_rc, stream, [&](hipStream_t st) -> int {
     GLINT_DISPATCH(s->dtype, pull_rows_dot, s, (const i64*)rows, n, x, q, out, st);
+  });
+}
+
+int glint_mat_pull_topk_dev(glint_shard_t s, const void* x, int64_t q, int64_t k, int64_t* out_rows, void* out_vals,
+                            void* stream) {
+  return dev_call(s, pull_topk_args(s, x, q, k, out_rows, out_vals), stream, [&](hipStream_t st) -> int {
+    GLINT_DISPATCH(s->dtype, pull_topk, s, x, q, k, (i64*)out_rows, out_vals, st);
   });
 }
 
@@ -2658,6 +2690,32 @@ int host_pull_rows_dot(glint_shard* s, const int64_t* rows, int64_t n, const voi
   return finish(s);
 }
 
+// glint_mat_pull_topk: x is staged, the scores and the selection levels run on the shard's stream with
+// their scratch in the shard's deterministic-path scratch, and the q * k rows and scores -- behind x in
+// the staging block -- come back: q * k * (8 + vsize) bytes, nothing of size `rows`.
+int host_pull_topk(glint_shard* s, const void* x, int64_t q, int64_t k, int64_t* out_rows, void* out_vals) {
+  ShardLock lk(s);
+  DeviceGuard dg(s->device);
+  int rc = host_enter(s, HostEntry::OrderFlush);
+  if (rc) return rc;
+  Staged st;
+  const void* src[1] = {x};
+  size_t bytes[1] = {(size_t)q * (size_t)s->part.cols * s->vsize};
+  const size_t rows_bytes = pad256((size_t)q * (size_t)k * 8), vals_bytes = (size_t)q * (size_t)k * s->vsize;
+  char* d_out = nullptr;
+  rc = stage(s, src, bytes, 1, st, rows_bytes + vals_bytes, &d_out);
+  if (rc) return rc;
+  HostCall hc(s);  // (no rows are named: nothing is recorded)
+  rc = [&]() -> int {
+    GLINT_DISPATCH(s->dtype, pull_topk, s, (const void*)st.p[0], q, k, (i64*)d_out, (void*)(d_out + rows_bytes),
+                   s->stream);
+  }();
+  if (rc) return launch_failed(s, rc);
+  HIPCHK(hipMemcpyAsync(out_rows, d_out, (size_t)q * (size_t)k * 8, hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(hipMemcpyAsync(out_vals, d_out + rows_bytes, vals_bytes, hipMemcpyDeviceToHost, s->stream));
+  return finish(s);
+}
+
 // glint_mat_push_rows_axpy: every row is checked before anything is enqueued (a rejected message applies
 // nothing), then rows, coef and x are staged in one block -- n * 8 + (n * q + q * cols) values, never
 // n * cols -- and the push runs on the shard's stream in message order (kPushHostSequential). Nothing
@@ -2686,6 +2744,11 @@ int host_push_rows_axpy(glint_shard* s, const int64_t* rows, int64_t n, const vo
 }  // namespace
 
 extern "C" {
+
+int glint_mat_pull_topk(glint_shard_t s, const void* x, int64_t q, int64_t k, int64_t* out_rows, void* out_vals) {
+  if (int rc = pull_topk_args(s, x, q, k, out_rows, out_vals)) return rc;
+  return host_pull_topk(s, x, q, k, out_rows, out_vals);
+}
 
 int glint_mat_push_rows_axpy(glint_shard_t s, const int64_t* rows, int64_t n, const void* coef, const void* x,
                              int64_t q, int flags) {

@@ -172,6 +172,7 @@ struct glint_shard {
   bool prof = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev[GLINT_K_COUNT];
   double prof_ms[GLINT_K_COUNT] = {0};
+  std::vector<float> prof_each[GLINT_K_COUNT];  // every launch's time, in launch order (glint_prof_read_launches)
   int64_t prof_n[GLINT_K_COUNT] = {0};
   // host-side time accounting (GLINT_HOST_PROF=1, read at create; printed to stderr at destroy as
   // one "glint_host_prof {...}" line): what the message path's calls spend where
@@ -393,6 +394,7 @@ inline void prof_drain(glint_shard* s) {
       if (hipEventSynchronize(pr.second) == hipSuccess && hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) {
         s->prof_ms[k] += ms;
         s->prof_n[k] += 1;
+        s->prof_each[k].push_back(ms);
       }
       (void)hipEventDestroy(pr.first);
       (void)hipEventDestroy(pr.second);
@@ -521,4 +523,10 @@ int pull_rows_sum(glint_shard* s, const i64* rows, i64 n, const i64* grp_ptr, i6
 // recorded in err_of(s). One launch on st, no host synchronisation.
 template <typename V>
 int pull_rows_dot(glint_shard* s, const i64* rows, i64 n, const void* x, i64 q, void* out, hipStream_t st);
+// top-k row pull (glint_topk.hip), instantiated for the same V: out_rows / out_vals (q x k, dense) = per
+// query vector of x (q x cols, dense) the k best-ranking rows of the shard as global keys and scores, in
+// the order include/glint_gpu.h fixes; device pointers. The scores launch and one launch per selection
+// level on st, no host synchronisation; the scratch is s->d_det.
+template <typename V>
+int pull_topk(glint_shard* s, const void* x, i64 q, i64 k, i64* out_rows, void* out_vals, hipStream_t st);
 }  // namespace glint

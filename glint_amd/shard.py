@@ -670,6 +670,49 @@ class PartialMatrix(_Shard):
         raise ValueError(f"x: shape {tuple(xshape)}, expected ({self.cols},) or (q, {self.cols}) with "
                          f"1 <= q <= {N.GLINT_DOT_MAX_QUERIES}")
 
+    def getTopK(self, x, k: int, sync: bool = True):
+        """The ``k`` rows of the shard that score highest against caller vectors (an extension;
+        glint_mat_pull_topk*): ``x`` of shape (cols,) gives ``(rows[k], vals[k])``, ``x`` of shape
+        (q, cols) two (q, k) arrays. A score is getRowsDot's ``dot(row, x[j])``, bit for bit. Rows come
+        by rank descending, then global row ascending: every NaN ranks below every number, -0 equals +0,
+        Int/Long rank by the signed value. ``rows`` holds global keys (int64); a shard of fewer than
+        ``k`` rows fills the rest with row -1 and value 0.
+
+        Host array: x goes up, the q x k pairs come back -- nothing of the shard's size crosses the
+        link. Device tensor: stream-ordered launches on the current stream, device tensors returned
+        (``sync=False`` leaves the wait to the caller)."""
+        k = int(k)
+        if not 1 <= k <= N.GLINT_TOPK_MAX_K:
+            raise ValueError(f"k: {k}, expected 1 <= k <= {N.GLINT_TOPK_MAX_K}")
+        if _is_torch_cuda(x):
+            import torch
+            if x.dtype != self.torch_dtype or not x.is_contiguous() or x.device.index != self.device:
+                raise TypeError(f"x: expected a contiguous {self.torch_dtype} CUDA tensor on cuda:{self.device}")
+            q, shape = self._topk_shape(tuple(x.shape), k)
+            rows = torch.empty(shape, dtype=torch.int64, device=x.device)
+            vals = torch.empty(shape, dtype=self.torch_dtype, device=x.device)
+            check(self.lib.glint_mat_pull_topk_dev(self.handle, x.data_ptr(), q, k, rows.data_ptr(), vals.data_ptr(),
+                                                   self._stream_of(x)), self.handle)
+            if sync:
+                self.sync(self._stream_of(x))
+            return rows, vals
+        x = _host(x, self.np_dtype)
+        q, shape = self._topk_shape(x.shape, k)
+        rows = np.empty(shape, np.int64)
+        vals = np.empty(shape, self.np_dtype)
+        check(self.lib.glint_mat_pull_topk(self.handle, x.ctypes.data, q, k, rows.ctypes.data, vals.ctypes.data),
+              self.handle)
+        return rows, vals
+
+    def _topk_shape(self, xshape, k: int):
+        """(q, answer shape) of getTopK for query vectors of shape ``xshape``."""
+        if xshape == (self.cols,):
+            return 1, (k,)
+        if len(xshape) == 2 and xshape[1] == self.cols and 1 <= xshape[0] <= N.GLINT_TOPK_MAX_QUERIES:
+            return xshape[0], (xshape[0], k)
+        raise ValueError(f"x: shape {tuple(xshape)}, expected ({self.cols},) or (q, {self.cols}) with "
+                         f"1 <= q <= {N.GLINT_TOPK_MAX_QUERIES}")
+
     def push_wire(self, payload: bytes, deterministic: bool = False) -> int:
         buf = (C.c_uint8 * len(payload)).from_buffer_copy(payload)
         mid = C.c_int32()

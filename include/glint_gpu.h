@@ -266,6 +266,33 @@ int glint_mat_pull_rows_dot(glint_shard_t shard, const int64_t* rows, int64_t n,
 int glint_mat_push_rows_axpy(glint_shard_t shard, const int64_t* rows, int64_t n, const void* coef, const void* x,
                              int64_t q, int flags);
 
+/* Top-k row pull (an extension: the reference has no such message): for each of q query vectors, the k
+ * rows of the shard that score highest against it -- nearest-row search, candidate retrieval -- answered
+ * with q x k (row, score) pairs whatever the shard's size.
+ *   x         q x cols values of the shard's type, dense row-major;
+ *   out_rows  q x k global row keys, dense; out_vals  q x k scores of the shard's type, dense.
+ * Scores. For query j every row of the shard is scored dot(row, x[j]) with the row dot pull's arithmetic
+ * (glint_mat_pull_rows_dot above: E, lane ownership and ascending columns, products rounded before the
+ * add, the xor butterfly, Int/Long wrap): the score bits of a row are what glint_mat_pull_rows_dot returns
+ * for it. Only `cols` elements of a row are read, never the pitch padding.
+ * Order. Rows are ordered by rank descending, then global row ascending. Float/Double rank: every NaN
+ * ranks below every number (-inf included), all NaNs rank equal, -0 equals +0, otherwise the numeric
+ * value. Int/Long rank: the signed value.
+ * Answer. Entry t of query j is the t-th row in that order: out_rows[j*k + t] its global key (on a cyclic
+ * shard index + local * parts), out_vals[j*k + t] its score (a NaN's payload and sign are unspecified).
+ * A shard of fewer than k rows fills the remaining entries with row -1 and value +0 / 0. The call is
+ * deterministic -- no atomics -- and the answer is a function of the shard, x and k only. There are no
+ * flags and no row errors: the caller names no rows.
+ * GLINT_EINVAL: a NULL or vector shard, NULL x, q outside [1, GLINT_TOPK_MAX_QUERIES], k outside
+ * [1, GLINT_TOPK_MAX_K], NULL out_rows or out_vals. Staged to the device: x; copied back:
+ * q * k * (8 + sizeof V) bytes -- nothing of size `rows` crosses the link. */
+#define GLINT_TOPK_MAX_K 1024
+#define GLINT_TOPK_MAX_QUERIES 64
+/* Candidates one workgroup selects from (tests size their cases by it; the answer never depends on it). */
+#define GLINT_TOPK_TILE 4096
+int glint_mat_pull_topk(glint_shard_t shard, const void* x, int64_t q, int64_t k, int64_t* out_rows,
+                        void* out_vals);
+
 /* After GLINT_EOUTOFRANGE: index (within the failing call) of the first rejected record. */
 int glint_shard_last_error(glint_shard_t shard, int64_t* first_bad_record);
 
@@ -316,6 +343,13 @@ int glint_mat_pull_rows_sum_dev(glint_shard_t shard, const int64_t* rows, int64_
  * element. */
 int glint_mat_pull_rows_dot_dev(glint_shard_t shard, const int64_t* rows, int64_t n, const void* x, int64_t q,
                                 void* out, void* stream);
+
+/* glint_mat_pull_topk, device-resident: the same answer, stream-ordered on `stream` with no host
+ * synchronisation: one scores launch and one launch per selection level. out_rows and out_vals must not
+ * overlap x. x is read by 16 B when it is 16-B aligned (and cols allow), else element by element: the
+ * same bits either way. Scratch is the shard's growable device scratch. */
+int glint_mat_pull_topk_dev(glint_shard_t shard, const void* x, int64_t q, int64_t k, int64_t* out_rows,
+                            void* out_vals, void* stream);
 
 /* glint_mat_push_rows_axpy, device-resident: the same contributions in the same order, stream-ordered on
  * `stream` with no host synchronisation. A row outside the partition is skipped and reported by
@@ -505,13 +539,20 @@ enum glint_kernel_id {
    * count kernel and the launches of its scan, so the sum is the pull's whole device time */
   GLINT_K_PULL_ROWS_SPARSE = 9,
   GLINT_K_PULL_ROWS_SUM = 10, /* the grouped row-sum pull (glint_mat_pull_rows_sum*): one launch per call */
-  GLINT_K_PULL_ROWS_DOT = 11, /* the row dot-product pull (glint_mat_pull_rows_dot*): one launch per call */
+  /* the row dot-product pull (glint_mat_pull_rows_dot*): one launch per call. Also every launch of a top-k
+   * pull (glint_mat_pull_topk*), which is a dot pull over every row plus a selection: its scores launch
+   * and one launch per selection level, so the sum is that pull's whole device time */
+  GLINT_K_PULL_ROWS_DOT = 11,
   /* the fold of a row axpy push (glint_mat_push_rows_axpy*): one launch per non-empty call */
   GLINT_K_PUSH_ROWS_AXPY = 12,
   GLINT_K_COUNT = 13
 };
 int glint_prof_enable(glint_shard_t shard, int on);
 int glint_prof_read(glint_shard_t shard, int kernel_id, double* total_ms, int64_t* launches);
+/* The device time of every launch of one kind since the last reset, in launch order: the first
+ * min(cap, *launches) of them are written to ms (a call that launches several kernels under one id, as a
+ * top-k pull does, is told apart launch by launch). */
+int glint_prof_read_launches(glint_shard_t shard, int kernel_id, double* ms, int64_t cap, int64_t* launches);
 int glint_prof_reset(glint_shard_t shard);
 
 /* ---- misc ---------------------------------------------------------------------------------- */

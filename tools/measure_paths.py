@@ -3,7 +3,7 @@ device-resident rates from HIP events around each kernel (glint_prof_*), and hos
 ("end-to-end": pageable host memory -> H2D -> kernels -> D2H) rates by wall clock, which is what
 the JNI shim sees. One JSON line per measurement on stdout.
 
-    python tools/measure_paths.py [--quick] [--sparse] [--rowsum] [--dot] [--axpy [--out FILE]]
+    python tools/measure_paths.py [--quick] [--sparse] [--rowsum] [--dot] [--axpy [--out FILE]] [--topk [--out FILE]]
 
 --sparse runs only the sparse-row-pull leg (dense getRows against getRowsSparse on a cfg5 shard).
 --rowsum runs only the grouped row-sum leg (getRowsSum against a dense row pull plus a reduction by the
@@ -12,6 +12,8 @@ caller, on a cfg5 shard).
 caller, on a cfg5 shard).
 --axpy runs only the row axpy push leg (updateRowsAxpy against coef @ x by the caller plus a row push, on
 cfg5 shards) and appends its lines to profiles/axpy/axpy_push.jsonl (or FILE).
+--topk runs only the top-k pull leg (getTopK against a dot pull over every row plus a selection by the
+caller, on a cfg5 shard) and appends its lines to profiles/topk/topk_pull.jsonl (or FILE).
 """
 import ctypes as C
 import json
@@ -426,7 +428,150 @@ def axpy_leg(rng, out_path):
         sh.destroy()
 
 
+def topk_leg(rng, out_path):
+    """cfg5 per GPU: a 2^17 x 512 Double shard, the k = 16 best rows against q = 1, 8 and 64 query vectors.
+    Host: glint_mat_pull_topk against glint_mat_pull_rows_dot over arange(size) + np.argpartition, wall time;
+    the dense host pull of the whole shard alone for scale. Device: glint_mat_pull_topk_dev against
+    glint_mat_pull_rows_dot_dev over arange(size) + torch.topk, a HIP event pair around each call. The legs
+    alternate inside each of 5 rounds after a warm-up round, in this one process. The baselines never run
+    the code under test, and both legs must name the same rows. The launches of a top-k call apart
+    (glint_prof_read_launches): its scores launch against the dot kernel over the same rows at q = 1 and at
+    this q, and its selection launches summed. One JSON line per q, also appended to out_path."""
+    shard_rows, cols, k, rounds = 1 << 17, 512, 16, 5
+    msh = glint_amd.PartialMatrix(glint_amd.RangePartition(0, 0, shard_rows), cols, "double", 0)
+    h = msh.handle
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(7)
+    d_all = torch.arange(shard_rows, dtype=torch.int64, device=dev)
+    for r0 in range(0, shard_rows, 1 << 14):  # fill in slices of whole rows
+        vv = torch.rand((1 << 14, cols), dtype=torch.float64, device=dev, generator=gen) - 0.5
+        msh.updateRows(d_all[r0:r0 + (1 << 14)].contiguous(), vv)
+    del vv
+    all_rows = np.arange(shard_rows, dtype=np.int64)
+    dense_out = np.empty((shard_rows, cols), np.float64)
+    DOT = N.GLINT_K_PULL_ROWS_DOT
+
+    def ev_ms(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b)
+
+    def wall_ms(fn):
+        t0 = time.perf_counter()
+        fn()
+        return (time.perf_counter() - t0) * 1e3
+
+    def stats(ms):
+        return {"mean": float(np.mean(ms)), "min": float(np.min(ms)), "max": float(np.max(ms))}
+
+    def launches(reps, fn):
+        """Per-launch device ms of `reps` calls of fn, as (reps, launches per call)."""
+        lib.glint_prof_reset(h)
+        lib.glint_prof_enable(h, 1)
+        for _ in range(reps):
+            fn()
+        torch.cuda.synchronize()
+        cnt = C.c_int64()
+        lib.glint_prof_read_launches(h, DOT, None, 0, C.byref(cnt))
+        ms = (C.c_double * cnt.value)()
+        lib.glint_prof_read_launches(h, DOT, ms, cnt.value, C.byref(cnt))
+        lib.glint_prof_enable(h, 0)
+        return np.array(ms[:]).reshape(reps, -1)
+
+    Path(out_path).parent.mkdir(parents=True, exist_ok=True)
+    for q in (1, 8, 64):
+        x = rng.standard_normal((q, cols))
+        d_x = torch.from_numpy(x).to(dev)
+        top_rows, top_vals = np.empty((q, k), np.int64), np.empty((q, k), np.float64)
+        dot_out = np.empty((shard_rows, q), np.float64)
+        base_rows = np.empty((q, k), np.int64)
+        d_top_rows = torch.empty((q, k), dtype=torch.int64, device=dev)
+        d_top_vals = torch.empty((q, k), dtype=torch.float64, device=dev)
+        d_dot = torch.empty((shard_rows, q), dtype=torch.float64, device=dev)
+        d_base = {}
+
+        def host_topk():
+            assert lib.glint_mat_pull_topk(h, x.ctypes.data, q, k, top_rows.ctypes.data, top_vals.ctypes.data) == 0
+
+        def host_base():
+            assert lib.glint_mat_pull_rows_dot(h, all_rows.ctypes.data, shard_rows, x.ctypes.data, q,
+                                               dot_out.ctypes.data) == 0
+            base_rows[:] = np.argpartition(-dot_out.T, k - 1, axis=1)[:, :k]
+
+        def host_dense_pull():
+            assert lib.glint_mat_pull_rows(h, all_rows.ctypes.data, dense_out.ctypes.data, shard_rows) == 0
+
+        def dev_topk():
+            assert lib.glint_mat_pull_topk_dev(h, d_x.data_ptr(), q, k, d_top_rows.data_ptr(), d_top_vals.data_ptr(),
+                                               stream) == 0
+
+        def dev_dot(qq=q):
+            assert lib.glint_mat_pull_rows_dot_dev(h, d_all.data_ptr(), shard_rows, d_x.data_ptr(), qq,
+                                                   d_dot.data_ptr(), stream) == 0
+
+        def dev_base():
+            dev_dot()
+            d_base["vals"], d_base["rows"] = torch.topk(d_dot.t(), k, dim=1)
+
+        t = {name: [] for name in ("host_topk", "host_base", "host_dense_pull", "dev_topk", "dev_base")}
+        for rnd in range(rounds + 1):  # round 0 warms up; the legs alternate inside every round
+            got = {"host_base": wall_ms(host_base), "host_topk": wall_ms(host_topk)}
+            if q == 1:
+                got["host_dense_pull"] = wall_ms(host_dense_pull)
+            torch.cuda.synchronize()
+            got["dev_base"] = ev_ms(dev_base)
+            got["dev_topk"] = ev_ms(dev_topk)
+            if rnd:
+                for name, v in got.items():
+                    t[name].append(v)
+        msh.sync(stream)
+        # both legs name the same rows (random Double scores: no ties), and the two calls the same bits
+        d_rows_h = d_top_rows.cpu().numpy()
+        same_host = bool(np.array_equal(np.sort(base_rows, axis=1), np.sort(top_rows, axis=1)))
+        same_dev = bool(np.array_equal(np.sort(d_base["rows"].cpu().numpy(), axis=1), np.sort(d_rows_h, axis=1)))
+        assert same_host and same_dev
+        identical = bool(np.array_equal(d_rows_h, top_rows) and np.array_equal(d_top_vals.cpu().numpy(), top_vals))
+        each = launches(5, dev_topk)
+        k_scores, k_select = float(each[:, 0].mean()), float(each[:, 1:].sum(axis=1).mean())
+        k_dot_q = float(launches(5, dev_dot).mean())
+        k_dot_1 = float(launches(5, lambda: dev_dot(1)).mean())
+        m = {name: stats(v) for name, v in t.items() if v}
+        line = dict(
+            op="mat_pull_topk", shape=[shard_rows, cols], k=k, queries=q, rounds=rounds,
+            host_topk_ms=m["host_topk"], host_baseline_ms=m["host_base"],
+            host_dense_pull_ms=m.get("host_dense_pull"),
+            host_speedup=m["host_base"]["mean"] / m["host_topk"]["mean"],
+            host_topk_bytes_up=q * cols * 8, host_topk_bytes_back=q * k * 16,
+            host_baseline_bytes_up=shard_rows * 8 + q * cols * 8, host_baseline_bytes_back=shard_rows * q * 8,
+            dev_topk_ms=m["dev_topk"], dev_baseline_ms=m["dev_base"],
+            dev_speedup=m["dev_base"]["mean"] / m["dev_topk"]["mean"],
+            launches_per_call=int(each.shape[1]), scores_kernel_ms=k_scores, selection_kernels_ms=k_select,
+            dot_kernel_same_q_ms=k_dot_q, dot_kernel_q1_ms=k_dot_1,
+            scores_over_dot_q1=k_scores / k_dot_1, scores_over_dot_same_q=k_scores / k_dot_q,
+            selection_over_scores=k_select / k_scores,
+            scores_GBps=shard_rows * cols * 8 / (k_scores * 1e-3) / 1e9,
+            same_rows_host=same_host, same_rows_dev=same_dev, host_and_device_answers_identical=identical,
+            note="host_*: C calls on pageable numpy arrays, synchronous, wall ms; baseline = glint_mat_pull_rows_dot "
+                 "over arange(size) + np.argpartition; host_dense_pull = glint_mat_pull_rows of the whole shard "
+                 "(measured with q = 1 only). dev_*: one HIP event pair per call; baseline = "
+                 "glint_mat_pull_rows_dot_dev over arange(size) + torch.topk. Legs alternate inside each of `rounds` "
+                 "rounds after one warm-up round. *_kernel*_ms: launches apart (glint_prof_read_launches), mean of 5 "
+                 "calls; scores_GBps counts the shard's rows once")
+        emit(**line)
+        with open(out_path, "a") as f:
+            f.write(json.dumps(line) + "\n")
+    msh.destroy()
+
+
 def main():
+    if "--topk" in sys.argv:
+        out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
+            str(Path(__file__).resolve().parent.parent / "profiles" / "topk" / "topk_pull.jsonl")
+        topk_leg(np.random.default_rng(42), out)
+        return
     if "--axpy" in sys.argv:
         out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
             str(Path(__file__).resolve().parent.parent / "profiles" / "axpy" / "axpy_push.jsonl")
