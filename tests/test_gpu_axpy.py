@@ -20,8 +20,9 @@ import glint_amd
 from glint_amd import _native as N
 from glint_amd import ArrayIndexOutOfBoundsException, Client, PartialMatrix, PartialVector, RangePartition
 from oracle import oracle as O
-from axpy_cases import assert_bits, axpy_inputs, bits, nofma_element, nofma_inner, replay_contrib
+from axpy_cases import assert_bits, axpy_inputs, bits, fold_rows, nofma_element, nofma_inner, replay_contrib
 from ieee_cases import write_image
+import test_gpu_rows as R  # the sort ladder's case builders
 
 pytestmark = pytest.mark.gpu
 DT = ["double", "float", "long", "int"]
@@ -140,6 +141,37 @@ def test_axpy_equals_row_push_of_the_replay(gpu, dtype, cols, q, path):
             else:
                 b.updateRows(torch.from_numpy(np.array(rows)).to(d), torch.from_numpy(t).to(d), deterministic=True)
         assert_bits(a.to_numpy(), b.to_numpy())
+
+
+# ---- the sort's geometry ------------------------------------------------------------------------------
+@pytest.mark.parametrize("q", [1, 5])
+@pytest.mark.parametrize("size", R.SORT_SIZES[:-1])
+def test_axpy_push_sort_passes(gpu, size, q):
+    """The row push's ladder of shard sizes (test_gpu_rows.sort_rows: one to three passes of the shared
+    sort, either buffer pair, the runs of RUNS): the axpy fold reads the sorted rows from whichever buffer
+    the sort ended in. Long on every path, Double with deterministic=True; three pushes onto one shard,
+    two records outside on the device paths. Expected: fold_rows over the replayed contributions."""
+    import torch
+    d = torch.device("cuda", gpu)
+    t = lambda a: torch.from_numpy(np.array(a)).to(d)  # noqa: E731
+    cols = R.sort_cols(size)
+    for dtype, path in (("long", "host"), ("long", "dev"), ("long", "dev_det"), ("double", "dev_det")):
+        npd = npd_of(dtype)
+        rng = np.random.default_rng(zlib.crc32(f"axpy/sort/{size}/{q}/{dtype}/{path}".encode()))
+        want = np.zeros((size, cols), npd)
+        with PartialMatrix(RangePartition(2, START, START + size), cols, dtype, gpu) as sh:
+            for n in R.SORT_N:
+                local, _, _ = R.sort_rows(rng, size, n, path != "host")
+                coef, x = axpy_inputs(np.dtype(npd).name, n, q, cols, f"sort/{size}/{path}")
+                inside = (local >= 0) & (local < size)
+                want = fold_rows(want, local[inside], replay_contrib(coef[inside], x))
+                if path == "host":
+                    assert sh.updateRowsAxpy(local + START, coef, x)
+                    continue
+                with pytest.raises(ArrayIndexOutOfBoundsException) as ei:
+                    sh.updateRowsAxpy(t(local + START), t(coef), t(x), deterministic=(path == "dev_det"))
+                assert ei.value.record == int(np.flatnonzero(~inside)[0])
+            assert_bits(sh.to_numpy(), want)
 
 
 # ---- no fused multiply-add ---------------------------------------------------------------------------

@@ -79,6 +79,122 @@ def case(dtype, cols, pattern):
     return rows, values, ref.data, mag
 
 
+# ---- the sort's geometry and the run shapes, constructed ---------------------------------------------
+# rows_front sorts (local row, record index) in ceil(end_bit / 8) passes, end_bit from the sentinel
+# `size`, and the result lies in the second buffer pair when that count is odd. SORT_SIZES are the sizes
+# at which the count, the buffer, or the sentinel's top bit changes: one pass up to 255 rows, two from 256
+# (the sentinel 256 needs bit 8, no valid row does), three from 65 536, four at 2^24 + 1.
+# Run lengths around the fold's depth of 8, its batch of 64 record indices, kRowsChunk = 128 and twice that.
+RUNS = (1, 2, 3, 7, 8, 9, 63, 64, 65, 127, 128, 129, 255, 256, 257)
+SORT_SIZES = [1, 2, 255, 256, 257, 65_535, 65_536, 65_537, (1 << 24) + 1]
+SORT_N = (2047, 2048, 2049)  # records of the three pushes onto one shard: around the sort's 2048-key tile
+SORT_PASSES = {1: 1, 2: 1, 255: 1, 256: 2, 257: 2, 65_535: 2, 65_536: 3, 65_537: 3, (1 << 24) + 1: 4}
+
+
+def sort_passes(size):
+    """The passes rows_front's sort makes for a shard of `size` rows."""
+    end_bit = 1
+    while end_bit < 32 and (1 << end_bit) <= size:
+        end_bit += 1
+    return (end_bit + 7) // 8
+
+
+def sort_cols(size):
+    return 1 if size > 1 << 20 else 3
+
+
+def sort_rows(rng, size, n, bad):
+    """(local rows of one push of n records, the rows that own a run, the runs' lengths). A shard of at
+    least 15 rows: runs of RUNS on distinct rows, the first and the last row among them, and fillers on
+    other rows -- each once where the shard has rows enough -- shuffled; the record pushed last is the
+    last record of the largest row, so it is the last valid record of the sorted list, where the sentinel
+    block begins. Fewer rows: every record on the rows there are. `bad`: two more records, local -1 and
+    `size`."""
+    nb = 2 if bad else 0
+    owners, lengths = np.zeros(0, np.int64), np.zeros(0, np.int64)
+    if size < len(RUNS):
+        local = rng.integers(0, size, n - nb)
+    else:
+        owners = np.concatenate([[0, size - 1], 1 + rng.choice(size - 2, len(RUNS) - 2, replace=False)]).astype(np.int64)
+        lengths = rng.permutation(RUNS)
+        fill = n - nb - sum(RUNS)
+        if size >= 1 << 15:
+            cand = np.setdiff1d(rng.integers(0, size, 4 * fill), owners)
+            fillers = rng.permutation(cand)[:fill]
+            assert fillers.size == fill
+        else:
+            fillers = rng.choice(np.setdiff1d(np.arange(size), owners), fill)
+        local = np.concatenate([np.repeat(owners, lengths), fillers])
+    if bad:
+        local = np.concatenate([local, [-1, size]])
+    local = local.astype(np.int64)
+    rng.shuffle(local)
+    if owners.size:
+        j = np.flatnonzero(local == size - 1)[-1]
+        local[[j, n - 1]] = local[[n - 1, j]]
+    assert local.size == n
+    return local, owners, lengths
+
+
+def sort_values(rng, dtype, shape):
+    """Long: anywhere in the type, so a lost, doubled or misplaced record cannot cancel. Double: mixed
+    magnitudes, 10 ** U(-6, 6) with a sign, so the order of a sum shows."""
+    if dtype == "long":
+        return rng.integers(-2**63, 2**63 - 1, shape, dtype=np.int64, endpoint=True)
+    return rng.choice((-1.0, 1.0), shape) * 10.0 ** rng.uniform(-6, 6, shape)
+
+
+def run_shows_order(terms):
+    """The reversed and the pairwise fold of a run each differ from the sequential one in some column."""
+    from rowsum_cases import replay, replay_pairwise, replay_reversed
+    seq = replay(terms)
+    return bool((seq != replay_reversed(terms)).any() and (seq != replay_pairwise(terms)).any())
+
+
+def order_shows(local, values):
+    """run_shows_order for every run of at least 8 records."""
+    rows, counts = np.unique(local, return_counts=True)
+    return all(run_shows_order(values[local == r]) for r in rows[counts >= 8])
+
+
+def sort_case(size, dtype, bad, what="rows"):
+    """([(rows, values, lowest index outside or None, local rows)] for the three pushes, the table after
+    them: np.add.at over the records inside, in push order). Double: the values of a run of at least 8
+    records are drawn again until run_shows_order holds for it, so a fold in another order cannot pass."""
+    cols = sort_cols(size)
+    rng = np.random.default_rng(zlib.crc32(f"{what}/sort/{size}/{dtype}/{bad}".encode()))
+    pushes = []
+    for n in SORT_N:
+        local, _, _ = sort_rows(rng, size, n, bad)
+        values = sort_values(rng, dtype, (n, cols))
+        inside = (local >= 0) & (local < size)
+        if dtype == "double":
+            rows, counts = np.unique(local[inside], return_counts=True)
+            for r in rows[counts >= 8]:
+                at = np.flatnonzero(local == r)
+                for _ in range(200):
+                    if run_shows_order(values[at]):
+                        break
+                    values[at] = sort_values(rng, dtype, (at.size, cols))
+                else:
+                    raise AssertionError("no draw shows the order")
+            assert order_shows(local[inside], values[inside])
+        if size >= len(RUNS):  # the sorted list's last valid record is the one pushed last
+            assert local[n - 1] == size - 1 == local[inside].max()
+        low = int(np.flatnonzero(~inside)[0]) if bad else None
+        pushes.append((local + START, values, low, local))
+    want = np.zeros((size, cols), values.dtype)
+    for _, values, _, local in pushes:
+        inside = (local >= 0) & (local < size)
+        np.add.at(want, local[inside], values[inside])
+    return pushes, want
+
+
+def same_bits(got, want):
+    assert got.dtype == want.dtype and got.shape == want.shape
+    np.testing.assert_array_equal(got.view(np.uint64), want.view(np.uint64))
+
+
 def push(sh, gpu, rows, values, path):
     if path == "host":
         assert sh.updateRows(rows, values)
@@ -319,6 +435,50 @@ def test_row_push_past_4gib(gpu):
         sh.updateRows(rows, values.view(n, cols))
         got = sh.getRows(torch.arange(R, dtype=torch.int64, device=d))
         assert torch.equal(got, want)
+
+
+@pytest.mark.parametrize("path", PATHS)
+@pytest.mark.parametrize("size", SORT_SIZES)
+def test_row_push_sort_passes(gpu, size, path):
+    """One to four passes of the sort, either buffer pair, 2^k-row shards whose sentinel alone has the top
+    bit; runs of RUNS with the first and the last row among their owners; three pushes of 2047, 2048 and
+    2049 records onto one shard. Long everywhere; Double, bit for bit, on the two paths that keep the
+    order. On the device paths two records lie outside (START - 1 and START + size): skipped, the lower
+    index reported."""
+    import torch
+    d = torch.device("cuda", gpu)
+    assert sort_passes(size) == SORT_PASSES[size]
+    for dtype in ("long",) + (("double",) if path != "dev" else ()):
+        pushes, want = sort_case(size, dtype, path != "host")
+        with PartialMatrix(RangePartition(2, START, START + size), sort_cols(size), dtype, gpu) as sh:
+            for rows, values, low, _ in pushes:
+                if path == "host":
+                    assert sh.updateRows(rows, values)
+                    continue
+                with pytest.raises(ArrayIndexOutOfBoundsException) as ei:
+                    sh.updateRows(torch.from_numpy(rows).to(d), torch.from_numpy(values).to(d),
+                                  deterministic=(path == "dev_det"))
+                assert ei.value.record == low
+            same_bits(sh.to_numpy(), want)
+
+
+@pytest.mark.parametrize("n", [1024 * 2048 + 1, 4096 * 2048 + 1])
+def test_row_push_many_tiles(gpu, n):
+    """1025 tiles: the second trip of the digit totals' loop; 4097 tiles: the second trip of the offsets'
+    scan, with its carry. Long, one column, 65 537 rows (three passes), one push per mode."""
+    import torch
+    d = torch.device("cuda", gpu)
+    size = 65_537
+    rng = np.random.default_rng(n)
+    local = rng.integers(0, size, n)
+    values = rng.integers(-2**63, 2**63 - 1, n, dtype=np.int64, endpoint=True)
+    want = np.zeros(size, np.int64)
+    np.add.at(want, local, values)
+    rows, vals = torch.from_numpy(local + START).to(d), torch.from_numpy(values).to(d)
+    for det in (False, True):
+        with PartialMatrix(RangePartition(2, START, START + size), 1, "long", gpu) as sh:
+            assert sh.updateRows(rows, vals, deterministic=det)
+            np.testing.assert_array_equal(sh.to_numpy()[:, 0], want)
 
 
 def test_row_push_client(gpu):

@@ -7,6 +7,7 @@ import glint_amd
 from glint_amd import _native as N
 from glint_amd import IndexOutOfBoundsException, RangePartitioner
 from glint_amd.client import BigMatrix
+import test_gpu_rows as R  # the case builders only: its tests need a GPU
 
 # glint_version() at the parent of the row push ("Row push")
 PARENT_VERSION = 100
@@ -75,6 +76,39 @@ def test_push_rows_rejects_before_any_shard_is_called():
     with pytest.raises(ValueError):
         m.pushRows(rows[:2], np.ones(13, np.int64))
     assert all(not sh.calls for sh in shards)
+
+
+@pytest.mark.parametrize("size", R.SORT_SIZES)
+def test_sort_cases_hold_their_conditions(size):
+    """What test_gpu_rows.test_row_push_sort_passes relies on, checked on the cases themselves."""
+    assert R.sort_passes(size) == R.SORT_PASSES[size]
+    assert [R.sort_passes(s) % 2 for s in (255, 256, 65_537)] == [1, 0, 1]  # both buffer pairs
+    for dtype, bad in (("long", True), ("double", True), ("double", False)):
+        pushes, want = R.sort_case(size, dtype, bad)
+        assert [p[0].size for p in pushes] == list(R.SORT_N) and want.shape == (size, R.sort_cols(size))
+        for rows, values, low, local in pushes:
+            n = rows.size
+            inside = (local >= 0) & (local < size)
+            assert sorted(local[~inside]) == ([-1, size] if bad else [])
+            assert low == (int(np.flatnonzero(~inside)[0]) if bad else None)
+            assert set(rows[~inside]) == ({R.START - 1, R.START + size} if bad else set())
+            if size < len(R.RUNS):
+                assert set(local[inside]) == set(range(size))  # every record on the rows there are
+                continue
+            # the sorted list as rows_prepare and the stable sort leave it: the sentinel block last
+            order = np.argsort(np.where(inside, local, size), kind="stable")
+            last_valid = order[inside.sum() - 1]
+            assert local[last_valid] == size - 1 and last_valid == n - 1  # ... and the record pushed last
+            runs = dict(zip(*np.unique(local[inside], return_counts=True)))
+            assert runs[0] in R.RUNS and runs[size - 1] in R.RUNS
+            if size >= 1 << 15:  # rows enough: RUNS on distinct rows, every other record alone on its row
+                lengths = sorted(runs.values())
+                assert lengths[-14:] == sorted(R.RUNS)[1:] and set(lengths[:-14]) == {1}
+            else:
+                assert sorted(runs.values())[-9:] == sorted(R.RUNS)[6:]  # (the fillers share the other rows)
+            if dtype == "double":
+                assert R.order_shows(local[inside], values[inside])
+                assert sum(c >= 8 for c in runs.values()) >= sum(r >= 8 for r in R.RUNS)
 
 
 def test_update_rows_is_public():
