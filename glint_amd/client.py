@@ -13,6 +13,9 @@ Mirrors the reference's client factory and asynchronous models, minus the Akka t
   side, whole rows added without expanding them into (row, col, value) triplets.
 * ``BigMatrix.pushAxpy`` -- an extension: rows += coefficients times caller vectors, the contribution
   rows rebuilt on the shards (PartialMatrix.updateRowsAxpy) instead of sent.
+* ``BigMatrix.pushAdagrad`` -- an extension: gradient rows summed per distinct row, then one Adagrad step
+  of this matrix and of a second one that holds the accumulators, on the shards
+  (PartialMatrix.updateRowsAdagrad).
 * ``BigMatrix.pullSum`` -- an extension: the sums of groups of rows, reduced on the shards
   (PartialMatrix.getRowsSum) and combined per group in partition-index order.
 * ``BigMatrix.pullDot`` -- an extension: the dot products of rows with caller vectors (or with
@@ -44,6 +47,11 @@ def bucket(owner: np.ndarray, nparts: int):
     offsets = np.zeros(nparts + 1, dtype=np.int64)
     np.cumsum(counts, out=offsets[1:])
     return order, offsets
+
+
+def _same_partitioner(a, b) -> bool:
+    """Whether two partitioners lay the same key space out the same way: one kind, the same partitions."""
+    return type(a) is type(b) and [repr(p) for p in a.all()] == [repr(p) for p in b.all()]
 
 
 class BigVector:
@@ -149,6 +157,35 @@ class BigMatrix:
             idx = order[off[p]:off[p + 1]]
             if idx.size:
                 sh.updateRowsAxpy(rows[idx], coef[idx], x, deterministic=deterministic)
+        return True
+
+    def pushAdagrad(self, state: "BigMatrix", rows, grads, lr: float, eps: float = 1e-10) -> bool:
+        """Adagrad row push (an extension): this matrix holds the weights and ``state`` -- a BigMatrix
+        with the same partitioner, rows, cols and dtype -- the accumulated squared gradients. ``grads`` is
+        (n, cols) or flat. Per distinct row: its gradient rows are summed in the caller's order, then
+        ``state += G * G`` and ``weights -= (lr * G) / (sqrt(state) + eps)`` on the shard that holds the
+        row (PartialMatrix.updateRowsAdagrad). Bucketed by partition as ``pushRows``; one
+        PartialMatrix.updateRowsAdagrad per non-empty partition, with its rows and gradient rows in the
+        caller's order and that partition's state shard. A row lives in one partition, so the bits are the
+        shard's."""
+        if not isinstance(state, BigMatrix):
+            raise ValueError("state: expected a BigMatrix")
+        dtype = self.shards[0].np_dtype
+        if (state.rows, state.cols) != (self.rows, self.cols) or len(state.shards) != len(self.shards) \
+                or np.dtype(state.shards[0].np_dtype) != np.dtype(dtype) \
+                or not _same_partitioner(state.partitioner, self.partitioner):
+            raise ValueError("state: expected a matrix with this one's partitioner, rows, cols and dtype")
+        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        grads = np.ascontiguousarray(grads, dtype=dtype)
+        if grads.size != rows.size * self.cols:
+            raise ValueError(f"grads: {grads.size} elements, expected {rows.size} rows x {self.cols} columns")
+        grads = grads.reshape(rows.size, self.cols)
+        owner = self.partitioner.partition_indices(rows)
+        order, off = bucket(owner, len(self.shards))
+        for p, sh in enumerate(self.shards):
+            idx = order[off[p]:off[p + 1]]
+            if idx.size:
+                sh.updateRowsAdagrad(state.shards[p], rows[idx], grads[idx], lr, eps)
         return True
 
     def pull(self, rows, cols=None) -> np.ndarray:

@@ -1234,6 +1234,45 @@ inline int push_axpy_args(const glint_shard* s, const void* rows, int64_t n, con
   return GLINT_OK;
 }
 
+// argument checks of glint_mat_push_rows_adagrad / _dev: a Float or Double matrix shard, a second shard
+// of the same type, device and partition that shares no memory with it (the same handle, or two views of
+// one slab that overlap), glint_mat_push_rows's sizes, lr a number and eps >= 0 (a NaN eps fails the test)
+inline int push_adagrad_args(const glint_shard* w, const glint_shard* h, const void* rows, const void* grads,
+                             int64_t n, double lr, double eps) {
+  if (!w || !h || w == h || w->part.cols == 0) return GLINT_EINVAL;
+  if (w->dtype != GLINT_F32 && w->dtype != GLINT_F64) return GLINT_EINVAL;
+  const PartDesc &a = w->part, &b = h->part;
+  if (h->dtype != w->dtype || h->device != w->device || a.cols != b.cols || a.pitch != b.pitch || a.size != b.size ||
+      a.kind != b.kind || a.start != b.start || (a.kind != 0 && (a.cidx != b.cidx || a.cparts != b.cparts)))
+    return GLINT_EINVAL;
+  const uintptr_t wa = (uintptr_t)w->data, ha = (uintptr_t)h->data;
+  const uintptr_t bytes = (uintptr_t)w->elems * w->vsize;  // (h's too: same size, pitch and type)
+  if (wa < ha + bytes && ha < wa + bytes) return GLINT_EINVAL;
+  if (n < 0 || n >= ((i64)1 << 32) - kSortTile) return GLINT_EINVAL;
+  if (n > 0 && (!rows || !grads)) return GLINT_EINVAL;
+  if (lr != lr || !(eps >= 0)) return GLINT_EINVAL;
+  return GLINT_OK;
+}
+
+// Both shards' locks for a call, taken in lock_order (glint_vec_push_dev_shards' rule).
+struct PairLock {
+  glint_shard* o[2];
+  PairLock(glint_shard* a, glint_shard* b) {
+    std::vector<glint_shard*> v{a, b};
+    lock_order(v);
+    o[0] = v[0];
+    o[1] = v[1];
+    o[0]->mu.lock();
+    o[1]->mu.lock();
+  }
+  ~PairLock() {
+    o[1]->mu.unlock();
+    o[0]->mu.unlock();
+  }
+  PairLock(const PairLock&) = delete;
+  PairLock& operator=(const PairLock&) = delete;
+};
+
 // argument checks of glint_mat_pull_rows_sparse / _dev: a matrix shard, 31-bit request count, outputs
 // present unless the call only counts
 inline int pull_sparse_args(const glint_shard* s, const void* rows, int64_t n, const void* row_ptr,
@@ -1342,7 +1381,7 @@ std::atomic<unsigned> g_env_gen{1};
 
 extern "C" {
 
-int glint_version(void) { return 700; }  // 0.7.0: glint_mat_pull_topk / _dev
+int glint_version(void) { return 800; }  // 0.8.0: glint_mat_push_rows_adagrad / _dev
 
 int glint_reload_env(void) {
   g_env_gen.fetch_add(1, std::memory_order_acq_rel);
@@ -1754,6 +1793,25 @@ int glint_mat_push_rows_axpy_dev(glint_shard_t s, const int64_t* rows, int64_t n
   return dev_call(s, args_rc, stream, [&](hipStream_t st) -> int {
     GLINT_DISPATCH(s->dtype, push_rows_axpy, s, (const i64*)rows, n, coef, x, q, flags, st);
   });
+}
+
+int glint_mat_push_rows_adagrad_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows, const void* grads,
+                                    int64_t n, double lr, double eps, void* stream) {
+  if (int rc = push_adagrad_args(weights, state, rows, grads, n, lr, eps)) return rc;
+  if (n == 0) return GLINT_OK;
+  PairLock lk(weights, state);
+  // a slab with views orders itself through their locks, which this call does not hold
+  // (glint_vec_push_dev_shards' rule)
+  if (!weights->views.empty() || !state->views.empty()) return GLINT_EINVAL;
+  DeviceGuard g(weights->device);
+  hipStream_t st = (hipStream_t)stream;
+  for (glint_shard* s : {weights, state}) {  // after both shards' host-pointer work; both marked for their sync
+    if (int rc = dev_order_after_host(s, st)) return rc;
+    (void)pick(s, stream);
+  }
+  if (weights->dtype == GLINT_F64)
+    return push_rows_adagrad<double>(weights, state, (const i64*)rows, grads, n, lr, eps, st);
+  return push_rows_adagrad<float>(weights, state, (const i64*)rows, grads, n, lr, eps, st);
 }
 
 }  // extern "C"
@@ -2741,9 +2799,50 @@ int host_push_rows_axpy(glint_shard* s, const int64_t* rows, int64_t n, const vo
   return finish(s);
 }
 
+// glint_mat_push_rows_adagrad: under both shards' locks every row is checked before anything is staged
+// (a rejected message changes neither shard), then rows and grads are staged in one block -- n * 8 +
+// n * cols values -- and the push runs on the weights shard's stream, which first waits for the state
+// shard's: its flushed ring entries and, through order_after_dev, its last device-resident call. The
+// call ends synchronised, so later calls on either shard see the step. Nothing comes back but the error
+// state.
+int host_push_rows_adagrad(glint_shard* w, glint_shard* h, const int64_t* rows, const void* grads, int64_t n, double lr,
+                           double eps) {
+  PairLock lk(w, h);
+  DeviceGuard g(w->device);
+  int rc = host_enter(w, HostEntry::OrderFlush);
+  if (rc == GLINT_OK) rc = host_enter(h, HostEntry::OrderFlush);
+  if (rc == GLINT_OK) rc = reject_if_bad(w, rows, nullptr, n);
+  if (rc) return rc;
+  if (!h->host_ev && hipEventCreateWithFlags(&h->host_ev, hipEventDisableTiming) != hipSuccess) {
+    (void)hipGetLastError();
+    h->host_ev = nullptr;
+    return GLINT_EDEVICE;
+  }
+  HIPCHK(hipEventRecord(h->host_ev, h->stream));
+  HIPCHK(hipStreamWaitEvent(w->stream, h->host_ev, 0));
+  Staged st;
+  const void* src[2] = {rows, grads};
+  size_t bytes[2] = {(size_t)n * 8, (size_t)n * (size_t)w->part.cols * w->vsize};
+  rc = stage(w, src, bytes, 2, st, 0, nullptr);
+  if (rc) return rc;
+  HostCall hc(w);  // this call's rejected records are its own (d_err_host, read by finish)
+  rc = w->dtype == GLINT_F64
+           ? push_rows_adagrad<double>(w, h, (const i64*)st.p[0], st.p[1], n, lr, eps, w->stream)
+           : push_rows_adagrad<float>(w, h, (const i64*)st.p[0], st.p[1], n, lr, eps, w->stream);
+  if (rc) return launch_failed(w, rc);
+  return finish(w);
+}
+
 }  // namespace
 
 extern "C" {
+
+int glint_mat_push_rows_adagrad(glint_shard_t weights, glint_shard_t state, const int64_t* rows, const void* grads,
+                                int64_t n, double lr, double eps) {
+  if (int rc = push_adagrad_args(weights, state, rows, grads, n, lr, eps)) return rc;
+  if (n == 0) return GLINT_OK;
+  return host_push_rows_adagrad(weights, state, rows, grads, n, lr, eps);
+}
 
 int glint_mat_pull_topk(glint_shard_t s, const void* x, int64_t q, int64_t k, int64_t* out_rows, void* out_vals) {
   if (int rc = pull_topk_args(s, x, q, k, out_rows, out_vals)) return rc;

@@ -503,6 +503,15 @@ int rows_front(glint_shard* s, const i64* rows, i64 n, int flags, hipStream_t st
 template <typename V>
 int push_rows_axpy(glint_shard* s, const i64* rows, i64 n, const void* coef, const void* x, i64 q, int flags,
                    hipStream_t st);
+// Adagrad row push (glint_rowadagrad.hip), instantiated for float and double: per distinct row of the
+// push, G = its gradient rows (grads n x cols, dense, device pointer) added to +0 in push order, then
+// state row += G * G and weights row -= (lr * G) / (sqrt(state row) + eps), in the order
+// include/glint_gpu.h fixes; `state` has `weights`' type, partition, cols and pitch. Rows outside the
+// partition are skipped and recorded in err_of(weights). The front end's launches (weights' scratch) and
+// one fold launch on st, no host synchronisation; under both shards' locks.
+template <typename V>
+int push_rows_adagrad(glint_shard* weights, glint_shard* state, const i64* rows, const void* grads, i64 n, double lr,
+                      double eps, hipStream_t st);
 // sparse row pull (glint_sparse.hip), instantiated for the same V. sparse_count_scan: row_ptr[0..n]
 // (device) = exclusive prefix of the requested rows' non-zero counts; rows outside the partition
 // count 0 and are recorded in err_of(s); the scan's scratch is s->d_det. sparse_emit: the entries

@@ -470,6 +470,41 @@ class PartialMatrix(_Shard):
                                                 flags), self.handle)
         return True
 
+    def updateRowsAdagrad(self, state: "PartialMatrix", rows, grads, lr: float, eps: float = 1e-10,
+                          sync: bool = True) -> bool:
+        """Adagrad row push (an extension; glint_mat_push_rows_adagrad*): this shard holds the weights and
+        ``state`` -- a PartialMatrix of the same type, device, partition and cols -- the accumulated
+        squared gradients. ``grads`` is (n, cols) or flat, dense row-major. Per distinct row of ``rows``:
+        ``G`` = its gradient rows added to +0 in push order, then ``state += G * G`` and ``weights -=
+        (lr * G) / (sqrt(state) + eps)``, every operation rounded on its own in the shard's type
+        (include/glint_gpu.h has the contract): duplicates are coalesced, then one step is taken. There
+        are no order flags: the call is deterministic. Errors as ``updateRows``: host arrays reject a
+        message with a row outside the partition before either shard changes; device tensors skip such a
+        row and raise at the weights shard's sync."""
+        if not isinstance(state, PartialMatrix):
+            raise TypeError("state: expected a PartialMatrix")
+        if np.dtype(self.np_dtype).kind != "f":
+            raise TypeError(f"updateRowsAdagrad needs a Float or Double shard, not {np.dtype(self.np_dtype).name}")
+        if _is_torch_cuda(rows) != _is_torch_cuda(grads):
+            raise TypeError("rows and grads: mixing host arrays and device tensors")
+        if _is_torch_cuda(rows):
+            n = rows.numel()
+            self._check_dev(n, rows, values=grads, value_elems=n * self.cols)
+            rc = self.lib.glint_mat_push_rows_adagrad_dev(self.handle, state.handle, rows.data_ptr(),
+                                                          grads.data_ptr(), n, float(lr), float(eps),
+                                                          self._stream_of(rows))
+            check(rc, self.handle)
+            if sync:
+                self.sync(self._stream_of(rows))
+            return True
+        r = _host(rows, np.int64).reshape(-1)
+        g = _host(grads, self.np_dtype).reshape(-1)
+        if g.size != r.size * self.cols:
+            raise ValueError(f"grads: {g.size} elements, expected {r.size} rows x {self.cols} columns")
+        check(self.lib.glint_mat_push_rows_adagrad(self.handle, state.handle, r.ctypes.data, g.ctypes.data, r.size,
+                                                   float(lr), float(eps)), self.handle)
+        return True
+
     def _axpy_q(self, xshape, cshape, n: int) -> int:
         """q of updateRowsAxpy for vectors of shape ``xshape`` and coefficients of shape ``cshape``."""
         if xshape == (self.cols,):

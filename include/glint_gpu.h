@@ -266,6 +266,40 @@ int glint_mat_pull_rows_dot(glint_shard_t shard, const int64_t* rows, int64_t n,
 int glint_mat_push_rows_axpy(glint_shard_t shard, const int64_t* rows, int64_t n, const void* coef, const void* x,
                              int64_t q, int flags);
 
+/* Adagrad row push (an extension: the reference has no such message): a stateful optimizer step next to
+ * the rows. `weights` and `state` are two Float or Double matrix shards of one type, device, partition
+ * and cols; `state` holds the accumulated squared gradients. One push crosses the link with n x cols
+ * gradients and nothing else, and steps both shards with one read-modify-write per touched row.
+ *   grads  n x cols values of the shards' type V, dense row-major, no pitch (glint_mat_push_rows's vals).
+ * lr and eps are rounded once on the host to V: lr_V, eps_V. For every distinct local row l the push names:
+ *   1. G[c] = (((+0 + g_i0[c]) + g_i1[c]) + ...) over the records i0 < i1 < ... with l(rows[i]) == l: the
+ *      sum runs in push order, in V, from +0.
+ *   2. Per column, with h = state[l][c] and w = weights[l][c], every operation in V and rounded on its own
+ *      (no fused multiply-add, no reassociation):
+ *        s = G * G;  h' = h + s;  r = sqrt(h');  d = r + eps_V;  u = lr_V * G;  p = u / d;  w' = w - p
+ *      h' is stored to state[l][c] and w' to weights[l][c].
+ *   3. sqrt and / are IEEE correctly rounded; subnormal inputs and results are kept; infinities and NaN
+ *      follow IEEE (a NaN's payload and sign are unspecified): G = 0, h = 0, eps = 0 gives 0 / 0 = NaN, and
+ *      an overflowing G * G makes h' infinite and p zero.
+ * This is mini-batch Adagrad as the sparse optimizers of the ML frameworks define it -- duplicates are
+ * coalesced, then one step is taken -- not one step per record. The step needs a row's whole sum, so no run
+ * is ever split and no atomic is used: there are no flags, and the answer is a function of the inputs only,
+ * never of pointer alignment, the slice path or the grid. A row the push does not name is neither read nor
+ * written in either shard, and neither is the pitch padding.
+ * Both shards' locks are held for the call and it is ordered after both shards' earlier work, ring
+ * entries and open batches of `state` included; it is synchronous for both: a following host call on
+ * either shard sees the step. Every row is checked before anything is staged: a row outside the partition
+ * returns GLINT_EOUTOFRANGE (the record's index in glint_shard_last_error(weights)) with both shards
+ * unchanged. A slab with views is refused for either shard, as for every host-pointer call.
+ * GLINT_EINVAL: a NULL, vector, Int or Long `weights`; a NULL `state`, the same handle as `weights`, one
+ * that overlaps it in memory (views of one slab), or one that differs from it in dtype, device, cols, size
+ * or partition (kind, start, and index / parts for cyclic); n < 0, n >= 2^32 - 2048; NULL rows or grads
+ * with n > 0; a NaN lr; !(eps >= 0). n == 0 launches nothing and returns GLINT_OK. Staged to the device:
+ * rows and grads in one block; nothing is copied back. Kernel timing: the one fold launch counts under
+ * GLINT_K_PUSH_ROWS on `weights`; nothing is recorded on `state`. */
+int glint_mat_push_rows_adagrad(glint_shard_t weights, glint_shard_t state, const int64_t* rows, const void* grads,
+                                int64_t n, double lr, double eps);
+
 /* Top-k row pull (an extension: the reference has no such message): for each of q query vectors, the k
  * rows of the shard that score highest against it -- nearest-row search, candidate retrieval -- answered
  * with q x k (row, score) pairs whatever the shard's size.
@@ -360,6 +394,16 @@ int glint_mat_pull_topk_dev(glint_shard_t shard, const void* x, int64_t q, int64
  * element by element; coef element by element: the same bits either way. */
 int glint_mat_push_rows_axpy_dev(glint_shard_t shard, const int64_t* rows, int64_t n, const void* coef,
                                  const void* x, int64_t q, int flags, void* stream);
+
+/* glint_mat_push_rows_adagrad, device-resident: the same step with the same bits, stream-ordered on
+ * `stream` with no host synchronisation, after both shards' host-pointer work; both shards are marked for
+ * their next sync. A row outside the partition is skipped -- it contributes to no G -- and is reported by
+ * glint_shard_sync(weights, ...) as the lowest such record index; every other row is stepped. grads is
+ * read by 16 B when it is 16-B aligned (and cols allow), else element by element: the same bits either
+ * way. A slab that has views is GLINT_EINVAL for either shard (the call holds the two shards' locks, not
+ * the views'). */
+int glint_mat_push_rows_adagrad_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows,
+                                    const void* grads, int64_t n, double lr, double eps, void* stream);
 
 /* glint_vec_push_dev / glint_mat_push_dev behind a device-side gate: the push is enqueued at once,
  * and when it runs it applies NOTHING if the 64-bit device word *gate is nonzero (a route status word,
@@ -534,7 +578,9 @@ enum glint_kernel_id {
   GLINT_K_PUSH_CHECK = 5,   /* order / affinity check over the keys in front of push_apply */
   GLINT_K_PUSH_BINNED = 6,  /* the binned unordered-push pipeline (count, partition, apply) */
   GLINT_K_PUSH_ORDERED = 7, /* the order-preserving push of message-sized pushes (one launch) */
-  GLINT_K_PUSH_ROWS = 8,    /* the per-destination fold of a whole-row push (glint_mat_push_rows*) */
+  /* the per-destination fold of a whole-row push (glint_mat_push_rows*), and the one fold launch of a
+   * non-empty Adagrad row push (glint_mat_push_rows_adagrad*), recorded on its weights shard only */
+  GLINT_K_PUSH_ROWS = 8,
   /* the sparse row pull (glint_mat_pull_rows_sparse*): its emit kernel, and under the same id its
    * count kernel and the launches of its scan, so the sum is the pull's whole device time */
   GLINT_K_PULL_ROWS_SPARSE = 9,

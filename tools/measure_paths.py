@@ -4,6 +4,7 @@ device-resident rates from HIP events around each kernel (glint_prof_*), and hos
 the JNI shim sees. One JSON line per measurement on stdout.
 
     python tools/measure_paths.py [--quick] [--sparse] [--rowsum] [--dot] [--axpy [--out FILE]] [--topk [--out FILE]]
+                                  [--adagrad [--out FILE]]
 
 --sparse runs only the sparse-row-pull leg (dense getRows against getRowsSparse on a cfg5 shard).
 --rowsum runs only the grouped row-sum leg (getRowsSum against a dense row pull plus a reduction by the
@@ -14,6 +15,9 @@ caller, on a cfg5 shard).
 cfg5 shards) and appends its lines to profiles/axpy/axpy_push.jsonl (or FILE).
 --topk runs only the top-k pull leg (getTopK against a dot pull over every row plus a selection by the
 caller, on a cfg5 shard) and appends its lines to profiles/topk/topk_pull.jsonl (or FILE).
+--adagrad runs only the Adagrad row push leg (updateRowsAdagrad against coalescing, two row pulls, the step
+and two row pushes by the caller, on cfg5 shards) and appends its lines to profiles/adagrad/adagrad_push.jsonl
+(or FILE).
 """
 import ctypes as C
 import json
@@ -428,6 +432,132 @@ def axpy_leg(rng, out_path):
         sh.destroy()
 
 
+def adagrad_leg(rng, out_path):
+    """cfg5 per GPU: two 2^17 x 512 Double shards (weights and accumulator), 2^14 and 2^16 Zipf(1.0) rows of
+    gradients. The leg under test steps one pair of shards, its baseline another pair, on alternating
+    rounds of one process.
+    Device: glint_mat_push_rows_adagrad_dev against what a caller does today -- torch.unique + index_add_
+    to coalesce, two glint_mat_pull_rows_dev, the elementwise step in torch, two glint_mat_push_rows_dev of
+    deltas -- a HIP event pair around each; the fold kernel alone by its prof id, and its bytes (n x cols
+    gradients plus a read and a write of distinct x cols in each shard) over that time as a fraction of the
+    HBM peak. Host: glint_mat_push_rows_adagrad against the same done with numpy and the host calls, wall
+    time. The baselines never run the code under test; after each n the two pairs are compared (the
+    baseline sums in another order and adds deltas, so they agree to rounding, not bit for bit). One JSON
+    line per n, also appended to out_path."""
+    shard_rows, cols, rounds = 1 << 17, 512, 5
+    lr, eps, hbm_peak_gbs = 0.05, 1e-8, 8000.0
+    part = glint_amd.RangePartition(0, 0, shard_rows)
+    wa, sa, wb, sb = (glint_amd.PartialMatrix(part, cols, "double", 0) for _ in range(4))
+    all_rows = torch.arange(shard_rows, dtype=torch.int64, device=dev)
+
+    def ev_ms(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b)
+
+    def wall_ms(fn):
+        t0 = time.perf_counter()
+        fn()
+        return (time.perf_counter() - t0) * 1e3
+
+    def stats(ms):
+        return {"mean": float(np.mean(ms)), "min": float(np.min(ms)), "max": float(np.max(ms))}
+
+    Path(out_path).parent.mkdir(parents=True, exist_ok=True)
+    for n in (1 << 14, 1 << 16):
+        rows = zipf_keys(rng, shard_rows, n, 1.0)
+        g = rng.standard_normal((n, cols))
+        d_rows, d_g = torch.from_numpy(rows).to(dev), torch.from_numpy(g).to(dev)
+        distinct = int(np.unique(rows).size)
+
+        def dev_adagrad():
+            assert lib.glint_mat_push_rows_adagrad_dev(wa.handle, sa.handle, d_rows.data_ptr(), d_g.data_ptr(), n,
+                                                       lr, eps, stream) == 0
+
+        def dev_base():
+            uniq, inv = torch.unique(d_rows, return_inverse=True)
+            G = torch.zeros((uniq.numel(), cols), dtype=torch.float64, device=dev).index_add_(0, inv, d_g)
+            w, h = torch.empty_like(G), torch.empty_like(G)
+            assert lib.glint_mat_pull_rows_dev(wb.handle, uniq.data_ptr(), w.data_ptr(), uniq.numel(), stream) == 0
+            assert lib.glint_mat_pull_rows_dev(sb.handle, uniq.data_ptr(), h.data_ptr(), uniq.numel(), stream) == 0
+            s = G * G
+            step = (lr * G) / (torch.sqrt(h + s) + eps)
+            dw = -step
+            assert lib.glint_mat_push_rows_dev(sb.handle, uniq.data_ptr(), s.data_ptr(), uniq.numel(), 0, stream) == 0
+            assert lib.glint_mat_push_rows_dev(wb.handle, uniq.data_ptr(), dw.data_ptr(), uniq.numel(), 0, stream) == 0
+            # (the temporaries are freed into torch's allocator, which reuses them on this stream only)
+
+        def host_adagrad():
+            assert lib.glint_mat_push_rows_adagrad(wa.handle, sa.handle, rows.ctypes.data, g.ctypes.data, n, lr,
+                                                   eps) == 0
+
+        def host_base():
+            uniq, inv = np.unique(rows, return_inverse=True)
+            G = np.zeros((uniq.size, cols))
+            np.add.at(G, inv, g)
+            w, h = np.empty_like(G), np.empty_like(G)
+            assert lib.glint_mat_pull_rows(wb.handle, uniq.ctypes.data, w.ctypes.data, uniq.size) == 0
+            assert lib.glint_mat_pull_rows(sb.handle, uniq.ctypes.data, h.ctypes.data, uniq.size) == 0
+            s = G * G
+            dw = -((lr * G) / (np.sqrt(h + s) + eps))
+            assert lib.glint_mat_push_rows(sb.handle, uniq.ctypes.data, s.ctypes.data, uniq.size, 0) == 0
+            assert lib.glint_mat_push_rows(wb.handle, uniq.ctypes.data, dw.ctypes.data, uniq.size, 0) == 0
+
+        t = {k: [] for k in ("host_adagrad", "host_base", "dev_adagrad", "dev_base")}
+        for rnd in range(rounds + 1):  # round 0 warms up; the two legs alternate inside every round
+            got = {"host_base": wall_ms(host_base), "host_adagrad": wall_ms(host_adagrad)}
+            torch.cuda.synchronize()
+            got["dev_base"] = ev_ms(dev_base)
+            got["dev_adagrad"] = ev_ms(dev_adagrad)
+            if rnd:
+                for k, v in got.items():
+                    t[k].append(v)
+        lib.glint_prof_reset(wa.handle)  # the fold alone, mirrored on the baseline's shards
+        lib.glint_prof_enable(wa.handle, 1)
+        for _ in range(3):
+            dev_adagrad()
+            dev_base()
+        torch.cuda.synchronize()
+        fold_ms = kernel_ms(wa.handle, N.GLINT_K_PUSH_ROWS)
+        lib.glint_prof_enable(wa.handle, 0)
+        for sh in (wa, sa, wb, sb):
+            sh.sync(stream)
+        dw = (wa.getRows(all_rows) - wb.getRows(all_rows)).abs().max().item()
+        ha_, hb_ = sa.getRows(all_rows), sb.getRows(all_rows)
+        dh = ((ha_ - hb_).abs() / hb_.abs().clamp_min(1e-300)).max().item()
+        del ha_, hb_
+        assert dw < 1e-6 and dh < 1e-9, (dw, dh)
+        m = {k: stats(v) for k, v in t.items()}
+        fold_bytes = (n * cols + 4 * distinct * cols) * 8
+        line = dict(
+            op="mat_push_rows_adagrad", pattern="zipf1.0 rows", shape=[shard_rows, cols], rows=n,
+            distinct_rows=distinct, rounds=rounds, lr=lr, eps=eps,
+            host_adagrad_ms=m["host_adagrad"], host_baseline_ms=m["host_base"],
+            host_speedup=m["host_base"]["mean"] / m["host_adagrad"]["mean"],
+            host_adagrad_bytes_staged=n * 8 + n * cols * 8,
+            host_baseline_bytes_over_link=2 * distinct * 8 + 4 * distinct * cols * 8,
+            dev_adagrad_ms=m["dev_adagrad"], dev_baseline_ms=m["dev_base"],
+            dev_speedup=m["dev_base"]["mean"] / m["dev_adagrad"]["mean"],
+            fold_kernel_ms=fold_ms, fold_bytes=fold_bytes, fold_GBps=fold_bytes / (fold_ms * 1e-3) / 1e9,
+            fold_fraction_of_hbm_peak=fold_bytes / (fold_ms * 1e-3) / 1e9 / hbm_peak_gbs, hbm_peak_GBps=hbm_peak_gbs,
+            max_abs_weight_difference=dw, max_relative_state_difference=dh,
+            note="host_*: C calls on pageable numpy arrays, synchronous, wall ms; baseline = np.unique + np.add.at, "
+                 "two glint_mat_pull_rows, the step in numpy, two glint_mat_push_rows of deltas. dev_*: one HIP "
+                 "event pair per call; baseline = torch.unique + index_add_, two glint_mat_pull_rows_dev, the step "
+                 "in torch, two glint_mat_push_rows_dev. "
+                 "Legs alternate inside each of `rounds` rounds after one warm-up round. fold_kernel_ms: the fold "
+                 "alone (glint_prof, GLINT_K_PUSH_ROWS on the weights shard); fold_bytes = (rows + 4 * "
+                 "distinct_rows) * cols * 8")
+        emit(**line)
+        with open(out_path, "a") as f:
+            f.write(json.dumps(line) + "\n")
+    for sh in (wa, sa, wb, sb):
+        sh.destroy()
+
+
 def topk_leg(rng, out_path):
     """cfg5 per GPU: a 2^17 x 512 Double shard, the k = 16 best rows against q = 1, 8 and 64 query vectors.
     Host: glint_mat_pull_topk against glint_mat_pull_rows_dot over arange(size) + np.argpartition, wall time;
@@ -571,6 +701,11 @@ def main():
         out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
             str(Path(__file__).resolve().parent.parent / "profiles" / "topk" / "topk_pull.jsonl")
         topk_leg(np.random.default_rng(42), out)
+        return
+    if "--adagrad" in sys.argv:
+        out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
+            str(Path(__file__).resolve().parent.parent / "profiles" / "adagrad" / "adagrad_push.jsonl")
+        adagrad_leg(np.random.default_rng(42), out)
         return
     if "--axpy" in sys.argv:
         out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
