@@ -26,10 +26,11 @@ CSRC = PKG / "csrc"
 HIP_SOURCES = [CSRC / "glint_gpu.hip", CSRC / "glint_sort.hip", CSRC / "glint_route.hip", CSRC / "glint_ordered.hip", CSRC / "glint_bin.hip",
                CSRC / "glint_exchange.hip", CSRC / "glint_rows.hip", CSRC / "glint_sparse.hip",
                CSRC / "glint_rowsum.hip", CSRC / "glint_rowdot.hip", CSRC / "glint_rowaxpy.hip",
-               CSRC / "glint_topk.hip", CSRC / "glint_rowadagrad.hip"]
+               CSRC / "glint_topk.hip", CSRC / "glint_rowadagrad.hip", CSRC / "glint_pairs.hip"]
 # plain C++: the push planners and the top-k pull's level plan
 PLAN_HEADERS = [CSRC / "glint_push_plan.h", CSRC / "glint_bin_plan.h", CSRC / "glint_topk_plan.h"]
 HIP_HEADERS = [CSRC / "glint_kernels.h", CSRC / "glint_device.h", CSRC / "glint_host.h", CSRC / "glint_dot.h",
+               CSRC / "glint_axpy.h",
                ROOT / "include" / "glint_gpu.h", *PLAN_HEADERS]
 HIP_DEPS = HIP_SOURCES + HIP_HEADERS
 OBJ_DIR = ROOT / "build" / "obj"

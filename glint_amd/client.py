@@ -23,6 +23,10 @@ Mirrors the reference's client factory and asynchronous models, minus the Akka t
   partition, so the answers are only scattered back.
 * ``BigMatrix.pullTopK`` -- an extension: the rows that score highest against caller vectors, selected on
   the shards (PartialMatrix.getTopK) and merged here, at most ``parts * k`` pairs per query.
+* ``BigMatrix.pullPairDot`` / ``BigMatrix.pushPairAxpy`` -- extensions: the two halves of a two-table
+  scoring step, rows of this matrix dotted with, or stepped by coefficients times, rows of a second
+  matrix on the same devices (PartialMatrix.getPairsDot / updatePairsAxpy); pairs are bucketed by (own
+  partition, other partition) and nothing of size ``cols`` leaves the devices.
 
 Out-of-range keys raise ``IndexOutOfBoundsException`` before any shard is touched, as the
 reference's ``partitioner.partition`` does synchronously inside ``mapPartitions``.
@@ -302,6 +306,77 @@ class BigMatrix:
             if idx.size:
                 out[idx] = sh.getRowsDot(rows[idx], x)
         return out
+
+    def _pair_buckets(self, other: "BigMatrix", name: str, rows, other_rows):
+        """What the row-pair calls do before any shard is called: ``other`` is a BigMatrix of this one's
+        cols and dtype (its row count and partitioner are its own), both row arrays are validated by their
+        own partitioner, and the pairs are bucketed by (own partition, other partition). Returns rows,
+        other_rows and the non-empty buckets ``[(p, o, idx)]`` in ascending (p, o) order, ``idx`` the
+        bucket's pair indices in the caller's order. A bucket whose two shards sit on different devices
+        raises ValueError here."""
+        if not isinstance(other, BigMatrix):
+            raise ValueError(f"{name}: expected a BigMatrix")
+        if other.cols != self.cols or np.dtype(other.shards[0].np_dtype) != np.dtype(self.shards[0].np_dtype):
+            raise ValueError(f"{name}: expected a matrix with this one's cols and dtype")
+        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        other_rows = np.ascontiguousarray(other_rows, dtype=np.int64).reshape(-1)
+        if other_rows.size != rows.size:
+            raise ValueError(f"{name} rows: {other_rows.size}, expected {rows.size}")
+        own = self.partitioner.partition_indices(rows)
+        oth = other.partitioner.partition_indices(other_rows)
+        nother = len(other.shards)
+        order, off = bucket(own * nother + oth, len(self.shards) * nother)
+        buckets = []
+        for b in np.flatnonzero(np.diff(off)):
+            p, o = divmod(int(b), nother)
+            da, db = getattr(self.shards[p], "device", None), getattr(other.shards[o], "device", None)
+            if da != db:
+                raise ValueError(f"pairs of partition {p} (device {da}) with partition {o} of {name} (device {db}): "
+                                 "the two shards of a pair must be on one device")
+            buckets.append((p, o, order[off[b]:off[b + 1]]))
+        return rows, other_rows, buckets
+
+    def pullPairDot(self, other: "BigMatrix", rows, otherRows) -> np.ndarray:
+        """Row-pair dot pull (an extension): ``out[i] = dot(row rows[i] of this matrix, row otherRows[i] of
+        other)``, an (n,) array, reduced on the shards (PartialMatrix.getPairsDot): row ids go out and
+        scores come back, nothing of size cols. ``other`` is a BigMatrix with this one's cols and dtype; its
+        row count and partitioner may differ, and it may be this matrix. Both row arrays are validated
+        before any shard is called. Pairs are bucketed by (own partition, other partition); each non-empty
+        bucket gets one shard call, in ascending (own, other) order, with the caller's order inside a
+        bucket, and the answers are scattered back to the caller's positions. A pair lives in one bucket,
+        so nothing is combined here: the bits are the shard's. A bucket whose two shards are on different
+        devices raises ValueError before any shard is called."""
+        rows, other_rows, buckets = self._pair_buckets(other, "other", rows, otherRows)
+        out = np.zeros(rows.size, dtype=self.shards[0].np_dtype)
+        for p, o, idx in buckets:
+            out[idx] = self.shards[p].getPairsDot(other.shards[o], rows[idx], other_rows[idx])
+        return out
+
+    def pushPairAxpy(self, src: "BigMatrix", rows, srcRows, coef, deterministic: bool = False) -> bool:
+        """Row-pair axpy push (an extension): row rows[i] of this matrix += ``coef[i] *`` (row srcRows[i] of
+        ``src``), the contribution rows built on the shards (PartialMatrix.updatePairsAxpy): row ids and
+        coefficients go out, nothing of size cols. ``src`` is another BigMatrix with this one's cols and
+        dtype; its row count and partitioner may differ. ``coef`` is (n,). Both row arrays are validated
+        before any shard is called. Pairs are bucketed by (own partition, source partition); each non-empty
+        bucket gets one shard call, in ascending (own, source) order, with the caller's order inside a
+        bucket. A bucket whose two shards are on different devices raises ValueError before any shard is
+        called.
+
+        Order of a destination row's additions: buckets run in ascending source-partition index, with the
+        caller's order inside a bucket -- source-partition-major. That equals the caller's order when
+        ``src`` has one partition. Deterministic either way (as ``pullSum``'s partition-major rule);
+        Int/Long wrap."""
+        dtype = self.shards[0].np_dtype
+        if src is self:
+            raise ValueError("src: expected another matrix (the source must share no memory with this one)")
+        rows, src_rows, buckets = self._pair_buckets(src, "src", rows, srcRows)
+        coef = np.ascontiguousarray(coef, dtype=dtype).reshape(-1)
+        if coef.size != rows.size:
+            raise ValueError(f"coef: {coef.size} values, expected {rows.size}")
+        for p, o, idx in buckets:
+            self.shards[p].updatePairsAxpy(src.shards[o], rows[idx], src_rows[idx], coef[idx],
+                                           deterministic=deterministic)
+        return True
 
     def pullTopK(self, x, k: int):
         """The ``k`` rows of the matrix that score highest against caller vectors (an extension): ``x``

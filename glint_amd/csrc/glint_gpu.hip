@@ -1273,6 +1273,59 @@ struct PairLock {
   PairLock& operator=(const PairLock&) = delete;
 };
 
+// The locks of a call on two shards that may be one (glint_mat_pull_pairs_dot*): the one lock once --
+// PairLock on the same shard twice would deadlock -- else both in lock_order.
+struct PairOrOneLock {
+  glint_shard* o[2];
+  int k;
+  PairOrOneLock(glint_shard* a, glint_shard* b) : k(a == b ? 1 : 2) {
+    std::vector<glint_shard*> v{a, b};
+    lock_order(v);
+    o[0] = v[0];
+    o[1] = v[1];
+    for (int i = 0; i < k; ++i) o[i]->mu.lock();
+  }
+  ~PairOrOneLock() {
+    for (int i = k - 1; i >= 0; --i) o[i]->mu.unlock();
+  }
+  PairOrOneLock(const PairOrOneLock&) = delete;
+  PairOrOneLock& operator=(const PairOrOneLock&) = delete;
+};
+
+// what the two shards of a row-pair call must share: both matrix shards, one dtype, device and cols
+// (their partitions are independent)
+inline int pairs_shards(const glint_shard* a, const glint_shard* b) {
+  if (!a || !b || a->part.cols == 0 || b->part.cols == 0) return GLINT_EINVAL;
+  if (a->dtype != b->dtype || a->device != b->device || a->part.cols != b->part.cols) return GLINT_EINVAL;
+  return GLINT_OK;
+}
+
+// argument checks of glint_mat_pull_pairs_dot / _dev: pairs_shards, a 31-bit pair count, the arrays
+// present when there are pairs
+inline int pull_pairs_args(const glint_shard* a, const glint_shard* b, const void* rows_a, const void* rows_b,
+                           int64_t n, const void* out) {
+  if (int rc = pairs_shards(a, b)) return rc;
+  if (n < 0 || n >= ((i64)1 << 31)) return GLINT_EINVAL;
+  if (n > 0 && (!rows_a || !rows_b || !out)) return GLINT_EINVAL;
+  return GLINT_OK;
+}
+
+// argument checks of glint_mat_push_pairs_axpy / _dev: pairs_shards, a source that shares no memory with
+// the destination (the same handle, or two views of one slab that overlap), glint_mat_push_rows's flags
+// and sizes, the arrays present when there are records
+inline int push_pairs_args(const glint_shard* dst, const glint_shard* src, const void* rows_dst, const void* rows_src,
+                           const void* coef, int64_t n, int flags) {
+  if (int rc = pairs_shards(dst, src)) return rc;
+  if (dst == src) return GLINT_EINVAL;
+  const uintptr_t da = (uintptr_t)dst->data, sa = (uintptr_t)src->data;
+  if (da < sa + (uintptr_t)src->elems * src->vsize && sa < da + (uintptr_t)dst->elems * dst->vsize)
+    return GLINT_EINVAL;
+  if (flags & ~(GLINT_PUSH_DETERMINISTIC | GLINT_PUSH_UNORDERED)) return GLINT_EINVAL;
+  if (n < 0 || n >= ((i64)1 << 32) - kSortTile) return GLINT_EINVAL;
+  if (n > 0 && (!rows_dst || !rows_src || !coef)) return GLINT_EINVAL;
+  return GLINT_OK;
+}
+
 // argument checks of glint_mat_pull_rows_sparse / _dev: a matrix shard, 31-bit request count, outputs
 // present unless the call only counts
 inline int pull_sparse_args(const glint_shard* s, const void* rows, int64_t n, const void* row_ptr,
@@ -1381,7 +1434,7 @@ std::atomic<unsigned> g_env_gen{1};
 
 extern "C" {
 
-int glint_version(void) { return 800; }  // 0.8.0: glint_mat_push_rows_adagrad / _dev
+int glint_version(void) { return 900; }  // 0.9.0: glint_mat_pull_pairs_dot / glint_mat_push_pairs_axpy / _dev
 
 int glint_reload_env(void) {
   g_env_gen.fetch_add(1, std::memory_order_acq_rel);
@@ -1812,6 +1865,39 @@ int glint_mat_push_rows_adagrad_dev(glint_shard_t weights, glint_shard_t state, 
   if (weights->dtype == GLINT_F64)
     return push_rows_adagrad<double>(weights, state, (const i64*)rows, grads, n, lr, eps, st);
   return push_rows_adagrad<float>(weights, state, (const i64*)rows, grads, n, lr, eps, st);
+}
+
+int glint_mat_pull_pairs_dot_dev(glint_shard_t a, glint_shard_t b, const int64_t* rows_a, const int64_t* rows_b,
+                                 int64_t n, void* out, void* stream) {
+  if (int rc = pull_pairs_args(a, b, rows_a, rows_b, n, out)) return rc;
+  if (n == 0) return GLINT_OK;
+  PairOrOneLock lk(a, b);
+  // a slab with views orders itself through their locks, which this call does not hold
+  // (glint_mat_push_rows_adagrad_dev's rule)
+  if (!a->views.empty() || !b->views.empty()) return GLINT_EINVAL;
+  DeviceGuard g(a->device);
+  hipStream_t st = (hipStream_t)stream;
+  for (int i = 0; i < lk.k; ++i) {  // after both shards' host-pointer work; both marked for their sync
+    if (int rc = dev_order_after_host(lk.o[i], st)) return rc;
+    (void)pick(lk.o[i], stream);
+  }
+  GLINT_DISPATCH(a->dtype, pull_pairs_dot, a, b, (const i64*)rows_a, (const i64*)rows_b, n, out, st);
+}
+
+int glint_mat_push_pairs_axpy_dev(glint_shard_t dst, glint_shard_t src, const int64_t* rows_dst,
+                                  const int64_t* rows_src, const void* coef, int64_t n, int flags, void* stream) {
+  if (int rc = push_pairs_args(dst, src, rows_dst, rows_src, coef, n, flags)) return rc;
+  if (n == 0) return GLINT_OK;
+  PairLock lk(dst, src);
+  if (!dst->views.empty() || !src->views.empty()) return GLINT_EINVAL;  // (as above)
+  DeviceGuard g(dst->device);
+  hipStream_t st = (hipStream_t)stream;
+  for (glint_shard* s : {dst, src}) {  // after both shards' host-pointer work; both marked for their sync
+    if (int rc = dev_order_after_host(s, st)) return rc;
+    (void)pick(s, stream);
+  }
+  GLINT_DISPATCH(dst->dtype, push_pairs_axpy, dst, src, (const i64*)rows_dst, (const i64*)rows_src, coef, n, flags,
+                 st);
 }
 
 }  // extern "C"
@@ -2833,9 +2919,105 @@ int host_push_rows_adagrad(glint_shard* w, glint_shard* h, const int64_t* rows, 
   return finish(w);
 }
 
+// What the two-shard host calls below do first, under both locks (host_push_rows_adagrad's order): both
+// shards are entered, and every pair is checked -- the lowest index with row ra[i] outside `a` or row
+// rb[i] outside `b` is rejected (glint_shard_last_error(a)) before anything is staged -- then a's stream
+// waits for an event on b's: its flushed ring entries and, through order_after_dev, its last
+// device-resident call.
+int pairs_host_enter(glint_shard* a, glint_shard* b, const int64_t* ra, const int64_t* rb, int64_t n) {
+  int rc = host_enter(a, HostEntry::OrderFlush);
+  if (rc == GLINT_OK && b != a) rc = host_enter(b, HostEntry::OrderFlush);
+  if (rc) return rc;
+  const i64 bad_a = host_first_bad(a, ra, nullptr, n), bad_b = host_first_bad(b, rb, nullptr, n);
+  const i64 bad = bad_a < 0 ? bad_b : (bad_b < 0 ? bad_a : std::min(bad_a, bad_b));
+  if (bad >= 0) {
+    a->last_bad = bad;
+    return GLINT_EOUTOFRANGE;
+  }
+  if (b == a) return GLINT_OK;
+  if (!b->host_ev && hipEventCreateWithFlags(&b->host_ev, hipEventDisableTiming) != hipSuccess) {
+    (void)hipGetLastError();
+    b->host_ev = nullptr;
+    return GLINT_EDEVICE;
+  }
+  HIPCHK(hipEventRecord(b->host_ev, b->stream));
+  HIPCHK(hipStreamWaitEvent(a->stream, b->host_ev, 0));
+  return GLINT_OK;
+}
+
+// glint_mat_pull_pairs_dot: pairs_host_enter, then the two row arrays are staged in one block, the one
+// kernel writes its n dots behind them in a's scratch and those come back -- 2 n ids out, n values back,
+// nothing of size cols. The work runs on a's stream and the call ends synchronised.
+int host_pull_pairs_dot(glint_shard* a, glint_shard* b, const int64_t* ra, const int64_t* rb, int64_t n, void* out) {
+  PairOrOneLock lk(a, b);
+  DeviceGuard g(a->device);
+  int rc = pairs_host_enter(a, b, ra, rb, n);
+  if (rc) return rc;
+  Staged st;
+  const void* src[2] = {ra, rb};
+  size_t bytes[2] = {(size_t)n * 8, (size_t)n * 8};
+  const size_t out_bytes = (size_t)n * a->vsize;
+  char* d_out = nullptr;
+  rc = stage(a, src, bytes, 2, st, out_bytes, &d_out);
+  if (rc) return rc;
+  HostCall hc(a);  // (every pair was checked: nothing is recorded)
+  rc = [&]() -> int {
+    GLINT_DISPATCH(a->dtype, pull_pairs_dot, a, b, (const i64*)st.p[0], (const i64*)st.p[1], n, (void*)d_out,
+                   a->stream);
+  }();
+  if (rc) return launch_failed(a, rc);
+  if (st.pinned) {  // answer into the pinned block behind the inputs, then one CPU copy out
+    char* h_out = (char*)a->h_stage + st.in_bytes;
+    HIPCHK(hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, a->stream));
+    rc = finish(a);
+    if (rc == GLINT_OK) std::memcpy(out, h_out, out_bytes);
+    return rc;
+  }
+  HIPCHK(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, a->stream));
+  return finish(a);
+}
+
+// glint_mat_push_pairs_axpy: pairs_host_enter (a rejected message changes nothing), then the two row
+// arrays and coef are staged in one block -- 2 n ids and n values, nothing of size cols -- and the push
+// runs on dst's stream in message order (kPushHostSequential). The call ends synchronised. Nothing comes
+// back but the error state.
+int host_push_pairs_axpy(glint_shard* dst, glint_shard* src, const int64_t* rd, const int64_t* rs, const void* coef,
+                         int64_t n, int flags) {
+  PairLock lk(dst, src);
+  DeviceGuard g(dst->device);
+  int rc = pairs_host_enter(dst, src, rd, rs, n);
+  if (rc) return rc;
+  Staged st;
+  const void* in[3] = {rd, rs, coef};
+  size_t bytes[3] = {(size_t)n * 8, (size_t)n * 8, (size_t)n * dst->vsize};
+  rc = stage(dst, in, bytes, 3, st, 0, nullptr);
+  if (rc) return rc;
+  HostCall hc(dst);  // this call's rejected records are its own (d_err_host, read by finish)
+  rc = [&]() -> int {
+    GLINT_DISPATCH(dst->dtype, push_pairs_axpy, dst, src, (const i64*)st.p[0], (const i64*)st.p[1],
+                   (const void*)st.p[2], n, flags | kPushHostSequential, dst->stream);
+  }();
+  if (rc) return launch_failed(dst, rc);
+  return finish(dst);
+}
+
 }  // namespace
 
 extern "C" {
+
+int glint_mat_pull_pairs_dot(glint_shard_t a, glint_shard_t b, const int64_t* rows_a, const int64_t* rows_b,
+                             int64_t n, void* out) {
+  if (int rc = pull_pairs_args(a, b, rows_a, rows_b, n, out)) return rc;
+  if (n == 0) return GLINT_OK;
+  return host_pull_pairs_dot(a, b, rows_a, rows_b, n, out);
+}
+
+int glint_mat_push_pairs_axpy(glint_shard_t dst, glint_shard_t src, const int64_t* rows_dst, const int64_t* rows_src,
+                              const void* coef, int64_t n, int flags) {
+  if (int rc = push_pairs_args(dst, src, rows_dst, rows_src, coef, n, flags)) return rc;
+  if (n == 0) return GLINT_OK;
+  return host_push_pairs_axpy(dst, src, rows_dst, rows_src, coef, n, flags);
+}
 
 int glint_mat_push_rows_adagrad(glint_shard_t weights, glint_shard_t state, const int64_t* rows, const void* grads,
                                 int64_t n, double lr, double eps) {

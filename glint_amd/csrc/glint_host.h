@@ -512,6 +512,22 @@ int push_rows_axpy(glint_shard* s, const i64* rows, i64 n, const void* coef, con
 template <typename V>
 int push_rows_adagrad(glint_shard* weights, glint_shard* state, const i64* rows, const void* grads, i64 n, double lr,
                       double eps, hipStream_t st);
+// row-pair dot pull (glint_pairs.hip), instantiated for V in {int, long long, float, double}: out[i] = the
+// dot of row rows_a[i] of `a` with row rows_b[i] of `b` (device pointers), each row array translated with
+// its own shard's partition, in the row dot pull's order; `b` has a's type, device and cols and may be
+// `a` itself. A pair with either row outside answers zero and is recorded in err_of(a). One launch on st,
+// recorded on `a`, no host synchronisation; under both shards' locks.
+template <typename V>
+int pull_pairs_dot(glint_shard* a, glint_shard* b, const i64* rows_a, const i64* rows_b, i64 n, void* out,
+                   hipStream_t st);
+// row-pair axpy push (glint_pairs.hip), instantiated for the same V: row rows_dst[i] of `dst` += coef[i] *
+// (row rows_src[i] of `src`) (device pointers), in the order include/glint_gpu.h fixes; `src` has dst's
+// type, device and cols and shares no memory with it. A record with either row outside is skipped and
+// recorded in err_of(dst). The front end's launches (dst's scratch) and one fold launch on st, no host
+// synchronisation; under both shards' locks.
+template <typename V>
+int push_pairs_axpy(glint_shard* dst, glint_shard* src, const i64* rows_dst, const i64* rows_src, const void* coef,
+                    i64 n, int flags, hipStream_t st);
 // sparse row pull (glint_sparse.hip), instantiated for the same V. sparse_count_scan: row_ptr[0..n]
 // (device) = exclusive prefix of the requested rows' non-zero counts; rows outside the partition
 // count 0 and are recorded in err_of(s); the scan's scratch is s->d_det. sparse_emit: the entries

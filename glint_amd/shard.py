@@ -696,6 +696,99 @@ class PartialMatrix(_Shard):
               self.handle)
         return res
 
+    def _pair_other(self, other, name: str) -> None:
+        """The second shard of a row-pair call: a PartialMatrix of this one's type, device and cols."""
+        if not isinstance(other, PartialMatrix):
+            raise TypeError(f"{name}: expected a PartialMatrix")
+        if other.code != self.code or other.cols != self.cols or other.device != self.device:
+            raise ValueError(f"{name}: expected a shard of this one's type, device and cols "
+                             f"({np.dtype(self.np_dtype).name}, cuda:{self.device}, {self.cols}), not "
+                             f"({np.dtype(other.np_dtype).name}, cuda:{other.device}, {other.cols})")
+
+    def _pair_rows_dev(self, rows, other_rows, name: str) -> int:
+        """Device-resident row arrays of a row-pair call: both as _check_dev asks, of one length."""
+        n = rows.numel()
+        self._check_dev(n, rows)
+        if not _is_torch_cuda(other_rows):
+            raise TypeError(f"{name}: expected a CUDA tensor (mixing host arrays and device tensors)")
+        self._check_dev(n, other_rows)
+        return n
+
+    def getPairsDot(self, other: "PartialMatrix", rows, other_rows, out=None, sync: bool = True):
+        """Row-pair dot pull (an extension; glint_mat_pull_pairs_dot*): ``out[i] = dot(row rows[i] of this
+        shard, row other_rows[i] of other)``, an (n,) array, reduced on the device: 2 n row ids go out and n
+        values come back, nothing of size cols. ``other`` is a PartialMatrix of this one's type, device and
+        cols; its partition is its own, and each row array is translated with its own shard's. ``other``
+        may be this shard itself, or a view of the same slab. The arithmetic is ``getRowsDot``'s, word for
+        word: the bits are those of ``getRowsDot([rows[i]], x=other.getRows([other_rows[i]]))``. Rows may
+        repeat; answers keep the caller's order.
+
+        Host arrays: every pair is checked first; a row of either array outside its shard's partition
+        raises with the lowest such index and nothing is written. Device tensors: one stream-ordered launch
+        on the current stream; such a pair answers zero and is raised by this shard's sync (``sync=True``,
+        or a later ``sync()``)."""
+        self._pair_other(other, "other")
+        if _is_torch_cuda(rows):
+            import torch
+            n = self._pair_rows_dev(rows, other_rows, "other_rows")
+            if out is None:
+                out = torch.empty(n, dtype=self.torch_dtype, device=rows.device)
+            self._check_dev(n, rows, out=out)
+            rc = self.lib.glint_mat_pull_pairs_dot_dev(self.handle, other.handle, rows.data_ptr(),
+                                                       other_rows.data_ptr(), n, out.data_ptr(),
+                                                       self._stream_of(rows))
+            check(rc, self.handle)
+            if sync:
+                self.sync(self._stream_of(rows))
+            return out
+        if _is_torch_cuda(other_rows):
+            raise TypeError("rows and other_rows: mixing host arrays and device tensors")
+        r = _host(rows, np.int64).reshape(-1)
+        o = _host(other_rows, np.int64).reshape(-1)
+        if o.size != r.size:
+            raise ValueError(f"other_rows: {o.size} rows, expected {r.size}")
+        res = self._host_out(out, (r.size,))
+        check(self.lib.glint_mat_pull_pairs_dot(self.handle, other.handle, r.ctypes.data, o.ctypes.data, r.size,
+                                                res.ctypes.data), self.handle)
+        return res
+
+    def updatePairsAxpy(self, src: "PartialMatrix", rows, src_rows, coef, deterministic: bool = False,
+                        sync: bool = True, unordered: bool = False) -> bool:
+        """Row-pair axpy push (an extension; glint_mat_push_pairs_axpy*): row rows[i] of this shard +=
+        ``coef[i] *`` (row src_rows[i] of ``src``), the contribution rows built on the device from the
+        second shard instead of sent: 2 n row ids and n coefficients go out, nothing of size cols. ``src``
+        is a PartialMatrix of this one's type, device and cols with a partition of its own; it must share
+        no memory with this shard (not the same shard, not an overlapping view) and is read as it was before
+        the call. ``coef`` is (n,). It is ``updateRows`` with ``values[i] = coef[i] * src.getRows(
+        [src_rows[i]])`` in the shard's type, rounding for rounding: the product is rounded before it is
+        added (no fused multiply-add), Int/Long wrap. Order and errors as ``updateRows``: host arrays keep
+        the push order for Float/Double unless ``unordered`` and reject a message with a row of either array
+        outside its partition before anything is applied; device tensors keep the order with
+        ``deterministic``, skip such a record -- it contributes nothing -- and raise at this shard's
+        sync."""
+        self._pair_other(src, "src")
+        flags = _flags(deterministic, unordered)
+        if _is_torch_cuda(rows):
+            n = self._pair_rows_dev(rows, src_rows, "src_rows")
+            self._check_dev(n, rows, values=coef)
+            rc = self.lib.glint_mat_push_pairs_axpy_dev(self.handle, src.handle, rows.data_ptr(),
+                                                        src_rows.data_ptr(), coef.data_ptr(), n, flags,
+                                                        self._stream_of(rows))
+            check(rc, self.handle)
+            if sync:
+                self.sync(self._stream_of(rows))
+            return True
+        if _is_torch_cuda(src_rows) or _is_torch_cuda(coef):
+            raise TypeError("rows, src_rows and coef: mixing host arrays and device tensors")
+        r = _host(rows, np.int64).reshape(-1)
+        o = _host(src_rows, np.int64).reshape(-1)
+        cf = _host(coef, self.np_dtype).reshape(-1)
+        if o.size != r.size or cf.size != r.size:
+            raise ValueError(f"src_rows: {o.size} rows and coef: {cf.size} values, expected {r.size} of each")
+        check(self.lib.glint_mat_push_pairs_axpy(self.handle, src.handle, r.ctypes.data, o.ctypes.data,
+                                                 cf.ctypes.data, r.size, flags), self.handle)
+        return True
+
     def _dot_shape(self, xshape, n: int):
         """(q, answer shape) of getRowsDot for query vectors of shape ``xshape``."""
         if xshape == (self.cols,):

@@ -300,6 +300,63 @@ int glint_mat_push_rows_axpy(glint_shard_t shard, const int64_t* rows, int64_t n
 int glint_mat_push_rows_adagrad(glint_shard_t weights, glint_shard_t state, const int64_t* rows, const void* grads,
                                 int64_t n, double lr, double eps);
 
+/* Row-pair dot pull (an extension: the reference has no such message): the read half of a two-table
+ * scoring step -- skip-gram with negative sampling, matrix factorisation, any two-tower model -- where
+ * the other operand is not a vector the caller sends but a row of a second shard on the same device.
+ *   out   n values of the shards' type: out[i] = dot(row rows_a[i] of a, row rows_b[i] of b).
+ * 2 n row ids cross the link and n values come back; nothing of size cols does.
+ * Arithmetic: the row dot pull's, word for word (glint_mat_pull_rows_dot above: E, lane ownership
+ * (c / E) % 64, ascending columns per lane from +0, acc = acc + (rowA[c] * rowB[c]) with the product rounded
+ * before the add, the xor butterfly, Int/Long wrap): the bits of out[i] are what
+ * glint_mat_pull_rows_dot(a, &rows_a[i], 1, x = the stored row rows_b[i] of b, 1, ...) returns. Only `cols`
+ * elements of a row of either shard are read, never the pitch padding. No flags, no atomics.
+ * Shards: `a` and `b` are matrix shards of one dtype, device and cols. Their partitions are independent
+ * -- kind, start, size, cyclic index and parts may all differ -- and each row array is translated with
+ * its own shard's partition. `b` may be `a` itself (rows of one table scored against each other;
+ * rows_a[i] == rows_b[i] gives the self-dot's bits), and the two may be views of one slab, overlapping or
+ * not: nothing is written to either.
+ * Both shards' locks are held for the call (the one lock once when b == a) and it is ordered after both
+ * shards' earlier work, as glint_mat_push_rows_adagrad: the work runs on a's stream, which waits for b's,
+ * and the call ends synchronised. Every pair is checked before anything is staged: for the lowest i with
+ * rows_a[i] outside a or rows_b[i] outside b the call returns GLINT_EOUTOFRANGE (i in
+ * glint_shard_last_error(a)) with nothing written to out. A slab with views is refused for either shard,
+ * as for every host-pointer call.
+ * GLINT_EINVAL: a NULL or vector shard; shards that differ in dtype, device or cols; n < 0; n >= 2^31; a
+ * NULL array with n > 0. n == 0 writes nothing and returns GLINT_OK. Staged to the device: the two row
+ * arrays in one block; copied back: n values. Kernel timing: one launch under GLINT_K_PULL_ROWS_DOT on
+ * `a`; nothing is recorded on `b`. */
+int glint_mat_pull_pairs_dot(glint_shard_t a, glint_shard_t b, const int64_t* rows_a, const int64_t* rows_b,
+                             int64_t n, void* out);
+
+/* Row-pair axpy push (an extension: the reference has no such message): the write half of that step,
+ * rows of `dst` += coefficients times rows of a second shard `src` on the same device.
+ *   coef  n values of the shards' type, one per pair.
+ * For i in push order, for c in [0, cols):
+ *   dst[l(rows_dst[i])][c] = dst[l(rows_dst[i])][c] + (coef[i] * src[l_src(rows_src[i])][c]),
+ * the product rounded before the add (no fused multiply-add), all arithmetic in the shards' type; Int/Long
+ * wrap. The call is glint_mat_push_rows(dst, rows_dst, vals) with vals[i] = coef[i] * (row rows_src[i] of
+ * src), rounding for rounding. `src` is read as it was before the call. Subnormal products and sums are
+ * kept; infinities and NaN follow IEEE (inf * 0 is NaN; a NaN's payload and sign are unspecified). Only
+ * `cols` elements of a row of either shard are read or written, never the pitch padding. 2 n row ids and n
+ * coefficients cross the link; nothing of size cols does.
+ * Shards: as glint_mat_pull_pairs_dot (one dtype, device and cols; independent partitions, each row array
+ * translated with its own shard's), but `src` must share no memory with `dst`: the same handle, or two
+ * views of one slab that overlap, is GLINT_EINVAL.
+ * Flags, order and sizes are glint_mat_push_rows's: only GLINT_PUSH_DETERMINISTIC and GLINT_PUSH_UNORDERED
+ * are accepted; Float/Double sums of repeated destination rows keep the push order unless
+ * GLINT_PUSH_UNORDERED is given. Both shards' locks are held and the call is ordered after both shards'
+ * earlier work; it runs on dst's stream, which waits for src's, and ends synchronised. Every pair is
+ * checked before anything is applied: for the lowest i with rows_dst[i] outside dst or rows_src[i] outside
+ * src nothing is applied (GLINT_EOUTOFRANGE, i in glint_shard_last_error(dst)). A slab with views is
+ * refused for either shard.
+ * GLINT_EINVAL: a NULL or vector shard; shards that differ in dtype, device or cols, or share memory;
+ * n < 0; n >= 2^32 - 2048; any other flag; a NULL array with n > 0. n == 0 launches nothing and returns
+ * GLINT_OK. Staged to the device: the two row arrays and coef in one block; nothing is copied back. Kernel
+ * timing: the front end counts as glint_mat_push_rows_axpy's does and the one fold launch under
+ * GLINT_K_PUSH_ROWS_AXPY, both on `dst`; nothing is recorded on `src`. */
+int glint_mat_push_pairs_axpy(glint_shard_t dst, glint_shard_t src, const int64_t* rows_dst,
+                              const int64_t* rows_src, const void* coef, int64_t n, int flags);
+
 /* Top-k row pull (an extension: the reference has no such message): for each of q query vectors, the k
  * rows of the shard that score highest against it -- nearest-row search, candidate retrieval -- answered
  * with q x k (row, score) pairs whatever the shard's size.
@@ -404,6 +461,27 @@ int glint_mat_push_rows_axpy_dev(glint_shard_t shard, const int64_t* rows, int64
  * the views'). */
 int glint_mat_push_rows_adagrad_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows,
                                     const void* grads, int64_t n, double lr, double eps, void* stream);
+
+/* glint_mat_pull_pairs_dot, device-resident: the same dots with the same bits, one launch, stream-ordered
+ * on `stream` with no host synchronisation, after both shards' host-pointer work; both shards are marked
+ * for their next sync. A pair with either row outside its partition answers 0 without a load and is
+ * reported by glint_shard_sync(a, ...) as the lowest such pair index; every other pair is answered. out is
+ * written element by element. A slab that has views is GLINT_EINVAL for either shard (the call holds the
+ * two shards' locks, not the views'). */
+int glint_mat_pull_pairs_dot_dev(glint_shard_t a, glint_shard_t b, const int64_t* rows_a, const int64_t* rows_b,
+                                 int64_t n, void* out, void* stream);
+
+/* glint_mat_push_pairs_axpy, device-resident: the same contributions, stream-ordered on `stream` with no
+ * host synchronisation, after both shards' host-pointer work; both shards are marked for their next sync.
+ * A record with either row outside its partition contributes nothing -- the destination's bits are as if
+ * the record were absent, not as if +0 were added -- and is reported by glint_shard_sync(dst, ...) as the
+ * lowest such record index; the other records are applied. Int/Long sums are exact. Float/Double: every
+ * contribution is bit-exact in every mode, and a destination row that occurs once in the push is
+ * bit-exact; sums of repeated rows keep the push order with GLINT_PUSH_DETERMINISTIC, else runs longer
+ * than 128 records are split and their partial sums added with atomics. A slab that has views is
+ * GLINT_EINVAL for either shard. */
+int glint_mat_push_pairs_axpy_dev(glint_shard_t dst, glint_shard_t src, const int64_t* rows_dst,
+                                  const int64_t* rows_src, const void* coef, int64_t n, int flags, void* stream);
 
 /* glint_vec_push_dev / glint_mat_push_dev behind a device-side gate: the push is enqueued at once,
  * and when it runs it applies NOTHING if the 64-bit device word *gate is nonzero (a route status word,
@@ -587,9 +665,11 @@ enum glint_kernel_id {
   GLINT_K_PULL_ROWS_SUM = 10, /* the grouped row-sum pull (glint_mat_pull_rows_sum*): one launch per call */
   /* the row dot-product pull (glint_mat_pull_rows_dot*): one launch per call. Also every launch of a top-k
    * pull (glint_mat_pull_topk*), which is a dot pull over every row plus a selection: its scores launch
-   * and one launch per selection level, so the sum is that pull's whole device time */
+   * and one launch per selection level, so the sum is that pull's whole device time. Also the one launch
+   * of a row-pair dot pull (glint_mat_pull_pairs_dot*), recorded on its first shard only */
   GLINT_K_PULL_ROWS_DOT = 11,
-  /* the fold of a row axpy push (glint_mat_push_rows_axpy*): one launch per non-empty call */
+  /* the fold of a row axpy push (glint_mat_push_rows_axpy*): one launch per non-empty call. Also the fold
+   * of a row-pair axpy push (glint_mat_push_pairs_axpy*), recorded on its destination shard only */
   GLINT_K_PUSH_ROWS_AXPY = 12,
   GLINT_K_COUNT = 13
 };

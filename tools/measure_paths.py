@@ -4,7 +4,7 @@ device-resident rates from HIP events around each kernel (glint_prof_*), and hos
 the JNI shim sees. One JSON line per measurement on stdout.
 
     python tools/measure_paths.py [--quick] [--sparse] [--rowsum] [--dot] [--axpy [--out FILE]] [--topk [--out FILE]]
-                                  [--adagrad [--out FILE]]
+                                  [--adagrad [--out FILE]] [--pairs [--out FILE]]
 
 --sparse runs only the sparse-row-pull leg (dense getRows against getRowsSparse on a cfg5 shard).
 --rowsum runs only the grouped row-sum leg (getRowsSum against a dense row pull plus a reduction by the
@@ -18,6 +18,9 @@ caller, on a cfg5 shard) and appends its lines to profiles/topk/topk_pull.jsonl 
 --adagrad runs only the Adagrad row push leg (updateRowsAdagrad against coalescing, two row pulls, the step
 and two row pushes by the caller, on cfg5 shards) and appends its lines to profiles/adagrad/adagrad_push.jsonl
 (or FILE).
+--pairs runs only the row-pair leg (getPairsDot / updatePairsAxpy between two shards against row pulls, the
+arithmetic by the caller and a row push, on cfg5-shaped Double and word2vec-shaped Float shards) and appends
+its lines to profiles/pairs/pairs.jsonl (or FILE).
 """
 import ctypes as C
 import json
@@ -558,6 +561,192 @@ def adagrad_leg(rng, out_path):
         sh.destroy()
 
 
+def pairs_leg(rng, out_path):
+    """Two tables per shape -- cfg5's per-GPU 2^17 x 512 Double, and word2vec-shaped 2^17 x 128 Float (short
+    rows under one wave per pair) -- and n = 2^14 and 2^16 pairs, rows_a Zipf(1.0), rows_b uniform. The legs
+    under test use one pair of shards (a1, b1), their baselines another (a2, b2) with the same content, on
+    alternating rounds of one process; the baselines never run the code under test.
+    Dot: glint_mat_pull_pairs_dot* against what a caller does today -- two glint_mat_pull_rows* and
+    (A * B).sum(1) in torch / numpy. Axpy (dst = a, src = b): glint_mat_push_pairs_axpy* against
+    glint_mat_pull_rows* of src, the scale by the caller, glint_mat_push_rows*. Device legs: a HIP event pair
+    around each call; the two kernels alone by their prof ids, and their algorithmic bytes over that time
+    as a fraction of the HBM peak. Host legs: wall time and the bytes over the link. After each n the two
+    legs are compared: they sum in other orders, so they agree to rounding, not bit for bit. One JSON line
+    per (shape, n, op), also appended to out_path."""
+    shard_rows, rounds, hbm_peak_gbs = 1 << 17, 5, 8000.0
+    part = glint_amd.RangePartition(0, 0, shard_rows)
+    all_rows = torch.arange(shard_rows, dtype=torch.int64, device=dev)
+
+    def ev_ms(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b)
+
+    def wall_ms(fn):
+        t0 = time.perf_counter()
+        fn()
+        return (time.perf_counter() - t0) * 1e3
+
+    def stats(ms):
+        return {"mean": float(np.mean(ms)), "min": float(np.min(ms)), "max": float(np.max(ms))}
+
+    def rounds_of(legs):
+        """legs: name -> (timer, fn), run in the order given inside every round; round 0 warms up."""
+        t = {k: [] for k in legs}
+        for rnd in range(rounds + 1):
+            for k, (timer, fn) in legs.items():
+                torch.cuda.synchronize()
+                v = timer(fn)
+                if rnd:
+                    t[k].append(v)
+        return {k: stats(v) for k, v in t.items()}
+
+    Path(out_path).parent.mkdir(parents=True, exist_ok=True)
+    for dtype, cols in (("double", 512), ("float", 128)):
+        a1, b1, a2, b2 = (glint_amd.PartialMatrix(part, cols, dtype, 0) for _ in range(4))
+        tdt, npd, vs = a1.torch_dtype, a1.np_dtype, np.dtype(a1.np_dtype).itemsize
+        tol = 1e-12 if dtype == "double" else 1e-4
+        for x, y in ((a1, a2), (b1, b2)):
+            v = torch.randn((shard_rows, cols), dtype=tdt, device=dev)
+            x.updateRows(all_rows, v)
+            y.updateRows(all_rows, v)
+            del v
+        for n in (1 << 14, 1 << 16):
+            ra = zipf_keys(rng, shard_rows, n, 1.0)
+            rb = rng.integers(0, shard_rows, n).astype(np.int64)
+            coef = (rng.standard_normal(n) * 1e-3).astype(npd)
+            d_ra, d_rb, d_coef = (torch.from_numpy(x).to(dev) for x in (ra, rb, coef))
+            distinct = int(np.unique(ra).size)
+            d_out = torch.empty(n, dtype=tdt, device=dev)
+            h_out = np.empty(n, npd)
+            res = {}
+
+            # ---- dot ----------------------------------------------------------------------------
+            def dev_dot():
+                assert lib.glint_mat_pull_pairs_dot_dev(a1.handle, b1.handle, d_ra.data_ptr(), d_rb.data_ptr(), n,
+                                                        d_out.data_ptr(), stream) == 0
+
+            def dev_dot_base():
+                A = torch.empty((n, cols), dtype=tdt, device=dev)
+                B = torch.empty((n, cols), dtype=tdt, device=dev)
+                assert lib.glint_mat_pull_rows_dev(a2.handle, d_ra.data_ptr(), A.data_ptr(), n, stream) == 0
+                assert lib.glint_mat_pull_rows_dev(b2.handle, d_rb.data_ptr(), B.data_ptr(), n, stream) == 0
+                res["dev_dot"] = (A * B).sum(1)
+
+            def host_dot():
+                assert lib.glint_mat_pull_pairs_dot(a1.handle, b1.handle, ra.ctypes.data, rb.ctypes.data, n,
+                                                    h_out.ctypes.data) == 0
+
+            def host_dot_base():
+                A, B = np.empty((n, cols), npd), np.empty((n, cols), npd)
+                assert lib.glint_mat_pull_rows(a2.handle, ra.ctypes.data, A.ctypes.data, n) == 0
+                assert lib.glint_mat_pull_rows(b2.handle, rb.ctypes.data, B.ctypes.data, n) == 0
+                res["host_dot"] = (A * B).sum(1)
+
+            m = rounds_of({"host_base": (wall_ms, host_dot_base), "host_pairs": (wall_ms, host_dot),
+                           "dev_base": (ev_ms, dev_dot_base), "dev_pairs": (ev_ms, dev_dot)})
+            lib.glint_prof_reset(a1.handle)
+            lib.glint_prof_enable(a1.handle, 1)
+            for _ in range(3):
+                dev_dot()
+            torch.cuda.synchronize()
+            k_ms = kernel_ms(a1.handle, N.GLINT_K_PULL_ROWS_DOT)
+            lib.glint_prof_enable(a1.handle, 0)
+            for sh in (a1, b1, a2, b2):
+                sh.sync(stream)
+            mag = (a2.getRows(d_ra).abs() * b2.getRows(d_rb).abs()).sum(1).clamp_min(1e-300)  # per pair: sum |a b|
+            d_dev = ((d_out - res["dev_dot"]).abs() / mag).max().item()
+            d_host = (np.abs(h_out - res["host_dot"]) / mag.cpu().numpy()).max()
+            assert d_dev < tol and d_host < tol, (d_dev, d_host)
+            k_bytes = 2 * n * cols * vs + 2 * n * 8 + n * vs
+            line = dict(
+                op="mat_pull_pairs_dot", dtype=dtype, pattern="rows_a zipf1.0, rows_b uniform", shape=[shard_rows, cols],
+                pairs=n, rounds=rounds,
+                host_pairs_ms=m["host_pairs"], host_baseline_ms=m["host_base"],
+                host_speedup=m["host_base"]["mean"] / m["host_pairs"]["mean"],
+                host_pairs_bytes_over_link=2 * n * 8 + n * vs, host_baseline_bytes_over_link=2 * n * 8 + 2 * n * cols * vs,
+                dev_pairs_ms=m["dev_pairs"], dev_baseline_ms=m["dev_base"],
+                dev_speedup=m["dev_base"]["mean"] / m["dev_pairs"]["mean"],
+                kernel_ms=k_ms, kernel_bytes=k_bytes, kernel_GBps=k_bytes / (k_ms * 1e-3) / 1e9,
+                kernel_fraction_of_hbm_peak=k_bytes / (k_ms * 1e-3) / 1e9 / hbm_peak_gbs, hbm_peak_GBps=hbm_peak_gbs,
+                max_difference_over_sum_of_magnitudes=max(d_dev, float(d_host)),
+                note="baseline = two glint_mat_pull_rows* and (A * B).sum(1) by the caller (torch on the device, "
+                     "numpy on the host). host_*: C calls on pageable numpy arrays, synchronous, wall ms. dev_*: "
+                     "one HIP event pair per call. Legs alternate inside each of `rounds` rounds after one "
+                     "warm-up round. kernel_ms: the one launch alone (glint_prof, GLINT_K_PULL_ROWS_DOT on a); "
+                     "kernel_bytes = 2 * pairs * cols * sizeof V plus ids and answers")
+            emit(**line)
+            with open(out_path, "a") as f:
+                f.write(json.dumps(line) + "\n")
+            res.clear()
+
+            # ---- axpy (dst = a, src = b) -----------------------------------------------------------
+            def dev_axpy():
+                assert lib.glint_mat_push_pairs_axpy_dev(a1.handle, b1.handle, d_ra.data_ptr(), d_rb.data_ptr(),
+                                                         d_coef.data_ptr(), n, 0, stream) == 0
+
+            def dev_axpy_base():
+                S = torch.empty((n, cols), dtype=tdt, device=dev)
+                assert lib.glint_mat_pull_rows_dev(b2.handle, d_rb.data_ptr(), S.data_ptr(), n, stream) == 0
+                T = d_coef[:, None] * S
+                assert lib.glint_mat_push_rows_dev(a2.handle, d_ra.data_ptr(), T.data_ptr(), n, 0, stream) == 0
+
+            def host_axpy():
+                assert lib.glint_mat_push_pairs_axpy(a1.handle, b1.handle, ra.ctypes.data, rb.ctypes.data,
+                                                     coef.ctypes.data, n, 0) == 0
+
+            def host_axpy_base():
+                S = np.empty((n, cols), npd)
+                assert lib.glint_mat_pull_rows(b2.handle, rb.ctypes.data, S.ctypes.data, n) == 0
+                T = coef[:, None] * S
+                assert lib.glint_mat_push_rows(a2.handle, ra.ctypes.data, T.ctypes.data, n, 0) == 0
+
+            m = rounds_of({"host_base": (wall_ms, host_axpy_base), "host_pairs": (wall_ms, host_axpy),
+                           "dev_base": (ev_ms, dev_axpy_base), "dev_pairs": (ev_ms, dev_axpy)})
+            lib.glint_prof_reset(a1.handle)
+            lib.glint_prof_enable(a1.handle, 1)
+            for _ in range(3):  # (both legs: the two destinations stay comparable)
+                dev_axpy()
+                dev_axpy_base()
+            torch.cuda.synchronize()
+            k_ms = kernel_ms(a1.handle, N.GLINT_K_PUSH_ROWS_AXPY)
+            lib.glint_prof_enable(a1.handle, 0)
+            for sh in (a1, b1, a2, b2):
+                sh.sync(stream)
+            g1, g2 = a1.getRows(all_rows), a2.getRows(all_rows)
+            diff = ((g1 - g2).abs() / g2.abs().clamp_min(1.0)).max().item()
+            del g1, g2
+            assert diff < tol * 100, diff  # sums of up to thousands of terms per hot row, in other orders
+            k_bytes = (n + 2 * distinct) * cols * vs + n * (4 + 8 + vs)
+            line = dict(
+                op="mat_push_pairs_axpy", dtype=dtype, pattern="rows_dst zipf1.0, rows_src uniform",
+                shape=[shard_rows, cols], pairs=n, distinct_dst_rows=distinct, rounds=rounds,
+                host_pairs_ms=m["host_pairs"], host_baseline_ms=m["host_base"],
+                host_speedup=m["host_base"]["mean"] / m["host_pairs"]["mean"],
+                host_pairs_bytes_over_link=2 * n * 8 + n * vs,
+                host_baseline_bytes_over_link=2 * n * 8 + 2 * n * cols * vs,
+                dev_pairs_ms=m["dev_pairs"], dev_baseline_ms=m["dev_base"],
+                dev_speedup=m["dev_base"]["mean"] / m["dev_pairs"]["mean"],
+                fold_kernel_ms=k_ms, fold_bytes=k_bytes, fold_GBps=k_bytes / (k_ms * 1e-3) / 1e9,
+                fold_fraction_of_hbm_peak=k_bytes / (k_ms * 1e-3) / 1e9 / hbm_peak_gbs, hbm_peak_GBps=hbm_peak_gbs,
+                max_relative_difference=diff,
+                note="baseline = glint_mat_pull_rows* of src, coef[:, None] * rows by the caller (torch on the device, "
+                     "numpy on the host), glint_mat_push_rows*. host_*: C calls on pageable numpy arrays, synchronous, "
+                     "wall ms. dev_*: one HIP event pair per call (front end and fold), default order flags. Legs "
+                     "alternate inside each of `rounds` rounds after one warm-up round. fold_kernel_ms: the fold "
+                     "alone (glint_prof, GLINT_K_PUSH_ROWS_AXPY on dst); fold_bytes = (pairs + 2 * "
+                     "distinct_dst_rows) * cols * sizeof V plus ids and coefficients")
+            emit(**line)
+            with open(out_path, "a") as f:
+                f.write(json.dumps(line) + "\n")
+        for sh in (a1, b1, a2, b2):
+            sh.destroy()
+        torch.cuda.empty_cache()
+
+
 def topk_leg(rng, out_path):
     """cfg5 per GPU: a 2^17 x 512 Double shard, the k = 16 best rows against q = 1, 8 and 64 query vectors.
     Host: glint_mat_pull_topk against glint_mat_pull_rows_dot over arange(size) + np.argpartition, wall time;
@@ -706,6 +895,11 @@ def main():
         out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
             str(Path(__file__).resolve().parent.parent / "profiles" / "adagrad" / "adagrad_push.jsonl")
         adagrad_leg(np.random.default_rng(42), out)
+        return
+    if "--pairs" in sys.argv:
+        out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
+            str(Path(__file__).resolve().parent.parent / "profiles" / "pairs" / "pairs.jsonl")
+        pairs_leg(np.random.default_rng(42), out)
         return
     if "--axpy" in sys.argv:
         out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
