@@ -45,6 +45,10 @@ SIGNATURES = {
     "glint_vec_push_dev_shards": (_I, [_P, _I, _P, _P, _I64, _P, _P]),
     "glint_shard_destroy": (_I, [_P]),
     "glint_shard_zero": (_I, [_P]),
+    "glint_shard_fill": (_I, [_P, _P, _I64, _P]),
+    "glint_shard_fill_dev": (_I, [_P, _P, _I64, _P, _P]),
+    "glint_shard_init_uniform": (_I, [_P, _P, _I64, C.c_uint64, C.c_double, C.c_double]),
+    "glint_shard_init_uniform_dev": (_I, [_P, _P, _I64, C.c_uint64, C.c_double, C.c_double, _P]),
     "glint_shard_info": (_I, [_P, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I), C.POINTER(_I)]),
     "glint_vec_push": (_I, [_P, _P, _P, _I64, _I]),
     "glint_vec_pull": (_I, [_P, _P, _P, _I64]),

@@ -26,9 +26,11 @@ CSRC = PKG / "csrc"
 HIP_SOURCES = [CSRC / "glint_gpu.hip", CSRC / "glint_sort.hip", CSRC / "glint_route.hip", CSRC / "glint_ordered.hip", CSRC / "glint_bin.hip",
                CSRC / "glint_exchange.hip", CSRC / "glint_rows.hip", CSRC / "glint_sparse.hip",
                CSRC / "glint_rowsum.hip", CSRC / "glint_rowdot.hip", CSRC / "glint_rowaxpy.hip",
-               CSRC / "glint_topk.hip", CSRC / "glint_rowadagrad.hip", CSRC / "glint_pairs.hip"]
-# plain C++: the push planners and the top-k pull's level plan
-PLAN_HEADERS = [CSRC / "glint_push_plan.h", CSRC / "glint_bin_plan.h", CSRC / "glint_topk_plan.h"]
+               CSRC / "glint_topk.hip", CSRC / "glint_rowadagrad.hip", CSRC / "glint_pairs.hip",
+               CSRC / "glint_init.hip"]
+# plain C++: the push planners, the top-k pull's level plan and the uniform init's value contract
+PLAN_HEADERS = [CSRC / "glint_push_plan.h", CSRC / "glint_bin_plan.h", CSRC / "glint_topk_plan.h",
+                CSRC / "glint_init_plan.h"]
 HIP_HEADERS = [CSRC / "glint_kernels.h", CSRC / "glint_device.h", CSRC / "glint_host.h", CSRC / "glint_dot.h",
                CSRC / "glint_axpy.h",
                ROOT / "include" / "glint_gpu.h", *PLAN_HEADERS]
@@ -205,6 +207,29 @@ def build_topk_probe(force: bool = False, verbose: bool = False) -> Path:
     return TOPK_PROBE
 
 
+INIT_PROBE_SRC = ROOT / "tests" / "c" / "init_probe.cpp"
+INIT_PROBE = ROOT / "tests" / "c" / "build" / "libinit_probe.so"
+
+
+def build_init_probe(force: bool = False, verbose: bool = False) -> Path:
+    """The uniform init's value contract (glint_init_plan.h: Philox4x32-10 and the bits-to-value mapping)
+    as a host-only library: what tests/test_init_cpu.py loads. Compiled by g++ alone, with contraction
+    off as the contract asks (the header's clang pragma is unknown to g++)."""
+    deps = [INIT_PROBE_SRC, CSRC / "glint_init_plan.h"]
+    if not force and not _stale(INIT_PROBE, deps):
+        return INIT_PROBE
+    INIT_PROBE.parent.mkdir(parents=True, exist_ok=True)
+    tmp = INIT_PROBE.with_suffix(".so.tmp")
+    cxx = shutil.which("g++") or "c++"
+    cmd = [cxx, "-O2", "-std=c++17", "-Wall", "-Werror", "-Wno-unknown-pragmas", "-ffp-contract=off", "-fPIC",
+           "-shared", "-o", str(tmp), str(INIT_PROBE_SRC)]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True, cwd=str(ROOT))
+    os.replace(tmp, INIT_PROBE)
+    return INIT_PROBE
+
+
 def build_all(force: bool = False, verbose: bool = False) -> None:
     build_gpu_lib(force=force, verbose=verbose)
     build_oracle(force=force, verbose=verbose)
@@ -213,6 +238,7 @@ def build_all(force: bool = False, verbose: bool = False) -> None:
     build_plan_probe(force=force, verbose=verbose)
     build_sweep_probe(force=force, verbose=verbose)
     build_topk_probe(force=force, verbose=verbose)
+    build_init_probe(force=force, verbose=verbose)
 
 
 if __name__ == "__main__":

@@ -27,6 +27,8 @@ Mirrors the reference's client factory and asynchronous models, minus the Akka t
   scoring step, rows of this matrix dotted with, or stepped by coefficients times, rows of a second
   matrix on the same devices (PartialMatrix.getPairsDot / updatePairsAxpy); pairs are bucketed by (own
   partition, other partition) and nothing of size ``cols`` leaves the devices.
+* ``fill`` / ``initUniform`` of both models -- extensions: a constant, or a seeded uniform table whose
+  bits do not depend on the layout, written on the shards (``fill`` / ``initUniform`` of the shards).
 
 Out-of-range keys raise ``IndexOutOfBoundsException`` before any shard is touched, as the
 reference's ``partitioner.partition`` does synchronously inside ``mapPartitions``.
@@ -58,7 +60,40 @@ def _same_partitioner(a, b) -> bool:
     return type(a) is type(b) and [repr(p) for p in a.all()] == [repr(p) for p in b.all()]
 
 
-class BigVector:
+def _init_fanout(model, rows, call) -> bool:
+    """What ``fill`` and ``initUniform`` of both models do: ``rows`` None reaches every shard once,
+    ``call(shard, None)``; else the rows (global keys) are validated by the partitioner before any shard is
+    called, and each non-empty partition gets one ``call(shard, its rows)`` in the caller's order."""
+    if rows is None:
+        for sh in model.shards:
+            call(sh, None)
+        return True
+    rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+    order, off = bucket(model.partitioner.partition_indices(rows), len(model.shards))
+    for p, sh in enumerate(model.shards):
+        idx = order[off[p]:off[p + 1]]
+        if idx.size:
+            call(sh, rows[idx])
+    return True
+
+
+class _InitMixin:
+    def fill(self, value, rows=None) -> bool:
+        """Every element of the named rows (vector: keys) = ``value``, written on the shards (an extension;
+        ``PartialVector.fill`` / ``PartialMatrix.fill``): an Adagrad accumulator's initial value. ``rows``
+        None: the whole model, one call per shard. Else global keys, validated before any shard is called
+        and bucketed by partition as ``push``; one call per non-empty partition."""
+        return _init_fanout(self, rows, lambda sh, r: sh.fill(value, rows=r))
+
+    def initUniform(self, seed: int, lo: float, hi: float, rows=None) -> bool:
+        """Seeded uniform init of the named rows in [lo, hi], generated on the shards (an extension;
+        ``initUniform`` of the shards; Float and Double). An element's value depends on (seed, global row,
+        column, lo, hi, dtype) only, so every shard gets the same seed and the model holds the same bits
+        under any partitioner and any number of partitions. ``rows`` as for ``fill``."""
+        return _init_fanout(self, rows, lambda sh, r: sh.initUniform(seed, lo, hi, rows=r))
+
+
+class BigVector(_InitMixin):
     """AsyncBigVector over PartialVector shards (one per partition)."""
 
     def __init__(self, partitioner, shards: Sequence[PartialVector], size: int):
@@ -98,7 +133,7 @@ class BigVector:
         return True
 
 
-class BigMatrix:
+class BigMatrix(_InitMixin):
     """AsyncBigMatrix over PartialMatrix shards."""
 
     def __init__(self, partitioner, shards: Sequence[PartialMatrix], rows: int, cols: int):

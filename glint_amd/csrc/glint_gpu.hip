@@ -788,6 +788,7 @@ __global__ __launch_bounds__(kTPB) void mat_pull_rows_kernel(const i64* rows, i6
 using namespace glint;
 
 #include "glint_host.h"
+#include "glint_init_plan.h"
 
 namespace {
 
@@ -1326,6 +1327,53 @@ inline int push_pairs_args(const glint_shard* dst, const glint_shard* src, const
   return GLINT_OK;
 }
 
+// What a fill or uniform init stores, settled on the host: for a fill `a` holds the value's bytes, for a
+// uniform init `a` and `b` the bits of lo and w in the shard's type (init_uniform_range).
+struct InitSpec {
+  bool uniform;
+  u64 seed, a, b;
+};
+
+// argument checks shared by glint_shard_fill / glint_shard_init_uniform / _dev: a shard, a 31-bit row
+// count, rows present unless n == 0 (rows == NULL with n == 0 names every row)
+inline int init_rows_args(const glint_shard* s, const void* rows, int64_t n) {
+  if (!s || n < 0 || n >= ((i64)1 << 31)) return GLINT_EINVAL;
+  if (!rows && n != 0) return GLINT_EINVAL;
+  return GLINT_OK;
+}
+
+// argument checks of glint_shard_fill / _dev; the value's sizeof V bytes go into spec as they are
+inline int fill_args(const glint_shard* s, const void* rows, int64_t n, const void* value, InitSpec* spec) {
+  if (int rc = init_rows_args(s, rows, n)) return rc;
+  if (!value) return GLINT_EINVAL;
+  *spec = InitSpec{false, 0, 0, 0};
+  std::memcpy(&spec->a, value, s->vsize);
+  return GLINT_OK;
+}
+
+// argument checks of glint_shard_init_uniform / _dev: a Float or Double shard and a range that
+// init_uniform_range accepts
+inline int uniform_args(const glint_shard* s, const void* rows, int64_t n, uint64_t seed, double lo, double hi,
+                        InitSpec* spec) {
+  if (int rc = init_rows_args(s, rows, n)) return rc;
+  *spec = InitSpec{true, seed, 0, 0};
+  if (s->dtype == GLINT_F32) {
+    float l, w;
+    if (!init_uniform_range<float>(lo, hi, &l, &w)) return GLINT_EINVAL;
+    std::memcpy(&spec->a, &l, 4);
+    std::memcpy(&spec->b, &w, 4);
+    return GLINT_OK;
+  }
+  if (s->dtype == GLINT_F64) {
+    double l, w;
+    if (!init_uniform_range<double>(lo, hi, &l, &w)) return GLINT_EINVAL;
+    std::memcpy(&spec->a, &l, 8);
+    std::memcpy(&spec->b, &w, 8);
+    return GLINT_OK;
+  }
+  return GLINT_EINVAL;
+}
+
 // argument checks of glint_mat_pull_rows_sparse / _dev: a matrix shard, 31-bit request count, outputs
 // present unless the call only counts
 inline int pull_sparse_args(const glint_shard* s, const void* rows, int64_t n, const void* row_ptr,
@@ -1425,6 +1473,16 @@ int push_dev_gated(glint_shard* s, bool mat, const int64_t* keys, const int32_t*
   });
 }
 
+// glint_shard_fill_dev / glint_shard_init_uniform_dev: one launch on the caller's stream, ordered and
+// marked as every single-shard device call (dev_call; a slab waits for its views' host-pointer work as
+// in glint_mat_push_rows_dev). An empty list launches nothing.
+int init_dev(glint_shard* s, int args_rc, const int64_t* rows, int64_t n, const InitSpec& sp, void* stream) {
+  if (args_rc == GLINT_OK && rows && n == 0) return GLINT_OK;
+  return dev_call(s, args_rc, stream, [&](hipStream_t st) -> int {
+    return shard_init(s, (const i64*)rows, n, rows != nullptr, sp.uniform, sp.seed, sp.a, sp.b, st);
+  });
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -1434,7 +1492,7 @@ std::atomic<unsigned> g_env_gen{1};
 
 extern "C" {
 
-int glint_version(void) { return 900; }  // 0.9.0: glint_mat_pull_pairs_dot / glint_mat_push_pairs_axpy / _dev
+int glint_version(void) { return 1000; }  // 0.10.0: glint_shard_fill / glint_shard_init_uniform / _dev
 
 int glint_reload_env(void) {
   g_env_gen.fetch_add(1, std::memory_order_acq_rel);
@@ -1898,6 +1956,17 @@ int glint_mat_push_pairs_axpy_dev(glint_shard_t dst, glint_shard_t src, const in
   }
   GLINT_DISPATCH(dst->dtype, push_pairs_axpy, dst, src, (const i64*)rows_dst, (const i64*)rows_src, coef, n, flags,
                  st);
+}
+
+int glint_shard_fill_dev(glint_shard_t s, const int64_t* rows, int64_t n, const void* value, void* stream) {
+  InitSpec sp{};
+  return init_dev(s, fill_args(s, rows, n, value, &sp), rows, n, sp, stream);
+}
+
+int glint_shard_init_uniform_dev(glint_shard_t s, const int64_t* rows, int64_t n, uint64_t seed, double lo, double hi,
+                                 void* stream) {
+  InitSpec sp{};
+  return init_dev(s, uniform_args(s, rows, n, seed, lo, hi, &sp), rows, n, sp, stream);
 }
 
 }  // extern "C"
@@ -3001,9 +3070,46 @@ int host_push_pairs_axpy(glint_shard* dst, glint_shard* src, const int64_t* rd, 
   return finish(dst);
 }
 
+// glint_shard_fill / glint_shard_init_uniform: the shard is entered as by glint_mat_push_rows (the open
+// ring batch flushed, after enqueued messages and the last device-resident call; a slab with views
+// refused), every named row is checked before anything is written, the row list is staged and the one
+// launch runs on the shard's stream; the call ends synchronised. An ordinary write: the error state and
+// the failed list are left alone.
+int host_init(glint_shard* s, const int64_t* rows, int64_t n, const InitSpec& sp) {
+  ShardLock lk(s);
+  DeviceGuard g(s->device);
+  int rc = host_enter(s, HostEntry::OrderFlush);
+  if (rc == GLINT_OK && rows) rc = reject_if_bad(s, rows, nullptr, n);
+  if (rc) return rc;
+  if (rows && n == 0) return GLINT_OK;  // an empty list names nothing
+  Staged st;
+  if (rows) {
+    const void* src[1] = {rows};
+    size_t bytes[1] = {(size_t)n * 8};
+    rc = stage(s, src, bytes, 1, st, 0, nullptr);
+    if (rc) return rc;
+  }
+  HostCall hc(s);  // (every row was checked: nothing is recorded)
+  rc = shard_init(s, (const i64*)st.p[0], n, rows != nullptr, sp.uniform, sp.seed, sp.a, sp.b, s->stream);
+  if (rc) return launch_failed(s, rc);
+  return finish(s);
+}
+
 }  // namespace
 
 extern "C" {
+
+int glint_shard_fill(glint_shard_t s, const int64_t* rows, int64_t n, const void* value) {
+  InitSpec sp{};
+  if (int rc = fill_args(s, rows, n, value, &sp)) return rc;
+  return host_init(s, rows, n, sp);
+}
+
+int glint_shard_init_uniform(glint_shard_t s, const int64_t* rows, int64_t n, uint64_t seed, double lo, double hi) {
+  InitSpec sp{};
+  if (int rc = uniform_args(s, rows, n, seed, lo, hi, &sp)) return rc;
+  return host_init(s, rows, n, sp);
+}
 
 int glint_mat_pull_pairs_dot(glint_shard_t a, glint_shard_t b, const int64_t* rows_a, const int64_t* rows_b,
                              int64_t n, void* out) {

@@ -528,6 +528,14 @@ int pull_pairs_dot(glint_shard* a, glint_shard* b, const i64* rows_a, const i64*
 template <typename V>
 int push_pairs_axpy(glint_shard* dst, glint_shard* src, const i64* rows_dst, const i64* rows_src, const void* coef,
                     i64 n, int flags, hipStream_t st);
+// shard fill and uniform init (glint_init.hip), for every dtype: the named rows' elements = the low vsize
+// bytes of `a` (uniform false), or the values include/glint_gpu.h fixes for (seed, global row, column)
+// with lo and w as bits of the shard's type in `a` and `b` (Float / Double only). list false names every
+// row of the partition; else rows[0 .. n) are global keys (device pointer), one outside the partition
+// skipped and recorded in err_of(s). One launch on st, none when nothing is named; no host
+// synchronisation.
+int shard_init(glint_shard* s, const i64* rows, i64 n, bool list, bool uniform, u64 seed, u64 a, u64 b,
+               hipStream_t st);
 // sparse row pull (glint_sparse.hip), instantiated for the same V. sparse_count_scan: row_ptr[0..n]
 // (device) = exclusive prefix of the requested rows' non-zero counts; rows outside the partition
 // count 0 and are recorded in err_of(s); the scan's scratch is s->d_det. sparse_emit: the entries

@@ -180,6 +180,51 @@ class _Shard:
         """What an Akka restart produces: a freshly constructed, zeroed partial model."""
         check(self.lib.glint_shard_zero(self.handle), self.handle)
 
+    def _init_call(self, name: str, rows, sync: bool, args: tuple) -> bool:
+        """fill / initUniform: ``rows`` None names every row (element) of the partition, a numpy array of
+        global keys takes the host call, a torch device tensor the device call on the current stream."""
+        if rows is None or not _is_torch_cuda(rows):
+            if rows is None:
+                check(getattr(self.lib, name)(self.handle, None, 0, *args), self.handle)
+                return True
+            r = _host(rows, np.int64).reshape(-1)
+            # (an empty array names nothing, but its data pointer may be NULL, which would name every row)
+            p = r if r.size else np.zeros(1, np.int64)
+            check(getattr(self.lib, name)(self.handle, p.ctypes.data, r.size, *args), self.handle)
+            return True
+        n = rows.numel()
+        self._check_dev(n, rows)
+        if n == 0:  # names nothing (its data pointer may be NULL, which would name every row)
+            return True
+        st = self._stream_of(rows)
+        check(getattr(self.lib, name + "_dev")(self.handle, rows.data_ptr(), n, *args, st), self.handle)
+        if sync:
+            self.sync(st)
+        return True
+
+    def fill(self, value, rows=None, sync: bool = True) -> bool:
+        """Every element of the named rows = ``value`` (an extension; glint_shard_fill*), written on the
+        device: the initial value of an Adagrad accumulator. ``value`` is converted to the shard's type once
+        and stored as those bytes: -0.0 and a NaN's payload and sign are kept. ``rows`` None: the whole
+        partition. A numpy array of global keys (any order, repeats allowed): every row is checked first,
+        one outside the partition raises with the lowest such index and nothing is written. A torch device
+        tensor: one stream-ordered launch on the current stream; such a row is skipped and raised by
+        ``sync`` (``sync=True``, or a later ``sync()``). Unnamed rows and the row padding are untouched."""
+        v = np.asarray(value).astype(self.np_dtype).reshape(1)  # (a value of the shard's type keeps its bits)
+        return self._init_call("glint_shard_fill", rows, sync, (v.ctypes.data,))
+
+    def initUniform(self, seed: int, lo: float, hi: float, rows=None, sync: bool = True) -> bool:
+        """Seeded uniform init of the named rows (an extension; glint_shard_init_uniform*; Float and
+        Double), generated on the device: element (global row g, column c) is ``lo + u * (hi - lo)`` with
+        ``u`` in [0, 1) taken from Philox4x32-10 under counter (g, c's block) and key ``seed`` -- a function
+        of (seed, g, c, lo, hi, dtype) only, whatever the partition or device (include/glint_gpu.h fixes
+        every bit; the result lies in [lo, hi]). ``seed`` is a 64-bit unsigned integer. ``rows`` and
+        ``sync`` as for ``fill``; naming a row again writes the same bits."""
+        seed = int(seed)
+        if not 0 <= seed < 1 << 64:
+            raise ValueError("seed: expected an unsigned 64-bit integer")
+        return self._init_call("glint_shard_init_uniform", rows, sync, (seed, float(lo), float(hi)))
+
     def data_ptr(self) -> int:
         p = C.c_void_p()
         check(self.lib.glint_shard_data(self.handle, C.byref(p)), self.handle)

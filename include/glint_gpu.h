@@ -128,6 +128,46 @@ int glint_shard_destroy(glint_shard_t shard);
 /* Zeroes the shard: what an Akka restart of the partial-model actor produces. */
 int glint_shard_zero(glint_shard_t shard);
 
+/* Shard fill and uniform init (extensions: the reference constructs zeroed models only): what an
+ * embedding table starts from, written on the device, so that nothing of size rows x cols crosses the
+ * link. glint_shard_fill gives every named element one constant (an Adagrad accumulator's initial
+ * value); glint_shard_init_uniform gives it a value drawn from a seeded counter-based generator.
+ *   rows   NULL with n == 0: every row (vector: every element) of the partition. Else n global keys in
+ *          any order, repeats allowed (a row named twice is written twice with the same bits); a non-NULL
+ *          rows with n == 0 names nothing.
+ * Element (g, c): g is the global key (vector) or global row (matrix) of the element, c its column (0 for
+ * a vector). Local row l has g = start + l in a range partition and g = index + l * numberOfPartitions in
+ * a cyclic one; the value is that of the row the element IS, however the key that named it was mapped.
+ * Fill: the element receives the sizeof V bytes at `value` as they are: a -0.0 and a NaN's payload and
+ * sign are stored unchanged. All four types.
+ * Uniform (Float and Double shards only): with L = 4 values per block for Float and 2 for Double, block
+ * b = c / L and position j = c % L,
+ *   (o0, o1, o2, o3) = Philox4x32-10(counter (lo32(g), hi32(g), b, 0), key (lo32(seed), hi32(seed)))
+ * with the standard multipliers 0xD2511F53, 0xCD9E8D57 and Weyl constants 0x9E3779B9, 0xBB67AE85;
+ *   Float:  u = (o[j] >> 8) * 2^-24
+ *   Double: u = ((o[2j] | (uint64)o[2j+1] << 32) >> 11) * 2^-53
+ * (both conversions exact). lo and hi are rounded once, on the host, to V; w = hi - lo is computed once,
+ * on the host, in V; the element is lo + (u * w) in V, the product rounded before the add (no fused
+ * multiply-add). It lies in [lo, hi]: u < 1, but rounding may give hi itself. The value is a function of
+ * (seed, g, c, lo, hi, dtype) only -- not of the partitioner, the number of partitions, the device, the
+ * grid or whether the row was named by a list -- so a model initialised under any layout holds the same
+ * bits, and initialising a row again is idempotent. A vector is the cols = 1 case: one block per element.
+ * Neither call reads or writes a row that is not named, nor the pitch padding of any row.
+ * Host calls: the shard is entered as by glint_shard_zero and the other host-pointer calls: the open ring
+ * batch is flushed, the call is ordered after the messages enqueued before it and after the last
+ * device-resident call, and a slab with views is refused. Every row is checked first: for the lowest i
+ * with rows[i] outside the partition the call returns GLINT_EOUTOFRANGE (i in glint_shard_last_error)
+ * with nothing written. Then rows is staged, one kernel runs on the shard's stream and the call ends
+ * synchronised. They are ordinary writes, not a restart: the error state and the failed tickets are left
+ * as they are.
+ * GLINT_EINVAL: a NULL shard; a NULL value; rows == NULL with n != 0; n < 0; n >= 2^31; a uniform init of
+ * an Int or Long shard; lo or hi NaN or infinite after rounding to V; lo > hi; a w that is not finite.
+ * lo == hi is allowed (every element is lo). Kernel timing: the one launch counts under
+ * GLINT_K_PUSH_ROWS; a call that names nothing launches nothing. */
+int glint_shard_fill(glint_shard_t shard, const int64_t* rows, int64_t n, const void* value);
+int glint_shard_init_uniform(glint_shard_t shard, const int64_t* rows, int64_t n, uint64_t seed, double lo,
+                             double hi);
+
 /* Shape: size = Partition.size (elements for a vector, rows for a matrix), cols (0 = vector),
  * dtype, device. Any out-pointer may be NULL. */
 int glint_shard_info(glint_shard_t shard, int32_t* size, int32_t* cols, int* dtype, int* device);
@@ -408,6 +448,16 @@ int glint_mat_pull_rows_dev(glint_shard_t shard, const int64_t* rows, void* out,
 int glint_mat_push_rows_dev(glint_shard_t shard, const int64_t* rows, const void* vals, int64_t n, int flags,
                             void* stream);
 
+/* glint_shard_fill / glint_shard_init_uniform, device-resident: the same bits, one launch,
+ * stream-ordered on `stream` with no host synchronisation, after the shard's host-pointer work; the
+ * shard is marked for its next sync. rows (device memory) as above; a row outside the partition is
+ * skipped -- nothing is written for it -- and reported by glint_shard_sync as the lowest such index; the
+ * other rows are written. A slab is ordered with its views as in glint_mat_push_rows_dev. `value` is host
+ * memory, read before the call returns. */
+int glint_shard_fill_dev(glint_shard_t shard, const int64_t* rows, int64_t n, const void* value, void* stream);
+int glint_shard_init_uniform_dev(glint_shard_t shard, const int64_t* rows, int64_t n, uint64_t seed, double lo,
+                                 double hi, void* stream);
+
 /* glint_mat_pull_rows_sparse, device-resident: the same triple and capacity rule, stream-ordered on
  * `stream` with no host synchronisation, so the caller reads row_ptr[n] itself (and compares it with
  * cap) after waiting on the stream. A row outside the partition has 0 entries and is reported by
@@ -657,7 +707,8 @@ enum glint_kernel_id {
   GLINT_K_PUSH_BINNED = 6,  /* the binned unordered-push pipeline (count, partition, apply) */
   GLINT_K_PUSH_ORDERED = 7, /* the order-preserving push of message-sized pushes (one launch) */
   /* the per-destination fold of a whole-row push (glint_mat_push_rows*), and the one fold launch of a
-   * non-empty Adagrad row push (glint_mat_push_rows_adagrad*), recorded on its weights shard only */
+   * non-empty Adagrad row push (glint_mat_push_rows_adagrad*), recorded on its weights shard only. Also
+   * the one launch of a shard fill or uniform init (glint_shard_fill*, glint_shard_init_uniform*) */
   GLINT_K_PUSH_ROWS = 8,
   /* the sparse row pull (glint_mat_pull_rows_sparse*): its emit kernel, and under the same id its
    * count kernel and the launches of its scan, so the sum is the pull's whole device time */

@@ -4,7 +4,7 @@ device-resident rates from HIP events around each kernel (glint_prof_*), and hos
 the JNI shim sees. One JSON line per measurement on stdout.
 
     python tools/measure_paths.py [--quick] [--sparse] [--rowsum] [--dot] [--axpy [--out FILE]] [--topk [--out FILE]]
-                                  [--adagrad [--out FILE]] [--pairs [--out FILE]]
+                                  [--adagrad [--out FILE]] [--pairs [--out FILE]] [--init [--out FILE]]
 
 --sparse runs only the sparse-row-pull leg (dense getRows against getRowsSparse on a cfg5 shard).
 --rowsum runs only the grouped row-sum leg (getRowsSum against a dense row pull plus a reduction by the
@@ -21,6 +21,10 @@ and two row pushes by the caller, on cfg5 shards) and appends its lines to profi
 --pairs runs only the row-pair leg (getPairsDot / updatePairsAxpy between two shards against row pulls, the
 arithmetic by the caller and a row push, on cfg5-shaped Double and word2vec-shaped Float shards) and appends
 its lines to profiles/pairs/pairs.jsonl (or FILE).
+--init runs only the shard fill / uniform init leg (fill and initUniform of a whole shard and of a row list
+against glint_shard_zero's memset, and against generating the table by the caller plus a row push, on a
+cfg5-shaped Double and a word2vec-shaped Float shard) and appends its lines to profiles/init/init.jsonl (or
+FILE).
 """
 import ctypes as C
 import json
@@ -747,6 +751,128 @@ def pairs_leg(rng, out_path):
         torch.cuda.empty_cache()
 
 
+def init_leg(rng, out_path):
+    """Shard fill and uniform init on cfg5's per-GPU shard (2^17 x 512 Double) and a word2vec-shaped one
+    (2^17 x 128 Float): the whole shard, and a list of 2^14 distinct rows in random order. The calls under
+    test run on one shard (s1), the floor and the baselines on another (s2), all inside each of 5 rounds of
+    one process after one warm-up round; the baselines never run the code under test.
+    Floor: glint_shard_zero of the same shard (a memset and one synchronisation), wall time, next to the
+    wall time of the whole-shard host calls, which end with the same synchronisation. Kernel: the one launch
+    alone (GLINT_K_PUSH_ROWS, glint_prof_read) and the bytes it stores over that time. Device baseline, what
+    a caller does today: torch.rand into an n x cols buffer, scale, glint_mat_push_rows_dev into the zeroed
+    shard (HIP events around the three; the zeroing is not timed). Host baseline: numpy random, scale,
+    glint_mat_push_rows (wall). link_bytes is what each sends over the host link. One JSON line per (shape,
+    rows named), also appended to out_path."""
+    shard_rows, n_list, rounds, hbm_peak_gbs = 1 << 17, 1 << 14, 5, 8000.0
+    part = glint_amd.RangePartition(0, 0, shard_rows)
+    lo, hi = -0.5 / 100, 0.5 / 100
+
+    def ev_ms(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b)
+
+    def wall_ms(fn):
+        t0 = time.perf_counter()
+        fn()
+        return (time.perf_counter() - t0) * 1e3
+
+    def stats(ms):
+        return {"mean": float(np.mean(ms)), "min": float(np.min(ms)), "max": float(np.max(ms))}
+
+    Path(out_path).parent.mkdir(parents=True, exist_ok=True)
+    for dtype, cols in (("double", 512), ("float", 128)):
+        s1, s2 = (glint_amd.PartialMatrix(part, cols, dtype, 0) for _ in range(2))
+        tdt, npd, vs = s1.torch_dtype, s1.np_dtype, np.dtype(s1.np_dtype).itemsize
+        lib.glint_prof_enable(s1.handle, 1)
+        some = rng.permutation(shard_rows)[:n_list].astype(np.int64)
+        for label, rows in (("whole", None), ("list", some)):
+            n = shard_rows if rows is None else rows.size
+            d_rows = torch.arange(shard_rows, dtype=torch.int64, device=dev) if rows is None else \
+                torch.from_numpy(rows).to(dev)
+            h_rows = np.arange(shard_rows, dtype=np.int64) if rows is None else rows
+            stored = n * cols * vs
+            one = np.full(1, 0.1, npd)
+            seed = [0]
+
+            def uniform_host():
+                seed[0] += 1
+                s1.initUniform(seed[0], lo, hi, rows=rows)
+
+            def fill_host():
+                s1.fill(one[0], rows=rows)
+
+            def uniform_dev():
+                seed[0] += 1
+                assert lib.glint_shard_init_uniform_dev(s1.handle, None if rows is None else d_rows.data_ptr(),
+                                                        0 if rows is None else n, seed[0], lo, hi, stream) == 0
+
+            def zero_floor():
+                s2.zero()
+
+            def dev_base():
+                v = torch.rand((n, cols), dtype=tdt, device=dev)
+                v = v * (hi - lo) + lo
+                assert lib.glint_mat_push_rows_dev(s2.handle, d_rows.data_ptr(), v.data_ptr(), n, 0, stream) == 0
+
+            def host_base():
+                v = (np.random.default_rng(seed[0]).random((n, cols), dtype=npd) * npd(hi - lo) + npd(lo))
+                s2.updateRows(h_rows, v)
+
+            t = {k: [] for k in ("zero", "uniform_host", "fill_host", "uniform_dev", "dev_base", "host_base",
+                                 "uniform_kernel", "fill_kernel")}
+            for rnd in range(rounds + 1):
+                def rec(k, v):
+                    if rnd:
+                        t[k].append(v)
+                torch.cuda.synchronize()
+                rec("zero", wall_ms(zero_floor))
+                lib.glint_prof_reset(s1.handle)
+                rec("uniform_host", wall_ms(uniform_host))
+                rec("uniform_kernel", kernel_total_ms(s1.handle, N.GLINT_K_PUSH_ROWS)[0])
+                rec("zero", wall_ms(zero_floor))
+                lib.glint_prof_reset(s1.handle)
+                rec("fill_host", wall_ms(fill_host))
+                rec("fill_kernel", kernel_total_ms(s1.handle, N.GLINT_K_PUSH_ROWS)[0])
+                torch.cuda.synchronize()
+                rec("uniform_dev", ev_ms(uniform_dev))
+                s1.sync(stream)
+                s2.zero()
+                torch.cuda.synchronize()
+                rec("dev_base", ev_ms(dev_base))
+                s2.sync(stream)
+                s2.zero()
+                rec("host_base", wall_ms(host_base))
+            r = {k: stats(v) for k, v in t.items()}
+            uk, fk = r["uniform_kernel"]["mean"], r["fill_kernel"]["mean"]
+            line = dict(
+                op="shard_init", dtype=dtype, shard_rows=shard_rows, cols=cols, rows_named=label, n=n,
+                rounds=rounds, stored_bytes=stored,
+                zero_wall_ms=r["zero"], uniform_host_wall_ms=r["uniform_host"], fill_host_wall_ms=r["fill_host"],
+                uniform_dev_call_ms=r["uniform_dev"], uniform_kernel_ms=r["uniform_kernel"],
+                fill_kernel_ms=r["fill_kernel"],
+                uniform_kernel_GBps=stored / (uk * 1e-3) / 1e9, fill_kernel_GBps=stored / (fk * 1e-3) / 1e9,
+                uniform_kernel_fraction_of_hbm_peak=stored / (uk * 1e-3) / 1e9 / hbm_peak_gbs,
+                uniform_host_over_zero=r["uniform_host"]["mean"] / r["zero"]["mean"],
+                fill_host_over_zero=r["fill_host"]["mean"] / r["zero"]["mean"],
+                uniform_kernel_over_zero=uk / r["zero"]["mean"],
+                device_baseline_ms=r["dev_base"], host_baseline_wall_ms=r["host_base"],
+                speedup_device=r["dev_base"]["mean"] / r["uniform_dev"]["mean"],
+                speedup_host=r["host_base"]["mean"] / r["uniform_host"]["mean"],
+                link_bytes={"uniform": 0 if rows is None else n * 8, "device_baseline": 0,
+                            "host_baseline": n * 8 + stored},
+                note="zero_wall_ms is glint_shard_zero of the whole shard in both rows: the floor of the whole-shard "
+                     "rows only; the device baseline also writes and reads an n x cols buffer in HBM")
+            emit(**line)
+            with open(out_path, "a") as f:
+                f.write(json.dumps(line) + "\n")
+        s1.destroy()
+        s2.destroy()
+
+
 def topk_leg(rng, out_path):
     """cfg5 per GPU: a 2^17 x 512 Double shard, the k = 16 best rows against q = 1, 8 and 64 query vectors.
     Host: glint_mat_pull_topk against glint_mat_pull_rows_dot over arange(size) + np.argpartition, wall time;
@@ -890,6 +1016,11 @@ def main():
         out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
             str(Path(__file__).resolve().parent.parent / "profiles" / "topk" / "topk_pull.jsonl")
         topk_leg(np.random.default_rng(42), out)
+        return
+    if "--init" in sys.argv:
+        out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
+            str(Path(__file__).resolve().parent.parent / "profiles" / "init" / "init.jsonl")
+        init_leg(np.random.default_rng(42), out)
         return
     if "--adagrad" in sys.argv:
         out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
