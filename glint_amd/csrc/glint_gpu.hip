@@ -1210,11 +1210,71 @@ uint8_t wire_response_type(int dtype) {
   }
 }
 
-// defined with the ring below: device-resident calls are ordered after the ring's entries
-int dev_order_after_host(glint_shard* s, hipStream_t st);
-void* host_dev_ptr(const void* p, size_t bytes, size_t align, HostHold* hold = nullptr);  // glint_host_alloc buffers (below)
+// defined with the ring below, after the device-resident entry points that are ordered after its entries
+// (the ring's kernels are instantiated behind theirs)
 int ring_flush_locked(glint_shard* s);
 int ring_retire_through(glint_shard* s, u64 t);
+
+// ---- caller buffers the kernels can write (glint_host_alloc) -----------------------------------
+// Pinned, device-mapped host memory handed to a server for its response images: a coalesced pull
+// whose destination lies in one is answered by the kernel straight into it.
+struct HostRange {
+  char* h;
+  size_t n;
+  char* d;
+  std::shared_ptr<std::atomic<long>> pending;  // kernel writes enqueued into it and not yet retired
+};
+std::mutex g_host_mu;
+std::vector<HostRange> g_host;  // sorted by h
+
+// p's device address if [p, p + bytes) lies in one glint_host_alloc buffer and p is aligned to
+// `align`, else nullptr; with `hold`, the buffer is held (glint_host_free refuses it) until *hold resets
+void* host_dev_ptr(const void* p, size_t bytes, size_t align, HostHold* hold = nullptr) {
+  if (!p || (uintptr_t)p % align) return nullptr;
+  std::lock_guard<std::mutex> lk(g_host_mu);
+  if (g_host.empty()) return nullptr;
+  const char* c = (const char*)p;
+  auto it = std::upper_bound(g_host.begin(), g_host.end(), c,
+                             [](const char* x, const HostRange& r) { return x < r.h; });
+  if (it == g_host.begin()) return nullptr;
+  --it;
+  if (c + bytes > it->h + it->n) return nullptr;
+  if (hold) *hold = HostHold(it->pending);
+  return it->d + (c - it->h);
+}
+
+// Stream st waits for what the shard's own stream holds now, through the shard's host_ev (created on
+// first use).
+int wait_for_host_stream(glint_shard* s, hipStream_t st) {
+  if (!s->host_ev && hipEventCreateWithFlags(&s->host_ev, hipEventDisableTiming) != hipSuccess) {
+    (void)hipGetLastError();
+    s->host_ev = nullptr;
+    return GLINT_EDEVICE;
+  }
+  HIPCHK(hipEventRecord(s->host_ev, s->stream));
+  HIPCHK(hipStreamWaitEvent(st, s->host_ev, 0));
+  return GLINT_OK;
+}
+
+// A device-resident call runs on the caller's stream: it first waits for the ring entries enqueued
+// on the shard's stream (they share the data array and the error state).
+int dev_order_after_host(glint_shard* s, hipStream_t st) {
+  // a slab's call reads or writes its views' elements: it waits for their host-pointer work, and
+  // their later host-pointer calls wait for it (lock order: slab, then view)
+  for (glint_shard* v : s->views) {
+    ShardLock lv(v);
+    if (int rc = dev_order_after_host(v, st)) return rc;
+    v->last_dev_stream = st;
+    v->dev_dirty = true;
+  }
+  int rc = ring_flush_locked(s);
+  if (rc) return rc;
+  if (!s->host_pending) return GLINT_OK;
+  rc = wait_for_host_stream(s, st);
+  if (rc) return rc;
+  s->host_pending = false;
+  return GLINT_OK;
+}
 
 // argument checks of glint_mat_push_rows / _dev: a matrix shard, sane sizes, only the two order flags
 // (no validating or gated row push), 32-bit record indices for the sort
@@ -1255,42 +1315,19 @@ inline int push_adagrad_args(const glint_shard* w, const glint_shard* h, const v
   return GLINT_OK;
 }
 
-// Both shards' locks for a call, taken in lock_order (glint_vec_push_dev_shards' rule).
+// The locks of a call on shards a and b, which may be one: the one lock once, else both in lock_order
+// (glint_vec_push_dev_shards' rule). The lock taken first is a ShardLock, so a call on one shard is
+// accounted as under a ShardLock.
 struct PairLock {
-  glint_shard* o[2];
-  PairLock(glint_shard* a, glint_shard* b) {
-    std::vector<glint_shard*> v{a, b};
-    lock_order(v);
-    o[0] = v[0];
-    o[1] = v[1];
-    o[0]->mu.lock();
-    o[1]->mu.lock();
+  ShardLock first;
+  glint_shard* second;  // (nullptr: a == b)
+  PairLock(glint_shard* a, glint_shard* b)
+      : first(a == b || locks_before(a, b) ? a : b), second(a == b ? nullptr : (first.s == a ? b : a)) {
+    if (second) second->mu.lock();
   }
   ~PairLock() {
-    o[1]->mu.unlock();
-    o[0]->mu.unlock();
+    if (second) second->mu.unlock();
   }
-  PairLock(const PairLock&) = delete;
-  PairLock& operator=(const PairLock&) = delete;
-};
-
-// The locks of a call on two shards that may be one (glint_mat_pull_pairs_dot*): the one lock once --
-// PairLock on the same shard twice would deadlock -- else both in lock_order.
-struct PairOrOneLock {
-  glint_shard* o[2];
-  int k;
-  PairOrOneLock(glint_shard* a, glint_shard* b) : k(a == b ? 1 : 2) {
-    std::vector<glint_shard*> v{a, b};
-    lock_order(v);
-    o[0] = v[0];
-    o[1] = v[1];
-    for (int i = 0; i < k; ++i) o[i]->mu.lock();
-  }
-  ~PairOrOneLock() {
-    for (int i = k - 1; i >= 0; --i) o[i]->mu.unlock();
-  }
-  PairOrOneLock(const PairOrOneLock&) = delete;
-  PairOrOneLock& operator=(const PairOrOneLock&) = delete;
 };
 
 // what the two shards of a row-pair call must share: both matrix shards, one dtype, device and cols
@@ -1431,6 +1468,23 @@ int dev_call(glint_shard* s, int args_rc, void* stream, F body) {
   DeviceGuard g(s->device);
   if (int rc = dev_order_after_host(s, (hipStream_t)stream)) return rc;
   return body(pick(s, stream));
+}
+
+// dev_call on two shards that may be one: under both locks, after both shards' host-pointer work, both
+// marked for their sync. A slab with views orders itself through their locks, which this call does not
+// hold, so it is refused (glint_vec_push_dev_shards' rule).
+template <typename F>
+int dev_call2(glint_shard* a, glint_shard* b, int args_rc, void* stream, F body) {
+  if (args_rc) return args_rc;
+  PairLock lk(a, b);
+  if (!a->views.empty() || !b->views.empty()) return GLINT_EINVAL;
+  DeviceGuard g(a->device);
+  glint_shard* const both[2] = {a, b};
+  for (int i = 0; i < (a == b ? 1 : 2); ++i) {
+    if (int rc = dev_order_after_host(both[i], (hipStream_t)stream)) return rc;
+    (void)pick(both[i], stream);
+  }
+  return body((hipStream_t)stream);
 }
 
 // What a host-pointer call does first, under the shard's lock: a slab with views is refused, the open
@@ -1908,54 +1962,32 @@ int glint_mat_push_rows_axpy_dev(glint_shard_t s, const int64_t* rows, int64_t n
 
 int glint_mat_push_rows_adagrad_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows, const void* grads,
                                     int64_t n, double lr, double eps, void* stream) {
-  if (int rc = push_adagrad_args(weights, state, rows, grads, n, lr, eps)) return rc;
-  if (n == 0) return GLINT_OK;
-  PairLock lk(weights, state);
-  // a slab with views orders itself through their locks, which this call does not hold
-  // (glint_vec_push_dev_shards' rule)
-  if (!weights->views.empty() || !state->views.empty()) return GLINT_EINVAL;
-  DeviceGuard g(weights->device);
-  hipStream_t st = (hipStream_t)stream;
-  for (glint_shard* s : {weights, state}) {  // after both shards' host-pointer work; both marked for their sync
-    if (int rc = dev_order_after_host(s, st)) return rc;
-    (void)pick(s, stream);
-  }
-  if (weights->dtype == GLINT_F64)
-    return push_rows_adagrad<double>(weights, state, (const i64*)rows, grads, n, lr, eps, st);
-  return push_rows_adagrad<float>(weights, state, (const i64*)rows, grads, n, lr, eps, st);
+  const int args_rc = push_adagrad_args(weights, state, rows, grads, n, lr, eps);
+  if (args_rc == GLINT_OK && n == 0) return GLINT_OK;
+  return dev_call2(weights, state, args_rc, stream, [&](hipStream_t st) -> int {
+    if (weights->dtype == GLINT_F64)
+      return push_rows_adagrad<double>(weights, state, (const i64*)rows, grads, n, lr, eps, st);
+    return push_rows_adagrad<float>(weights, state, (const i64*)rows, grads, n, lr, eps, st);
+  });
 }
 
 int glint_mat_pull_pairs_dot_dev(glint_shard_t a, glint_shard_t b, const int64_t* rows_a, const int64_t* rows_b,
                                  int64_t n, void* out, void* stream) {
-  if (int rc = pull_pairs_args(a, b, rows_a, rows_b, n, out)) return rc;
-  if (n == 0) return GLINT_OK;
-  PairOrOneLock lk(a, b);
-  // a slab with views orders itself through their locks, which this call does not hold
-  // (glint_mat_push_rows_adagrad_dev's rule)
-  if (!a->views.empty() || !b->views.empty()) return GLINT_EINVAL;
-  DeviceGuard g(a->device);
-  hipStream_t st = (hipStream_t)stream;
-  for (int i = 0; i < lk.k; ++i) {  // after both shards' host-pointer work; both marked for their sync
-    if (int rc = dev_order_after_host(lk.o[i], st)) return rc;
-    (void)pick(lk.o[i], stream);
-  }
-  GLINT_DISPATCH(a->dtype, pull_pairs_dot, a, b, (const i64*)rows_a, (const i64*)rows_b, n, out, st);
+  const int args_rc = pull_pairs_args(a, b, rows_a, rows_b, n, out);
+  if (args_rc == GLINT_OK && n == 0) return GLINT_OK;
+  return dev_call2(a, b, args_rc, stream, [&](hipStream_t st) -> int {
+    GLINT_DISPATCH(a->dtype, pull_pairs_dot, a, b, (const i64*)rows_a, (const i64*)rows_b, n, out, st);
+  });
 }
 
 int glint_mat_push_pairs_axpy_dev(glint_shard_t dst, glint_shard_t src, const int64_t* rows_dst,
                                   const int64_t* rows_src, const void* coef, int64_t n, int flags, void* stream) {
-  if (int rc = push_pairs_args(dst, src, rows_dst, rows_src, coef, n, flags)) return rc;
-  if (n == 0) return GLINT_OK;
-  PairLock lk(dst, src);
-  if (!dst->views.empty() || !src->views.empty()) return GLINT_EINVAL;  // (as above)
-  DeviceGuard g(dst->device);
-  hipStream_t st = (hipStream_t)stream;
-  for (glint_shard* s : {dst, src}) {  // after both shards' host-pointer work; both marked for their sync
-    if (int rc = dev_order_after_host(s, st)) return rc;
-    (void)pick(s, stream);
-  }
-  GLINT_DISPATCH(dst->dtype, push_pairs_axpy, dst, src, (const i64*)rows_dst, (const i64*)rows_src, coef, n, flags,
-                 st);
+  const int args_rc = push_pairs_args(dst, src, rows_dst, rows_src, coef, n, flags);
+  if (args_rc == GLINT_OK && n == 0) return GLINT_OK;
+  return dev_call2(dst, src, args_rc, stream, [&](hipStream_t st) -> int {
+    GLINT_DISPATCH(dst->dtype, push_pairs_axpy, dst, src, (const i64*)rows_dst, (const i64*)rows_src, coef, n, flags,
+                   st);
+  });
 }
 
 int glint_shard_fill_dev(glint_shard_t s, const int64_t* rows, int64_t n, const void* value, void* stream) {
@@ -1973,68 +2005,6 @@ int glint_shard_init_uniform_dev(glint_shard_t s, const int64_t* rows, int64_t n
 
 // ---- host-pointer entry points --------------------------------------------------------------------
 namespace {
-
-// Host arrays up to this size are staged through the shard's pinned buffer: one CPU memcpy per
-// section, then ONE DMA for the whole message (a pageable hipMemcpy costs a driver-side bounce and a
-// fence per section, which dominated small Akka-sized messages: ~1000 records per push,
-// GranularBigVectorSpec.scala:21). Larger arrays go straight from pageable memory at PCIe rate.
-// GLINT_PINNED_STAGE_MAX (bytes) overrides the crossover; tools/host_latency.py measures it.
-size_t pinned_stage_max() {
-  static EnvKnob k("GLINT_PINNED_STAGE_MAX");
-  return (size_t)k.get([](const char* e) -> long long {
-    return e ? (long long)std::strtoull(e, nullptr, 10) : (2ll << 20);
-  });
-}
-
-// stage host arrays into the shard's device scratch: returns device pointers to each section and,
-// when the call is small enough, the pinned host block that mirrors the scratch (pinned = true)
-struct Staged {
-  char* p[3] = {nullptr, nullptr, nullptr};
-  bool pinned = false;
-  size_t in_bytes = 0;  // bytes of the staged input sections (the pinned block's first part)
-};
-
-int stage(glint_shard* s, const void* const* src, const size_t* bytes, int count, Staged& out, size_t extra,
-          char** extra_ptr) {
-  size_t need = 0;
-  for (int i = 0; i < count; ++i) need += pad256(bytes[i]);
-  out.in_bytes = need;
-  need += pad256(extra);
-  int rc = grow(&s->d_scratch, &s->scratch_bytes, need);
-  if (rc) return rc;
-  out.pinned = need <= pinned_stage_max() && grow_pinned(&s->h_stage, &s->h_stage_bytes, need) == GLINT_OK;
-  char* b = (char*)s->d_scratch;
-  char* h = (char*)s->h_stage;
-  for (int i = 0; i < count; ++i) {
-    out.p[i] = b;
-    if (bytes[i]) {
-      if (out.pinned) std::memcpy(h, src[i], bytes[i]);
-      else HIPCHK(hipMemcpyAsync(b, src[i], bytes[i], hipMemcpyHostToDevice, s->stream));
-    }
-    b += pad256(bytes[i]);
-    h += pad256(bytes[i]);
-  }
-  if (out.pinned && out.in_bytes) {
-    HIPCHK(hipMemcpyAsync(s->d_scratch, s->h_stage, out.in_bytes, hipMemcpyHostToDevice, s->stream));
-  }
-  if (extra_ptr) *extra_ptr = b;
-  return GLINT_OK;
-}
-
-// Ends a host call: the device error state rides back with the call's last copy (pinned, async),
-// so a clean call costs one stream synchronisation.
-int finish(glint_shard* s) {
-  ErrState local{};
-  ErrState* h = s->h_err ? s->h_err : &local;
-  HIPCHK(hipMemcpyAsync(h, s->d_err_host, sizeof(ErrState), hipMemcpyDeviceToHost, s->stream));
-  HIPCHK(hipStreamSynchronize(s->stream));
-  if (!s->dev_dirty) latch_hints(s);  // a sync point (the shard's pushes all ran on this stream)
-  if (h->min_bad_enc == 0) return GLINT_OK;
-  s->last_bad = (i64)~h->min_bad_enc;
-  HIPCHK(hipMemsetAsync(s->d_err_host, 0, sizeof(ErrState), s->stream));
-  HIPCHK(hipStreamSynchronize(s->stream));
-  return GLINT_EOUTOFRANGE;
-}
 
 // ---- host-side validation of ring messages ------------------------------------------------------
 // The first record of a message the reference would reject -- RangePartition.globalToLocal /
@@ -2287,34 +2257,6 @@ int ring_acquire_locked(glint_shard* s, i64 n, int* slot, size_t out_bytes = 0) 
     return GLINT_OK;
   }
   return GLINT_ENOMEM;  // every slot handed out and not pushed
-}
-
-// ---- caller buffers the kernels can write (glint_host_alloc) -----------------------------------
-// Pinned, device-mapped host memory handed to a server for its response images: a coalesced pull
-// whose destination lies in one is answered by the kernel straight into it.
-struct HostRange {
-  char* h;
-  size_t n;
-  char* d;
-  std::shared_ptr<std::atomic<long>> pending;  // kernel writes enqueued into it and not yet retired
-};
-std::mutex g_host_mu;
-std::vector<HostRange> g_host;  // sorted by h
-
-// p's device address if [p, p + bytes) lies in one glint_host_alloc buffer and p is aligned to
-// `align`, else nullptr; with `hold`, the buffer is held (glint_host_free refuses it) until *hold resets
-void* host_dev_ptr(const void* p, size_t bytes, size_t align, HostHold* hold) {
-  if (!p || (uintptr_t)p % align) return nullptr;
-  std::lock_guard<std::mutex> lk(g_host_mu);
-  if (g_host.empty()) return nullptr;
-  const char* c = (const char*)p;
-  auto it = std::upper_bound(g_host.begin(), g_host.end(), c,
-                             [](const char* x, const HostRange& r) { return x < r.h; });
-  if (it == g_host.begin()) return nullptr;
-  --it;
-  if (c + bytes > it->h + it->n) return nullptr;
-  if (hold) *hold = HostHold(it->pending);
-  return it->d + (c - it->h);
 }
 
 // smallest answer (bytes) a pull writes straight into a glint_host_alloc buffer (GLINT_DIRECT_MIN_BYTES)
@@ -2642,31 +2584,6 @@ int ring_wait_locked(glint_shard* s, u64 ticket, i64* first_bad) {
   return GLINT_OK;
 }
 
-// A device-resident call runs on the caller's stream: it first waits for the ring entries enqueued
-// on the shard's stream (they share the data array and the error state).
-int dev_order_after_host(glint_shard* s, hipStream_t st) {
-  // a slab's call reads or writes its views' elements: it waits for their host-pointer work, and
-  // their later host-pointer calls wait for it (lock order: slab, then view)
-  for (glint_shard* v : s->views) {
-    ShardLock lv(v);
-    if (int rc = dev_order_after_host(v, st)) return rc;
-    v->last_dev_stream = st;
-    v->dev_dirty = true;
-  }
-  int rc = ring_flush_locked(s);
-  if (rc) return rc;
-  if (!s->host_pending) return GLINT_OK;
-  if (!s->host_ev && hipEventCreateWithFlags(&s->host_ev, hipEventDisableTiming) != hipSuccess) {
-    (void)hipGetLastError();
-    s->host_ev = nullptr;
-    return GLINT_EDEVICE;
-  }
-  HIPCHK(hipEventRecord(s->host_ev, s->stream));
-  HIPCHK(hipStreamWaitEvent(st, s->host_ev, 0));
-  s->host_pending = false;
-  return GLINT_OK;
-}
-
 // pull answer bytes: n values, or n rows of cols values
 inline size_t pull_bytes(const glint_shard* s, int kind, i64 n) {
   return (size_t)n * s->vsize * (kind == 2 ? (size_t)s->part.cols : 1);
@@ -2690,6 +2607,145 @@ int pull_enqueue_locked(glint_shard* s, int kind, const int64_t* keys, const int
   return ring_pull_locked(s, slot, kind, n, out, ob, ticket);
 }
 
+// Host arrays up to this size are staged through the shard's pinned buffer: one CPU memcpy per
+// section, then ONE DMA for the whole message (a pageable hipMemcpy costs a driver-side bounce and a
+// fence per section, which dominated small Akka-sized messages: ~1000 records per push,
+// GranularBigVectorSpec.scala:21). Larger arrays go straight from pageable memory at PCIe rate.
+// GLINT_PINNED_STAGE_MAX (bytes) overrides the crossover; tools/host_latency.py measures it.
+size_t pinned_stage_max() {
+  static EnvKnob k("GLINT_PINNED_STAGE_MAX");
+  return (size_t)k.get([](const char* e) -> long long {
+    return e ? (long long)std::strtoull(e, nullptr, 10) : (2ll << 20);
+  });
+}
+
+struct HostIn {  // one host array a call stages
+  const void* p;
+  size_t bytes;
+};
+
+// stage host arrays into the shard's device scratch: returns device pointers to each section and to
+// the `extra` bytes behind them and, when the call is small enough, the pinned host block that mirrors
+// the scratch (pinned = true)
+struct Staged {
+  char* p[3] = {nullptr, nullptr, nullptr};
+  char* extra = nullptr;
+  bool pinned = false;
+  size_t in_bytes = 0;  // bytes of the staged input sections (the pinned block's first part)
+};
+
+int stage(glint_shard* s, std::initializer_list<HostIn> in, size_t extra, Staged& out) {
+  size_t need = 0;
+  for (const HostIn& i : in) need += pad256(i.bytes);
+  out.in_bytes = need;
+  need += pad256(extra);
+  int rc = grow(&s->d_scratch, &s->scratch_bytes, need);
+  if (rc) return rc;
+  out.pinned = need <= pinned_stage_max() && grow_pinned(&s->h_stage, &s->h_stage_bytes, need) == GLINT_OK;
+  char* b = (char*)s->d_scratch;
+  char* h = (char*)s->h_stage;
+  char** p = out.p;
+  for (const HostIn& i : in) {
+    *p++ = b;
+    if (i.bytes) {
+      if (out.pinned) std::memcpy(h, i.p, i.bytes);
+      else HIPCHK(hipMemcpyAsync(b, i.p, i.bytes, hipMemcpyHostToDevice, s->stream));
+    }
+    b += pad256(i.bytes);
+    h += pad256(i.bytes);
+  }
+  if (out.pinned && out.in_bytes) {
+    HIPCHK(hipMemcpyAsync(s->d_scratch, s->h_stage, out.in_bytes, hipMemcpyHostToDevice, s->stream));
+  }
+  out.extra = b;
+  return GLINT_OK;
+}
+
+// Ends a host call: the device error state rides back with the call's last copy (pinned, async),
+// so a clean call costs one stream synchronisation.
+int finish(glint_shard* s) {
+  ErrState local{};
+  ErrState* h = s->h_err ? s->h_err : &local;
+  HIPCHK(hipMemcpyAsync(h, s->d_err_host, sizeof(ErrState), hipMemcpyDeviceToHost, s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  if (!s->dev_dirty) latch_hints(s);  // a sync point (the shard's pushes all ran on this stream)
+  if (h->min_bad_enc == 0) return GLINT_OK;
+  s->last_bad = (i64)~h->min_bad_enc;
+  HIPCHK(hipMemsetAsync(s->d_err_host, 0, sizeof(ErrState), s->stream));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  return GLINT_EOUTOFRANGE;
+}
+
+// One copy from the device to the caller's memory at the end of a host call. With `bounce` (the first
+// copy only, src = Staged::extra) the answer of a pinned call goes into the pinned block behind the
+// inputs, then one CPU copy out.
+struct HostBack {
+  void* dst = nullptr;
+  const void* src = nullptr;
+  size_t bytes = 0;
+  bool bounce = false;
+};
+
+// The staged part of a host-pointer call, on a shard entered and locked: the `in` sections are staged
+// (at most three) with `extra` device bytes behind them, body(staged, stream, back) launches on the
+// shard's stream and names up to two copies back, and the call ends synchronised with the error state
+// read (finish). The body's launches record rejected records as the call's own (d_err_host). Any
+// failure once something is staged drains the stream first (launch_failed).
+template <typename F>
+int host_staged(glint_shard* s, std::initializer_list<HostIn> in, size_t extra, F body) {
+  Staged st;
+  int rc = stage(s, in, extra, st);
+  if (rc) return rc;
+  HostCall hc(s);
+  HostBack back[2];
+  rc = body(st, s->stream, back);
+  if (rc) return launch_failed(s, rc);
+  char* h_out = back[0].bounce && st.pinned ? (char*)s->h_stage + st.in_bytes : nullptr;
+  if (back[0].dst) {
+    HIPCHK(hipMemcpyAsync(h_out ? h_out : back[0].dst, back[0].src, back[0].bytes, hipMemcpyDeviceToHost, s->stream));
+  }
+  if (back[1].dst) HIPCHK(hipMemcpyAsync(back[1].dst, back[1].src, back[1].bytes, hipMemcpyDeviceToHost, s->stream));
+  rc = finish(s);
+  if (rc == GLINT_OK && h_out) std::memcpy(back[0].dst, h_out, back[0].bytes);
+  return rc;
+}
+
+// The rows a host-pointer call names: `a` of the first shard, `b` (if any) of the second.
+struct HostRows {
+  const int64_t* a;
+  const int64_t* b;
+  int64_t n;
+};
+
+// A host-pointer call on shards a and b, which are one for a single-shard call and may be one for a
+// pair call. Under the lock(s) and on a's device both shards are entered (OrderFlush; host_push and
+// host_pull, which enter otherwise and have ring paths in front, use host_staged themselves), then every
+// named row is checked before anything is staged or enqueued: the lowest index with rows.a[i] outside
+// `a` or rows.b[i] outside `b` is rejected (glint_shard_last_error(a)) and the call changes nothing.
+// `nothing` ends a call that names no work here. Else a's stream waits for b's -- its flushed ring
+// entries and, through order_after_dev, its last device-resident call -- and the work is host_staged's,
+// on a.
+template <typename F>
+int host_call(glint_shard* a, glint_shard* b, HostRows rows, bool nothing, std::initializer_list<HostIn> in,
+              size_t extra, F body) {
+  PairLock lk(a, b);
+  DeviceGuard g(a->device);
+  int rc = host_enter(a, HostEntry::OrderFlush);
+  if (rc == GLINT_OK && b != a) rc = host_enter(b, HostEntry::OrderFlush);
+  if (rc) return rc;
+  const i64 bad_a = rows.a ? host_first_bad(a, rows.a, nullptr, rows.n) : -1;
+  const i64 bad_b = rows.b ? host_first_bad(b, rows.b, nullptr, rows.n) : -1;
+  const i64 bad = bad_a < 0 ? bad_b : (bad_b < 0 ? bad_a : std::min(bad_a, bad_b));
+  if (bad >= 0) {
+    a->last_bad = bad;
+    return GLINT_EOUTOFRANGE;
+  }
+  if (nothing) return GLINT_OK;
+  if (b != a) rc = wait_for_host_stream(b, a->stream);
+  if (rc) return rc;
+  return host_staged(a, in, extra, body);
+}
+
 int host_push(glint_shard* s, bool mat, const int64_t* keys, const int32_t* cols, const void* vals, int64_t n,
               int flags) {
   if (n < 0 || (n > 0 && (!keys || !vals || (mat && !cols)))) return GLINT_EINVAL;
@@ -2707,25 +2763,18 @@ int host_push(glint_shard* s, bool mat, const int64_t* keys, const int32_t* cols
   }
   rc = ring_flush_locked(s);
   if (rc) return rc;
-  Staged st;
-  const void* src[3] = {keys, mat ? (const void*)cols : vals, vals};
-  size_t bytes[3] = {(size_t)n * 8, mat ? (size_t)n * 4 : (size_t)n * s->vsize, (size_t)n * s->vsize};
-  rc = stage(s, src, bytes, mat ? 3 : 2, st, 0, nullptr);
-  if (rc) return rc;
+  const size_t kb = (size_t)n * 8, vb = (size_t)n * s->vsize;
   const int hflags = flags | kPushHostSequential;  // the actor's update: message order by default
-  HostCall hc(s);  // this call's rejected records are its own (d_err_host, read by finish)
   if (mat) {
-    rc = [&]() -> int {
-      GLINT_DISPATCH(s->dtype, push_mat_t, s, (const i64*)st.p[0], (const int32_t*)st.p[1], st.p[2], n, hflags,
-                     s->stream);
-    }();
-  } else {
-    rc = [&]() -> int {
-      GLINT_DISPATCH(s->dtype, push_vec_t, s, (const i64*)st.p[0], nullptr, st.p[1], n, hflags, s->stream);
-    }();
+    return host_staged(s, {{keys, kb}, {cols, (size_t)n * 4}, {vals, vb}}, 0,
+                       [&](const Staged& st, hipStream_t stream, HostBack*) -> int {
+                         GLINT_DISPATCH(s->dtype, push_mat_t, s, (const i64*)st.p[0], (const int32_t*)st.p[1], st.p[2], n,
+                                        hflags, stream);
+                       });
   }
-  if (rc) return launch_failed(s, rc);
-  return finish(s);
+  return host_staged(s, {{keys, kb}, {vals, vb}}, 0, [&](const Staged& st, hipStream_t stream, HostBack*) -> int {
+    GLINT_DISPATCH(s->dtype, push_vec_t, s, (const i64*)st.p[0], nullptr, st.p[1], n, hflags, stream);
+  });
 }
 
 // kind: 0 vector get, 1 matrix get, 2 matrix rows
@@ -2737,7 +2786,8 @@ int host_pull(glint_shard* s, int kind, const int64_t* keys, const int32_t* cols
   DeviceGuard g(s->device);
   int rc = host_enter(s, HostEntry::FlushOrder);
   if (rc) return rc;
-  if (n <= GLINT_ZERO_COPY_MAX && pull_bytes(s, kind, n) <= kRingAnswerMax) {
+  const size_t out_bytes = pull_bytes(s, kind, n);
+  if (n <= GLINT_ZERO_COPY_MAX && out_bytes <= kRingAnswerMax) {
     // Akka-sized: one workgroup reads the keys from a mapped pinned ring slot, writes the answer into
     // it and signals its ticket, so the call is one launch and a wait on host memory. The keys are
     // checked first: a rejected pull enqueues nothing and throws, as get() does in the reference.
@@ -2746,353 +2796,32 @@ int host_pull(glint_shard* s, int kind, const int64_t* keys, const int32_t* cols
     if (rc) return rc;
     return ring_wait_locked(s, ticket, nullptr);
   }
-  const size_t out_bytes = pull_bytes(s, kind, n);
-  Staged st;
-  const void* src[2] = {keys, cols};
-  size_t bytes[2] = {(size_t)n * 8, kind == 1 ? (size_t)n * 4 : 0};
-  char* d_out = nullptr;
-  rc = stage(s, src, bytes, kind == 1 ? 2 : 1, st, out_bytes, &d_out);
-  if (rc) return rc;
-  HostCall hc(s);  // this call's rejected records are its own (d_err_host, read by finish)
-  if (kind == 0) {
-    rc = [&]() -> int { GLINT_DISPATCH(s->dtype, launch_vec_pull, s, (const i64*)st.p[0], d_out, n, s->stream); }();
-  } else if (kind == 1) {
-    rc = [&]() -> int {
-      GLINT_DISPATCH(s->dtype, launch_mat_pull, s, (const i64*)st.p[0], (const int32_t*)st.p[1], d_out, n,
-                     s->stream);
-    }();
-  } else {
-    rc = [&]() -> int {
-      GLINT_DISPATCH(s->dtype, launch_mat_pull_rows, s, (const i64*)st.p[0], d_out, n, s->stream);
-    }();
-  }
-  if (rc) return launch_failed(s, rc);
-  if (st.pinned) {  // answer into the pinned block behind the inputs, then one CPU copy out
-    char* h_out = (char*)s->h_stage + st.in_bytes;
-    HIPCHK(hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, s->stream));
-    rc = finish(s);
-    if (rc == GLINT_OK) std::memcpy(out, h_out, out_bytes);
-    return rc;
-  }
-  HIPCHK(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, s->stream));
-  return finish(s);
-}
-
-// glint_mat_push_rows: every row is checked before anything is enqueued (a rejected message applies
-// nothing, as host_push's ring messages), then the two sections are staged and the push runs on the
-// shard's stream in message order (kPushHostSequential).
-int host_push_rows(glint_shard* s, const int64_t* rows, const void* vals, int64_t n, int flags) {
-  ShardLock lk(s);
-  DeviceGuard g(s->device);
-  int rc = host_enter(s, HostEntry::OrderFlush);
-  if (rc == GLINT_OK) rc = reject_if_bad(s, rows, nullptr, n);
-  if (rc) return rc;
-  Staged st;
-  const void* src[2] = {rows, vals};
-  size_t bytes[2] = {(size_t)n * 8, (size_t)n * (size_t)s->part.cols * s->vsize};
-  rc = stage(s, src, bytes, 2, st, 0, nullptr);
-  if (rc) return rc;
-  HostCall hc(s);  // this call's rejected records are its own (d_err_host, read by finish)
-  rc = [&]() -> int {
-    GLINT_DISPATCH(s->dtype, push_rows, s, (const i64*)st.p[0], st.p[1], n, flags | kPushHostSequential, s->stream);
-  }();
-  if (rc) return launch_failed(s, rc);
-  return finish(s);
-}
-
-// glint_mat_pull_rows_sparse: the rows are checked and staged, the count and its scan run, and the host
-// reads row_ptr -- the one thing it cannot size beforehand is the answer. The emit then writes into
-// device buffers of min(nnz, cap) entries (the shard's deterministic-path scratch: the scan is done
-// with it by then), and only those come back: (n + 1) * 8 + min(nnz, cap) * (4 + vsize) bytes.
-int host_pull_rows_sparse(glint_shard* s, const int64_t* rows, int64_t n, int64_t* row_ptr, int32_t* out_cols,
-                          void* out_vals, int64_t cap, int64_t* nnz) {
-  ShardLock lk(s);
-  DeviceGuard g(s->device);
-  int rc = host_enter(s, HostEntry::OrderFlush);
-  if (rc == GLINT_OK) rc = reject_if_bad(s, rows, nullptr, n);
-  if (rc) return rc;
-  if (n == 0) {
-    row_ptr[0] = 0;
-    if (nnz) *nnz = 0;
-    return GLINT_OK;
-  }
-  Staged st;
-  const void* src[1] = {rows};
-  size_t bytes[1] = {(size_t)n * 8};
-  char* d_ptr = nullptr;
-  rc = stage(s, src, bytes, 1, st, (size_t)(n + 1) * 8, &d_ptr);
-  if (rc) return rc;
-  HostCall hc(s);  // (every row was checked: nothing is recorded)
-  const i64* d_rows = (const i64*)st.p[0];
-  rc = [&]() -> int { GLINT_DISPATCH(s->dtype, sparse_count_scan, s, d_rows, n, (i64*)d_ptr, s->stream); }();
-  if (rc) return launch_failed(s, rc);
-  HIPCHK(hipMemcpyAsync(row_ptr, d_ptr, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s->stream));
-  HIPCHK(hipStreamSynchronize(s->stream));
-  const i64 total = row_ptr[n];
-  if (nnz) *nnz = total;
-  const i64 m = std::min<i64>(total, cap);
-  if (m <= 0) return finish(s);
-  const size_t cb = pad256((size_t)m * 4);
-  rc = grow(&s->d_det, &s->det_bytes, cb + (size_t)m * s->vsize);
-  if (rc) return rc;
-  int32_t* d_cols = (int32_t*)s->d_det;
-  char* d_vals = (char*)s->d_det + cb;
-  rc = [&]() -> int {
-    GLINT_DISPATCH(s->dtype, sparse_emit, s, d_rows, n, (const i64*)d_ptr, d_cols, (void*)d_vals, m, s->stream);
-  }();
-  if (rc) return launch_failed(s, rc);
-  HIPCHK(hipMemcpyAsync(out_cols, d_cols, (size_t)m * 4, hipMemcpyDeviceToHost, s->stream));
-  HIPCHK(hipMemcpyAsync(out_vals, d_vals, (size_t)m * s->vsize, hipMemcpyDeviceToHost, s->stream));
-  return finish(s);
-}
-
-// glint_mat_pull_rows_sum: grp_ptr and every row are checked before anything is staged (a rejected call
-// writes nothing), then rows and grp_ptr are staged, the one kernel sums into device scratch (the
-// shard's deterministic-path scratch) and g * cols values come back -- never n * cols.
-int host_pull_rows_sum(glint_shard* s, const int64_t* rows, int64_t n, const int64_t* grp_ptr, int64_t g, void* out) {
-  if (grp_ptr[0] != 0 || grp_ptr[g] != n) return GLINT_EINVAL;
-  for (i64 k = 0; k < g; ++k)
-    if (grp_ptr[k + 1] < grp_ptr[k]) return GLINT_EINVAL;
-  if (g == 0) return GLINT_OK;
-  ShardLock lk(s);
-  DeviceGuard dg(s->device);
-  int rc = host_enter(s, HostEntry::OrderFlush);
-  if (rc == GLINT_OK) rc = reject_if_bad(s, rows, nullptr, n);
-  if (rc) return rc;
-  Staged st;
-  const void* src[2] = {rows, grp_ptr};
-  size_t bytes[2] = {(size_t)n * 8, (size_t)(g + 1) * 8};
-  rc = stage(s, src, bytes, 2, st, 0, nullptr);
-  if (rc) return rc;
-  const size_t out_bytes = (size_t)g * (size_t)s->part.cols * s->vsize;
-  rc = grow(&s->d_det, &s->det_bytes, out_bytes);
-  if (rc) return launch_failed(s, rc);
-  HostCall hc(s);  // (every row was checked: nothing is recorded)
-  rc = [&]() -> int {
-    GLINT_DISPATCH(s->dtype, pull_rows_sum, s, (const i64*)st.p[0], n, (const i64*)st.p[1], g, s->d_det, s->stream);
-  }();
-  if (rc) return launch_failed(s, rc);
-  HIPCHK(hipMemcpyAsync(out, s->d_det, out_bytes, hipMemcpyDeviceToHost, s->stream));
-  return finish(s);
-}
-
-// glint_mat_pull_rows_dot: every row is checked before anything is staged (a rejected call writes
-// nothing), then rows and x are staged in one block, the one kernel writes its n * q dots into device
-// scratch (the shard's deterministic-path scratch) and those come back -- never n * cols values.
-int host_pull_rows_dot(glint_shard* s, const int64_t* rows, int64_t n, const void* x, int64_t q, void* out) {
-  ShardLock lk(s);
-  DeviceGuard dg(s->device);
-  int rc = host_enter(s, HostEntry::OrderFlush);
-  if (rc == GLINT_OK) rc = reject_if_bad(s, rows, nullptr, n);
-  if (rc) return rc;
-  Staged st;
-  const void* src[2] = {rows, x};
-  size_t bytes[2] = {(size_t)n * 8, x ? (size_t)q * (size_t)s->part.cols * s->vsize : 0};
-  rc = stage(s, src, bytes, 2, st, 0, nullptr);
-  if (rc) return rc;
-  const size_t out_bytes = (size_t)n * (size_t)q * s->vsize;
-  rc = grow(&s->d_det, &s->det_bytes, out_bytes);
-  if (rc) return launch_failed(s, rc);
-  HostCall hc(s);  // (every row was checked: nothing is recorded)
-  rc = [&]() -> int {
-    GLINT_DISPATCH(s->dtype, pull_rows_dot, s, (const i64*)st.p[0], n, x ? (const void*)st.p[1] : nullptr, q, s->d_det,
-                   s->stream);
-  }();
-  if (rc) return launch_failed(s, rc);
-  HIPCHK(hipMemcpyAsync(out, s->d_det, out_bytes, hipMemcpyDeviceToHost, s->stream));
-  return finish(s);
-}
-
-// glint_mat_pull_topk: x is staged, the scores and the selection levels run on the shard's stream with
-// their scratch in the shard's deterministic-path scratch, and the q * k rows and scores -- behind x in
-// the staging block -- come back: q * k * (8 + vsize) bytes, nothing of size `rows`.
-int host_pull_topk(glint_shard* s, const void* x, int64_t q, int64_t k, int64_t* out_rows, void* out_vals) {
-  ShardLock lk(s);
-  DeviceGuard dg(s->device);
-  int rc = host_enter(s, HostEntry::OrderFlush);
-  if (rc) return rc;
-  Staged st;
-  const void* src[1] = {x};
-  size_t bytes[1] = {(size_t)q * (size_t)s->part.cols * s->vsize};
-  const size_t rows_bytes = pad256((size_t)q * (size_t)k * 8), vals_bytes = (size_t)q * (size_t)k * s->vsize;
-  char* d_out = nullptr;
-  rc = stage(s, src, bytes, 1, st, rows_bytes + vals_bytes, &d_out);
-  if (rc) return rc;
-  HostCall hc(s);  // (no rows are named: nothing is recorded)
-  rc = [&]() -> int {
-    GLINT_DISPATCH(s->dtype, pull_topk, s, (const void*)st.p[0], q, k, (i64*)d_out, (void*)(d_out + rows_bytes),
-                   s->stream);
-  }();
-  if (rc) return launch_failed(s, rc);
-  HIPCHK(hipMemcpyAsync(out_rows, d_out, (size_t)q * (size_t)k * 8, hipMemcpyDeviceToHost, s->stream));
-  HIPCHK(hipMemcpyAsync(out_vals, d_out + rows_bytes, vals_bytes, hipMemcpyDeviceToHost, s->stream));
-  return finish(s);
-}
-
-// glint_mat_push_rows_axpy: every row is checked before anything is enqueued (a rejected message applies
-// nothing), then rows, coef and x are staged in one block -- n * 8 + (n * q + q * cols) values, never
-// n * cols -- and the push runs on the shard's stream in message order (kPushHostSequential). Nothing
-// comes back but the error state.
-int host_push_rows_axpy(glint_shard* s, const int64_t* rows, int64_t n, const void* coef, const void* x, int64_t q,
-                        int flags) {
-  ShardLock lk(s);
-  DeviceGuard g(s->device);
-  int rc = host_enter(s, HostEntry::OrderFlush);
-  if (rc == GLINT_OK) rc = reject_if_bad(s, rows, nullptr, n);
-  if (rc) return rc;
-  Staged st;
-  const void* src[3] = {rows, coef, x};
-  size_t bytes[3] = {(size_t)n * 8, (size_t)n * (size_t)q * s->vsize, (size_t)q * (size_t)s->part.cols * s->vsize};
-  rc = stage(s, src, bytes, 3, st, 0, nullptr);
-  if (rc) return rc;
-  HostCall hc(s);  // this call's rejected records are its own (d_err_host, read by finish)
-  rc = [&]() -> int {
-    GLINT_DISPATCH(s->dtype, push_rows_axpy, s, (const i64*)st.p[0], n, st.p[1], st.p[2], q,
-                   flags | kPushHostSequential, s->stream);
-  }();
-  if (rc) return launch_failed(s, rc);
-  return finish(s);
-}
-
-// glint_mat_push_rows_adagrad: under both shards' locks every row is checked before anything is staged
-// (a rejected message changes neither shard), then rows and grads are staged in one block -- n * 8 +
-// n * cols values -- and the push runs on the weights shard's stream, which first waits for the state
-// shard's: its flushed ring entries and, through order_after_dev, its last device-resident call. The
-// call ends synchronised, so later calls on either shard see the step. Nothing comes back but the error
-// state.
-int host_push_rows_adagrad(glint_shard* w, glint_shard* h, const int64_t* rows, const void* grads, int64_t n, double lr,
-                           double eps) {
-  PairLock lk(w, h);
-  DeviceGuard g(w->device);
-  int rc = host_enter(w, HostEntry::OrderFlush);
-  if (rc == GLINT_OK) rc = host_enter(h, HostEntry::OrderFlush);
-  if (rc == GLINT_OK) rc = reject_if_bad(w, rows, nullptr, n);
-  if (rc) return rc;
-  if (!h->host_ev && hipEventCreateWithFlags(&h->host_ev, hipEventDisableTiming) != hipSuccess) {
-    (void)hipGetLastError();
-    h->host_ev = nullptr;
-    return GLINT_EDEVICE;
-  }
-  HIPCHK(hipEventRecord(h->host_ev, h->stream));
-  HIPCHK(hipStreamWaitEvent(w->stream, h->host_ev, 0));
-  Staged st;
-  const void* src[2] = {rows, grads};
-  size_t bytes[2] = {(size_t)n * 8, (size_t)n * (size_t)w->part.cols * w->vsize};
-  rc = stage(w, src, bytes, 2, st, 0, nullptr);
-  if (rc) return rc;
-  HostCall hc(w);  // this call's rejected records are its own (d_err_host, read by finish)
-  rc = w->dtype == GLINT_F64
-           ? push_rows_adagrad<double>(w, h, (const i64*)st.p[0], st.p[1], n, lr, eps, w->stream)
-           : push_rows_adagrad<float>(w, h, (const i64*)st.p[0], st.p[1], n, lr, eps, w->stream);
-  if (rc) return launch_failed(w, rc);
-  return finish(w);
-}
-
-// What the two-shard host calls below do first, under both locks (host_push_rows_adagrad's order): both
-// shards are entered, and every pair is checked -- the lowest index with row ra[i] outside `a` or row
-// rb[i] outside `b` is rejected (glint_shard_last_error(a)) before anything is staged -- then a's stream
-// waits for an event on b's: its flushed ring entries and, through order_after_dev, its last
-// device-resident call.
-int pairs_host_enter(glint_shard* a, glint_shard* b, const int64_t* ra, const int64_t* rb, int64_t n) {
-  int rc = host_enter(a, HostEntry::OrderFlush);
-  if (rc == GLINT_OK && b != a) rc = host_enter(b, HostEntry::OrderFlush);
-  if (rc) return rc;
-  const i64 bad_a = host_first_bad(a, ra, nullptr, n), bad_b = host_first_bad(b, rb, nullptr, n);
-  const i64 bad = bad_a < 0 ? bad_b : (bad_b < 0 ? bad_a : std::min(bad_a, bad_b));
-  if (bad >= 0) {
-    a->last_bad = bad;
-    return GLINT_EOUTOFRANGE;
-  }
-  if (b == a) return GLINT_OK;
-  if (!b->host_ev && hipEventCreateWithFlags(&b->host_ev, hipEventDisableTiming) != hipSuccess) {
-    (void)hipGetLastError();
-    b->host_ev = nullptr;
-    return GLINT_EDEVICE;
-  }
-  HIPCHK(hipEventRecord(b->host_ev, b->stream));
-  HIPCHK(hipStreamWaitEvent(a->stream, b->host_ev, 0));
-  return GLINT_OK;
-}
-
-// glint_mat_pull_pairs_dot: pairs_host_enter, then the two row arrays are staged in one block, the one
-// kernel writes its n dots behind them in a's scratch and those come back -- 2 n ids out, n values back,
-// nothing of size cols. The work runs on a's stream and the call ends synchronised.
-int host_pull_pairs_dot(glint_shard* a, glint_shard* b, const int64_t* ra, const int64_t* rb, int64_t n, void* out) {
-  PairOrOneLock lk(a, b);
-  DeviceGuard g(a->device);
-  int rc = pairs_host_enter(a, b, ra, rb, n);
-  if (rc) return rc;
-  Staged st;
-  const void* src[2] = {ra, rb};
-  size_t bytes[2] = {(size_t)n * 8, (size_t)n * 8};
-  const size_t out_bytes = (size_t)n * a->vsize;
-  char* d_out = nullptr;
-  rc = stage(a, src, bytes, 2, st, out_bytes, &d_out);
-  if (rc) return rc;
-  HostCall hc(a);  // (every pair was checked: nothing is recorded)
-  rc = [&]() -> int {
-    GLINT_DISPATCH(a->dtype, pull_pairs_dot, a, b, (const i64*)st.p[0], (const i64*)st.p[1], n, (void*)d_out,
-                   a->stream);
-  }();
-  if (rc) return launch_failed(a, rc);
-  if (st.pinned) {  // answer into the pinned block behind the inputs, then one CPU copy out
-    char* h_out = (char*)a->h_stage + st.in_bytes;
-    HIPCHK(hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, a->stream));
-    rc = finish(a);
-    if (rc == GLINT_OK) std::memcpy(out, h_out, out_bytes);
-    return rc;
-  }
-  HIPCHK(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, a->stream));
-  return finish(a);
-}
-
-// glint_mat_push_pairs_axpy: pairs_host_enter (a rejected message changes nothing), then the two row
-// arrays and coef are staged in one block -- 2 n ids and n values, nothing of size cols -- and the push
-// runs on dst's stream in message order (kPushHostSequential). The call ends synchronised. Nothing comes
-// back but the error state.
-int host_push_pairs_axpy(glint_shard* dst, glint_shard* src, const int64_t* rd, const int64_t* rs, const void* coef,
-                         int64_t n, int flags) {
-  PairLock lk(dst, src);
-  DeviceGuard g(dst->device);
-  int rc = pairs_host_enter(dst, src, rd, rs, n);
-  if (rc) return rc;
-  Staged st;
-  const void* in[3] = {rd, rs, coef};
-  size_t bytes[3] = {(size_t)n * 8, (size_t)n * 8, (size_t)n * dst->vsize};
-  rc = stage(dst, in, bytes, 3, st, 0, nullptr);
-  if (rc) return rc;
-  HostCall hc(dst);  // this call's rejected records are its own (d_err_host, read by finish)
-  rc = [&]() -> int {
-    GLINT_DISPATCH(dst->dtype, push_pairs_axpy, dst, src, (const i64*)st.p[0], (const i64*)st.p[1],
-                   (const void*)st.p[2], n, flags | kPushHostSequential, dst->stream);
-  }();
-  if (rc) return launch_failed(dst, rc);
-  return finish(dst);
+  return host_staged(s, {{keys, (size_t)n * 8}, {cols, kind == 1 ? (size_t)n * 4 : 0}}, out_bytes,
+                     [&](const Staged& st, hipStream_t stream, HostBack* back) -> int {
+                       back[0] = {out, st.extra, out_bytes, true};
+                       const i64* k = (const i64*)st.p[0];
+                       if (kind == 0) {
+                         GLINT_DISPATCH(s->dtype, launch_vec_pull, s, k, st.extra, n, stream);
+                       }
+                       if (kind == 1) {
+                         GLINT_DISPATCH(s->dtype, launch_mat_pull, s, k, (const int32_t*)st.p[1], st.extra, n, stream);
+                       }
+                       GLINT_DISPATCH(s->dtype, launch_mat_pull_rows, s, k, st.extra, n, stream);
+                     });
 }
 
 // glint_shard_fill / glint_shard_init_uniform: the shard is entered as by glint_mat_push_rows (the open
 // ring batch flushed, after enqueued messages and the last device-resident call; a slab with views
 // refused), every named row is checked before anything is written, the row list is staged and the one
 // launch runs on the shard's stream; the call ends synchronised. An ordinary write: the error state and
-// the failed list are left alone.
-int host_init(glint_shard* s, const int64_t* rows, int64_t n, const InitSpec& sp) {
-  ShardLock lk(s);
-  DeviceGuard g(s->device);
-  int rc = host_enter(s, HostEntry::OrderFlush);
-  if (rc == GLINT_OK && rows) rc = reject_if_bad(s, rows, nullptr, n);
-  if (rc) return rc;
-  if (rows && n == 0) return GLINT_OK;  // an empty list names nothing
-  Staged st;
-  if (rows) {
-    const void* src[1] = {rows};
-    size_t bytes[1] = {(size_t)n * 8};
-    rc = stage(s, src, bytes, 1, st, 0, nullptr);
-    if (rc) return rc;
-  }
-  HostCall hc(s);  // (every row was checked: nothing is recorded)
-  rc = shard_init(s, (const i64*)st.p[0], n, rows != nullptr, sp.uniform, sp.seed, sp.a, sp.b, s->stream);
-  if (rc) return launch_failed(s, rc);
-  return finish(s);
+// the failed list are left alone. An empty list names nothing.
+int host_init(glint_shard* s, int args_rc, const int64_t* rows, int64_t n, const InitSpec& sp) {
+  if (args_rc) return args_rc;
+  return host_call(s, s, {rows, nullptr, n}, rows && n == 0, {{rows, (size_t)n * 8}}, 0,
+                   [&](const Staged& st, hipStream_t stream, HostBack*) -> int {
+                     return shard_init(s, rows ? (const i64*)st.p[0] : nullptr, n, rows != nullptr, sp.uniform, sp.seed,
+                                       sp.a, sp.b, stream);
+                   });
 }
 
 }  // namespace
@@ -3101,47 +2830,12 @@ extern "C" {
 
 int glint_shard_fill(glint_shard_t s, const int64_t* rows, int64_t n, const void* value) {
   InitSpec sp{};
-  if (int rc = fill_args(s, rows, n, value, &sp)) return rc;
-  return host_init(s, rows, n, sp);
+  return host_init(s, fill_args(s, rows, n, value, &sp), rows, n, sp);
 }
 
 int glint_shard_init_uniform(glint_shard_t s, const int64_t* rows, int64_t n, uint64_t seed, double lo, double hi) {
   InitSpec sp{};
-  if (int rc = uniform_args(s, rows, n, seed, lo, hi, &sp)) return rc;
-  return host_init(s, rows, n, sp);
-}
-
-int glint_mat_pull_pairs_dot(glint_shard_t a, glint_shard_t b, const int64_t* rows_a, const int64_t* rows_b,
-                             int64_t n, void* out) {
-  if (int rc = pull_pairs_args(a, b, rows_a, rows_b, n, out)) return rc;
-  if (n == 0) return GLINT_OK;
-  return host_pull_pairs_dot(a, b, rows_a, rows_b, n, out);
-}
-
-int glint_mat_push_pairs_axpy(glint_shard_t dst, glint_shard_t src, const int64_t* rows_dst, const int64_t* rows_src,
-                              const void* coef, int64_t n, int flags) {
-  if (int rc = push_pairs_args(dst, src, rows_dst, rows_src, coef, n, flags)) return rc;
-  if (n == 0) return GLINT_OK;
-  return host_push_pairs_axpy(dst, src, rows_dst, rows_src, coef, n, flags);
-}
-
-int glint_mat_push_rows_adagrad(glint_shard_t weights, glint_shard_t state, const int64_t* rows, const void* grads,
-                                int64_t n, double lr, double eps) {
-  if (int rc = push_adagrad_args(weights, state, rows, grads, n, lr, eps)) return rc;
-  if (n == 0) return GLINT_OK;
-  return host_push_rows_adagrad(weights, state, rows, grads, n, lr, eps);
-}
-
-int glint_mat_pull_topk(glint_shard_t s, const void* x, int64_t q, int64_t k, int64_t* out_rows, void* out_vals) {
-  if (int rc = pull_topk_args(s, x, q, k, out_rows, out_vals)) return rc;
-  return host_pull_topk(s, x, q, k, out_rows, out_vals);
-}
-
-int glint_mat_push_rows_axpy(glint_shard_t s, const int64_t* rows, int64_t n, const void* coef, const void* x,
-                             int64_t q, int flags) {
-  if (int rc = push_axpy_args(s, rows, n, coef, x, q, flags)) return rc;
-  if (n == 0) return GLINT_OK;
-  return host_push_rows_axpy(s, rows, n, coef, x, q, flags);
+  return host_init(s, uniform_args(s, rows, n, seed, lo, hi, &sp), rows, n, sp);
 }
 
 int glint_vec_push(glint_shard_t s, const int64_t* keys, const void* vals, int64_t n, int flags) {
@@ -3170,28 +2864,173 @@ int glint_mat_pull_rows(glint_shard_t s, const int64_t* rows, void* out, int64_t
   return host_pull(s, 2, rows, nullptr, out, n);
 }
 
+// glint_mat_push_rows: every row is checked before anything is enqueued (a rejected message applies
+// nothing, as host_push's ring messages), then the two sections are staged and the push runs on the
+// shard's stream in message order (kPushHostSequential).
 int glint_mat_push_rows(glint_shard_t s, const int64_t* rows, const void* vals, int64_t n, int flags) {
   if (int rc = push_rows_args(s, rows, vals, n, flags)) return rc;
   if (n == 0) return GLINT_OK;
-  return host_push_rows(s, rows, vals, n, flags);
+  return host_call(s, s, {rows, nullptr, n}, false,
+                   {{rows, (size_t)n * 8}, {vals, (size_t)n * (size_t)s->part.cols * s->vsize}}, 0,
+                   [&](const Staged& st, hipStream_t stream, HostBack*) -> int {
+                     GLINT_DISPATCH(s->dtype, push_rows, s, (const i64*)st.p[0], st.p[1], n, flags | kPushHostSequential, stream);
+                   });
 }
 
+// glint_mat_pull_rows_sparse: the rows are checked and staged, the count and its scan run, and the host
+// reads row_ptr -- the one thing it cannot size beforehand is the answer. The emit then writes into
+// device buffers of min(nnz, cap) entries (the shard's deterministic-path scratch: the scan is done
+// with it by then), and only those come back: (n + 1) * 8 + min(nnz, cap) * (4 + vsize) bytes.
 int glint_mat_pull_rows_sparse(glint_shard_t s, const int64_t* rows, int64_t n, int64_t* row_ptr, int32_t* out_cols,
                                void* out_vals, int64_t cap, int64_t* nnz) {
   if (int rc = pull_sparse_args(s, rows, n, row_ptr, out_cols, out_vals, cap)) return rc;
-  return host_pull_rows_sparse(s, rows, n, row_ptr, out_cols, out_vals, cap, nnz);
+  const int rc = host_call(
+      s, s, {rows, nullptr, n}, n == 0, {{rows, (size_t)n * 8}}, (size_t)(n + 1) * 8,
+      [&](const Staged& st, hipStream_t stream, HostBack* back) -> int {
+        const i64* d_rows = (const i64*)st.p[0];
+        i64* d_ptr = (i64*)st.extra;
+        int rc = [&]() -> int { GLINT_DISPATCH(s->dtype, sparse_count_scan, s, d_rows, n, d_ptr, stream); }();
+        if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(row_ptr, d_ptr, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        if (nnz) *nnz = row_ptr[n];
+        const i64 m = std::min<i64>(row_ptr[n], cap);
+        if (m <= 0) return GLINT_OK;
+        const size_t cb = pad256((size_t)m * 4);
+        rc = grow(&s->d_det, &s->det_bytes, cb + (size_t)m * s->vsize);
+        if (rc) return rc;
+        int32_t* d_cols = (int32_t*)s->d_det;
+        char* d_vals = (char*)s->d_det + cb;
+        back[0] = {out_cols, d_cols, (size_t)m * 4};
+        back[1] = {out_vals, d_vals, (size_t)m * s->vsize};
+        GLINT_DISPATCH(s->dtype, sparse_emit, s, d_rows, n, (const i64*)d_ptr, d_cols, (void*)d_vals, m, stream);
+      });
+  if (rc == GLINT_OK && n == 0) {
+    row_ptr[0] = 0;
+    if (nnz) *nnz = 0;
+  }
+  return rc;
 }
 
+// glint_mat_pull_rows_sum: grp_ptr and every row are checked before anything is staged (a rejected call
+// writes nothing), then rows and grp_ptr are staged, the one kernel sums into device scratch (the
+// shard's deterministic-path scratch) and g * cols values come back -- never n * cols.
 int glint_mat_pull_rows_sum(glint_shard_t s, const int64_t* rows, int64_t n, const int64_t* grp_ptr, int64_t g,
                             void* out) {
   if (int rc = pull_sum_args(s, rows, n, grp_ptr, g, out)) return rc;
-  return host_pull_rows_sum(s, rows, n, grp_ptr, g, out);
+  if (grp_ptr[0] != 0 || grp_ptr[g] != n) return GLINT_EINVAL;
+  for (i64 k = 0; k < g; ++k)
+    if (grp_ptr[k + 1] < grp_ptr[k]) return GLINT_EINVAL;
+  if (g == 0) return GLINT_OK;
+  const size_t out_bytes = (size_t)g * (size_t)s->part.cols * s->vsize;
+  return host_call(s, s, {rows, nullptr, n}, false, {{rows, (size_t)n * 8}, {grp_ptr, (size_t)(g + 1) * 8}}, 0,
+                   [&](const Staged& st, hipStream_t stream, HostBack* back) -> int {
+                     if (int rc = grow(&s->d_det, &s->det_bytes, out_bytes)) return rc;
+                     back[0] = {out, s->d_det, out_bytes};
+                     GLINT_DISPATCH(s->dtype, pull_rows_sum, s, (const i64*)st.p[0], n, (const i64*)st.p[1], g, s->d_det, stream);
+                   });
 }
 
+// glint_mat_pull_rows_dot: every row is checked before anything is staged (a rejected call writes
+// nothing), then rows and x are staged in one block, the one kernel writes its n * q dots into device
+// scratch (the shard's deterministic-path scratch) and those come back -- never n * cols values.
 int glint_mat_pull_rows_dot(glint_shard_t s, const int64_t* rows, int64_t n, const void* x, int64_t q, void* out) {
   if (int rc = pull_dot_args(s, rows, n, x, q, out)) return rc;
   if (n == 0) return GLINT_OK;
-  return host_pull_rows_dot(s, rows, n, x, q, out);
+  const size_t out_bytes = (size_t)n * (size_t)q * s->vsize;
+  return host_call(s, s, {rows, nullptr, n}, false,
+                   {{rows, (size_t)n * 8}, {x, x ? (size_t)q * (size_t)s->part.cols * s->vsize : 0}}, 0,
+                   [&](const Staged& st, hipStream_t stream, HostBack* back) -> int {
+                     if (int rc = grow(&s->d_det, &s->det_bytes, out_bytes)) return rc;
+                     back[0] = {out, s->d_det, out_bytes};
+                     GLINT_DISPATCH(s->dtype, pull_rows_dot, s, (const i64*)st.p[0], n, x ? (const void*)st.p[1] : nullptr, q,
+                                    s->d_det, stream);
+                   });
+}
+
+// glint_mat_pull_topk: x is staged, the scores and the selection levels run on the shard's stream with
+// their scratch in the shard's deterministic-path scratch, and the q * k rows and scores -- behind x in
+// the staging block -- come back: q * k * (8 + vsize) bytes, nothing of size `rows`. No rows are named,
+// so nothing is checked or recorded.
+int glint_mat_pull_topk(glint_shard_t s, const void* x, int64_t q, int64_t k, int64_t* out_rows, void* out_vals) {
+  if (int rc = pull_topk_args(s, x, q, k, out_rows, out_vals)) return rc;
+  const size_t rows_bytes = pad256((size_t)q * (size_t)k * 8), vals_bytes = (size_t)q * (size_t)k * s->vsize;
+  return host_call(s, s, {nullptr, nullptr, 0}, false, {{x, (size_t)q * (size_t)s->part.cols * s->vsize}},
+                   rows_bytes + vals_bytes, [&](const Staged& st, hipStream_t stream, HostBack* back) -> int {
+                     back[0] = {out_rows, st.extra, (size_t)q * (size_t)k * 8};
+                     back[1] = {out_vals, st.extra + rows_bytes, vals_bytes};
+                     GLINT_DISPATCH(s->dtype, pull_topk, s, (const void*)st.p[0], q, k, (i64*)st.extra,
+                                    (void*)(st.extra + rows_bytes), stream);
+                   });
+}
+
+// glint_mat_push_rows_axpy: every row is checked before anything is enqueued (a rejected message applies
+// nothing), then rows, coef and x are staged in one block -- n * 8 + (n * q + q * cols) values, never
+// n * cols -- and the push runs on the shard's stream in message order (kPushHostSequential). Nothing
+// comes back but the error state.
+int glint_mat_push_rows_axpy(glint_shard_t s, const int64_t* rows, int64_t n, const void* coef, const void* x,
+                             int64_t q, int flags) {
+  if (int rc = push_axpy_args(s, rows, n, coef, x, q, flags)) return rc;
+  if (n == 0) return GLINT_OK;
+  return host_call(s, s, {rows, nullptr, n}, false,
+                   {{rows, (size_t)n * 8},
+                    {coef, (size_t)n * (size_t)q * s->vsize},
+                    {x, (size_t)q * (size_t)s->part.cols * s->vsize}},
+                   0, [&](const Staged& st, hipStream_t stream, HostBack*) -> int {
+                     GLINT_DISPATCH(s->dtype, push_rows_axpy, s, (const i64*)st.p[0], n, st.p[1], st.p[2], q,
+                                    flags | kPushHostSequential, stream);
+                   });
+}
+
+// glint_mat_push_rows_adagrad: under both shards' locks every row is checked, against the weights shard,
+// before anything is staged (a rejected message changes neither shard), then rows and grads are staged
+// in one block -- n * 8 + n * cols values -- and the push runs on the weights shard's stream, which first
+// waits for the state shard's. The call ends synchronised, so later calls on either shard see the step.
+// Nothing comes back but the error state.
+int glint_mat_push_rows_adagrad(glint_shard_t weights, glint_shard_t state, const int64_t* rows, const void* grads,
+                                int64_t n, double lr, double eps) {
+  if (int rc = push_adagrad_args(weights, state, rows, grads, n, lr, eps)) return rc;
+  if (n == 0) return GLINT_OK;
+  return host_call(weights, state, {rows, nullptr, n}, false,
+                   {{rows, (size_t)n * 8}, {grads, (size_t)n * (size_t)weights->part.cols * weights->vsize}}, 0,
+                   [&](const Staged& st, hipStream_t stream, HostBack*) -> int {
+                     const i64* d_rows = (const i64*)st.p[0];
+                     if (weights->dtype == GLINT_F64)
+                       return push_rows_adagrad<double>(weights, state, d_rows, st.p[1], n, lr, eps, stream);
+                     return push_rows_adagrad<float>(weights, state, d_rows, st.p[1], n, lr, eps, stream);
+                   });
+}
+
+// glint_mat_pull_pairs_dot: every pair is checked, then the two row arrays are staged in one block, the
+// one kernel writes its n dots behind them in a's scratch and those come back -- 2 n ids out, n values
+// back, nothing of size cols. The work runs on a's stream and the call ends synchronised.
+int glint_mat_pull_pairs_dot(glint_shard_t a, glint_shard_t b, const int64_t* rows_a, const int64_t* rows_b,
+                             int64_t n, void* out) {
+  if (int rc = pull_pairs_args(a, b, rows_a, rows_b, n, out)) return rc;
+  if (n == 0) return GLINT_OK;
+  const size_t out_bytes = (size_t)n * a->vsize;
+  return host_call(a, b, {rows_a, rows_b, n}, false, {{rows_a, (size_t)n * 8}, {rows_b, (size_t)n * 8}}, out_bytes,
+                   [&](const Staged& st, hipStream_t stream, HostBack* back) -> int {
+                     back[0] = {out, st.extra, out_bytes, true};
+                     GLINT_DISPATCH(a->dtype, pull_pairs_dot, a, b, (const i64*)st.p[0], (const i64*)st.p[1], n,
+                                    (void*)st.extra, stream);
+                   });
+}
+
+// glint_mat_push_pairs_axpy: every pair is checked (a rejected message changes nothing), then the two row
+// arrays and coef are staged in one block -- 2 n ids and n values, nothing of size cols -- and the push
+// runs on dst's stream in message order (kPushHostSequential). The call ends synchronised. Nothing comes
+// back but the error state.
+int glint_mat_push_pairs_axpy(glint_shard_t dst, glint_shard_t src, const int64_t* rows_dst, const int64_t* rows_src,
+                              const void* coef, int64_t n, int flags) {
+  if (int rc = push_pairs_args(dst, src, rows_dst, rows_src, coef, n, flags)) return rc;
+  if (n == 0) return GLINT_OK;
+  return host_call(dst, src, {rows_dst, rows_src, n}, false,
+                   {{rows_dst, (size_t)n * 8}, {rows_src, (size_t)n * 8}, {coef, (size_t)n * dst->vsize}}, 0,
+                   [&](const Staged& st, hipStream_t stream, HostBack*) -> int {
+                     GLINT_DISPATCH(dst->dtype, push_pairs_axpy, dst, src, (const i64*)st.p[0], (const i64*)st.p[1],
+                                    (const void*)st.p[2], n, flags | kPushHostSequential, stream);
+                   });
 }
 
 // RequestSerializer.fromBinary (RequestSerializer.scala:59-130) for the push messages, applied

@@ -195,12 +195,11 @@ struct glint_shard {
 // The order a call that locks several shards takes their locks in: shards that are not views (slabs
 // among them) before views, each group by address -- a slab's own device calls lock the slab, then
 // each of its views (dev_order_after_host), so every caller takes a slab's lock before its views'.
-inline void lock_order(std::vector<glint_shard*>& v) {
-  std::sort(v.begin(), v.end(), [](const glint_shard* a, const glint_shard* b) {
-    const bool va = a->slab != nullptr, vb = b->slab != nullptr;
-    return va != vb ? vb : a < b;
-  });
+inline bool locks_before(const glint_shard* a, const glint_shard* b) {
+  const bool va = a->slab != nullptr, vb = b->slab != nullptr;
+  return va != vb ? vb : a < b;
 }
+inline void lock_order(std::vector<glint_shard*>& v) { std::sort(v.begin(), v.end(), locks_before); }
 
 // ---- environment knobs ----------------------------------------------------------------------------
 // Test and policy overrides (GLINT_BINNED, GLINT_BIN_FRONT, ...; DESIGN.md §8 lists them) are read once per

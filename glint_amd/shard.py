@@ -196,10 +196,8 @@ class _Shard:
         self._check_dev(n, rows)
         if n == 0:  # names nothing (its data pointer may be NULL, which would name every row)
             return True
-        st = self._stream_of(rows)
-        check(getattr(self.lib, name + "_dev")(self.handle, rows.data_ptr(), n, *args, st), self.handle)
-        if sync:
-            self.sync(st)
+        rc = getattr(self.lib, name + "_dev")(self.handle, rows.data_ptr(), n, *args, self._stream_of(rows))
+        self._dev_done(rc, rows, sync)
         return True
 
     def fill(self, value, rows=None, sync: bool = True) -> bool:
@@ -302,6 +300,12 @@ class _Shard:
             raise ArrayIndexOutOfBoundsException(f"record {bad.value} is outside the partition", bad.value)
         check(rc, self.handle)
 
+    def _dev_done(self, rc: int, t, sync: bool) -> None:
+        """Ends a device-resident call enqueued on tensor ``t``'s stream: raise on ``rc``, then wait if ``sync``."""
+        check(rc, self.handle)
+        if sync:
+            self.sync(self._stream_of(t))
+
     @staticmethod
     def _stream_of(t) -> int:
         import torch
@@ -371,9 +375,7 @@ class PartialVector(_Shard):
             else:
                 rc = self.lib.glint_vec_push_dev(self.handle, keys.data_ptr(), values.data_ptr(), keys.numel(), flags,
                                                  self._stream_of(keys))
-            check(rc, self.handle)
-            if sync:
-                self.sync(self._stream_of(keys))
+            self._dev_done(rc, keys, sync)
             return True
         k = _host(keys, np.int64)
         v = _host(values, self.np_dtype)
@@ -391,9 +393,7 @@ class PartialVector(_Shard):
             self._check_dev(keys.numel(), keys, out=out)
             rc = self.lib.glint_vec_pull_dev(self.handle, keys.data_ptr(), out.data_ptr(), keys.numel(),
                                              self._stream_of(keys))
-            check(rc, self.handle)
-            if sync:
-                self.sync(self._stream_of(keys))
+            self._dev_done(rc, keys, sync)
             return out
         k = _host(keys, np.int64)
         res = self._host_out(out, k.shape)
@@ -445,9 +445,7 @@ class PartialMatrix(_Shard):
             else:
                 rc = self.lib.glint_mat_push_dev(self.handle, rows.data_ptr(), cols.data_ptr(), values.data_ptr(),
                                                  rows.numel(), flags, self._stream_of(rows))
-            check(rc, self.handle)
-            if sync:
-                self.sync(self._stream_of(rows))
+            self._dev_done(rc, rows, sync)
             return True
         r = _host(rows, np.int64)
         c = _host(cols, np.int32)
@@ -471,9 +469,7 @@ class PartialMatrix(_Shard):
             self._check_dev(n, rows, values=values, value_elems=n * self.cols)
             rc = self.lib.glint_mat_push_rows_dev(self.handle, rows.data_ptr(), values.data_ptr(), n, flags,
                                                   self._stream_of(rows))
-            check(rc, self.handle)
-            if sync:
-                self.sync(self._stream_of(rows))
+            self._dev_done(rc, rows, sync)
             return True
         r = _host(rows, np.int64).reshape(-1)
         v = _host(values, self.np_dtype).reshape(-1)
@@ -503,9 +499,7 @@ class PartialMatrix(_Shard):
             self._check_dev(n, rows)
             rc = self.lib.glint_mat_push_rows_axpy_dev(self.handle, rows.data_ptr(), n, coef.data_ptr(),
                                                        x.data_ptr(), q, flags, self._stream_of(rows))
-            check(rc, self.handle)
-            if sync:
-                self.sync(self._stream_of(rows))
+            self._dev_done(rc, rows, sync)
             return True
         r = _host(rows, np.int64).reshape(-1)
         cf = _host(coef, self.np_dtype)
@@ -538,9 +532,7 @@ class PartialMatrix(_Shard):
             rc = self.lib.glint_mat_push_rows_adagrad_dev(self.handle, state.handle, rows.data_ptr(),
                                                           grads.data_ptr(), n, float(lr), float(eps),
                                                           self._stream_of(rows))
-            check(rc, self.handle)
-            if sync:
-                self.sync(self._stream_of(rows))
+            self._dev_done(rc, rows, sync)
             return True
         r = _host(rows, np.int64).reshape(-1)
         g = _host(grads, self.np_dtype).reshape(-1)
@@ -572,9 +564,7 @@ class PartialMatrix(_Shard):
             self._check_dev(rows.numel(), rows, cols=cols, out=out)
             rc = self.lib.glint_mat_pull_dev(self.handle, rows.data_ptr(), cols.data_ptr(), out.data_ptr(),
                                              rows.numel(), self._stream_of(rows))
-            check(rc, self.handle)
-            if sync:
-                self.sync(self._stream_of(rows))
+            self._dev_done(rc, rows, sync)
             return out
         r = _host(rows, np.int64)
         c = _host(cols, np.int32)
@@ -595,9 +585,7 @@ class PartialMatrix(_Shard):
             self._check_dev(rows.numel(), rows, out=out, out_elems=rows.numel() * self.cols)
             rc = self.lib.glint_mat_pull_rows_dev(self.handle, rows.data_ptr(), out.data_ptr(), rows.numel(),
                                                   self._stream_of(rows))
-            check(rc, self.handle)
-            if sync:
-                self.sync(self._stream_of(rows))
+            self._dev_done(rc, rows, sync)
             return out
         r = _host(rows, np.int64).reshape(-1)
         res = self._host_out(out, (r.size, self.cols))
@@ -632,12 +620,12 @@ class PartialMatrix(_Shard):
                 k = int(cap)
             cols = torch.empty(k, dtype=torch.int32, device=rows.device)
             vals = torch.empty(k, dtype=self.torch_dtype, device=rows.device)
+            rc = N.GLINT_OK
             if k or cap is not None:
-                check(self.lib.glint_mat_pull_rows_sparse_dev(self.handle, rows.data_ptr(), n, indptr.data_ptr(),
-                                                              cols.data_ptr() if k else None,
-                                                              vals.data_ptr() if k else None, k, st), self.handle)
-            if sync:
-                self.sync(st)
+                rc = self.lib.glint_mat_pull_rows_sparse_dev(self.handle, rows.data_ptr(), n, indptr.data_ptr(),
+                                                             cols.data_ptr() if k else None,
+                                                             vals.data_ptr() if k else None, k, st)
+            self._dev_done(rc, rows, sync)
             return indptr, cols, vals
         r = _host(rows, np.int64).reshape(-1)
         indptr = np.empty(r.size + 1, np.int64)
@@ -685,9 +673,7 @@ class PartialMatrix(_Shard):
             self._check_dev(n, rows, out=out, out_elems=g * self.cols)
             rc = self.lib.glint_mat_pull_rows_sum_dev(self.handle, rows.data_ptr(), n, offsets.data_ptr(), g,
                                                       out.data_ptr(), self._stream_of(rows))
-            check(rc, self.handle)
-            if sync:
-                self.sync(self._stream_of(rows))
+            self._dev_done(rc, rows, sync)
             return out
         r = _host(rows, np.int64).reshape(-1)
         o = _host(offsets, np.int64).reshape(-1)
@@ -726,9 +712,7 @@ class PartialMatrix(_Shard):
             rc = self.lib.glint_mat_pull_rows_dot_dev(self.handle, rows.data_ptr(), n,
                                                       x.data_ptr() if x is not None else None, q, out.data_ptr(),
                                                       self._stream_of(rows))
-            check(rc, self.handle)
-            if sync:
-                self.sync(self._stream_of(rows))
+            self._dev_done(rc, rows, sync)
             return out
         r = _host(rows, np.int64).reshape(-1)
         q, shape = 1, (r.size,)
@@ -782,9 +766,7 @@ class PartialMatrix(_Shard):
             rc = self.lib.glint_mat_pull_pairs_dot_dev(self.handle, other.handle, rows.data_ptr(),
                                                        other_rows.data_ptr(), n, out.data_ptr(),
                                                        self._stream_of(rows))
-            check(rc, self.handle)
-            if sync:
-                self.sync(self._stream_of(rows))
+            self._dev_done(rc, rows, sync)
             return out
         if _is_torch_cuda(other_rows):
             raise TypeError("rows and other_rows: mixing host arrays and device tensors")
@@ -819,9 +801,7 @@ class PartialMatrix(_Shard):
             rc = self.lib.glint_mat_push_pairs_axpy_dev(self.handle, src.handle, rows.data_ptr(),
                                                         src_rows.data_ptr(), coef.data_ptr(), n, flags,
                                                         self._stream_of(rows))
-            check(rc, self.handle)
-            if sync:
-                self.sync(self._stream_of(rows))
+            self._dev_done(rc, rows, sync)
             return True
         if _is_torch_cuda(src_rows) or _is_torch_cuda(coef):
             raise TypeError("rows, src_rows and coef: mixing host arrays and device tensors")
@@ -864,10 +844,9 @@ class PartialMatrix(_Shard):
             q, shape = self._topk_shape(tuple(x.shape), k)
             rows = torch.empty(shape, dtype=torch.int64, device=x.device)
             vals = torch.empty(shape, dtype=self.torch_dtype, device=x.device)
-            check(self.lib.glint_mat_pull_topk_dev(self.handle, x.data_ptr(), q, k, rows.data_ptr(), vals.data_ptr(),
-                                                   self._stream_of(x)), self.handle)
-            if sync:
-                self.sync(self._stream_of(x))
+            rc = self.lib.glint_mat_pull_topk_dev(self.handle, x.data_ptr(), q, k, rows.data_ptr(), vals.data_ptr(),
+                                                  self._stream_of(x))
+            self._dev_done(rc, x, sync)
             return rows, vals
         x = _host(x, self.np_dtype)
         q, shape = self._topk_shape(x.shape, k)

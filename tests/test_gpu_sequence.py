@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from glint_amd import ArrayIndexOutOfBoundsException, PartialMatrix, RangePartition
+import glint_amd._native as N
 from axpy_cases import assert_bits
 import sequence_cases as S
 
@@ -38,6 +39,25 @@ def test_sequence_grid(gpu, geometry, dtype):
 @pytest.mark.parametrize("geometry", S.GEOMETRIES, ids=GEOMETRY_IDS)
 def test_sequence_strict(gpu, geometry, dtype):
     run_sequences(gpu, geometry, dtype, "strict")
+
+
+@pytest.fixture
+def pageable_staging(monkeypatch):
+    """GLINT_PINNED_STAGE_MAX=0 for the test (test_gpu_validation.test_pinned_stage_max_knob's knob), and
+    the default again for the tests after it."""
+    monkeypatch.setenv("GLINT_PINNED_STAGE_MAX", "0")
+    N.reload_env()
+    yield
+    monkeypatch.undo()
+    N.reload_env()
+
+
+@pytest.mark.parametrize("dtype,regime", [("float", "strict"), ("long", "grid")])
+def test_sequence_pageable_staging(gpu, pageable_staging, dtype, regime):
+    """The sequences with every host-pointer call staged from pageable memory, one copy per section, and
+    answered straight into the caller's arrays: the branch that only messages above the 2 MiB default
+    take."""
+    run_sequences(gpu, S.GEOMETRIES[1], dtype, regime)
 
 
 def test_sequence_on_a_side_stream(gpu):

@@ -6,6 +6,7 @@ GranularBigVectorSpec.scala:21, and the 79 999-record frame cap of the granular 
 One JSON line per (op, n) on stdout.
 
     python tools/host_latency.py [--reps R]
+    python tools/host_latency.py --rows [--reps R]    the row-family host calls on a matrix shard
 """
 import ctypes as C
 import json
@@ -36,6 +37,40 @@ def per_call(fn, reps):
         fn()
     return (time.perf_counter() - t0) / reps
 
+
+def rows_mode():
+    """The row-family host calls at 1000 rows of a 2^17 x 128 Float matrix shard: one JSON line each."""
+    size, cols, n, k = 1 << 17, 128, 1000, 16
+    m = C.c_void_p()
+    assert lib.glint_shard_create(0, N.GLINT_F32, 0, size, cols, C.byref(m)) == 0
+    rng = np.random.default_rng(42)
+    rows = rng.integers(0, size, n, dtype=np.int64)
+    vals = rng.random((n, cols), dtype=np.float32)
+    x = rng.random(cols, dtype=np.float32)
+    grp = np.arange(0, n + 1, 8, dtype=np.int64)
+    dots, sums = np.empty(n, np.float32), np.empty((grp.size - 1, cols), np.float32)
+    top_rows, top_vals = np.empty(k, np.int64), np.empty(k, np.float32)
+    calls = (
+        ("mat_push_rows", lambda: lib.glint_mat_push_rows(m, ptr(rows), ptr(vals), n, 0)),
+        ("mat_pull_rows_dot", lambda: lib.glint_mat_pull_rows_dot(m, ptr(rows), n, ptr(x), 1, ptr(dots))),
+        ("mat_pull_rows_sum", lambda: lib.glint_mat_pull_rows_sum(m, ptr(rows), n, ptr(grp), grp.size - 1, ptr(sums))),
+        ("mat_pull_topk", lambda: lib.glint_mat_pull_topk(m, ptr(x), 1, k, ptr(top_rows), ptr(top_vals))),
+        ("mat_pull_pairs_dot", lambda: lib.glint_mat_pull_pairs_dot(m, m, ptr(rows), ptr(rows), n, ptr(dots))),
+    )
+    for op, fn in calls:
+        def checked(fn=fn):
+            rc = fn()
+            assert rc == 0, rc
+
+        dt = per_call(checked, REPS)
+        print(json.dumps({"op": op, "records": n, "pinned_stage_max": os.environ.get("GLINT_PINNED_STAGE_MAX", "default"),
+                          "us_per_call": round(dt * 1e6, 2), "reps": REPS}), flush=True)
+    lib.glint_shard_destroy(m)
+
+
+if "--rows" in sys.argv:
+    rows_mode()
+    sys.exit(0)
 
 h = C.c_void_p()
 assert lib.glint_shard_create(0, N.GLINT_F64, 0, SIZE, 0, C.byref(h)) == 0
