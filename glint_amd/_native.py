@@ -71,6 +71,8 @@ SIGNATURES = {
     "glint_mat_pull_pairs_dot_dev": (_I, [_P, _P, _P, _P, _I64, _P, _P]),
     "glint_mat_push_pairs_axpy": (_I, [_P, _P, _P, _P, _P, _I64, _I]),
     "glint_mat_push_pairs_axpy_dev": (_I, [_P, _P, _P, _P, _P, _I64, _I, _P]),
+    "glint_mat_push_rows_grouped": (_I, [_P, _P, _I64, _P, _I64, _P, _P, _I]),
+    "glint_mat_push_rows_grouped_dev": (_I, [_P, _P, _I64, _P, _I64, _P, _P, _I, _P]),
     "glint_mat_pull_topk": (_I, [_P, _P, _I64, _I64, _P, _P]),
     "glint_mat_pull_topk_dev": (_I, [_P, _P, _I64, _I64, _P, _P, _P]),
     "glint_shard_last_error": (_I, [_P, C.POINTER(_I64)]),

@@ -198,6 +198,49 @@ class BigMatrix(_InitMixin):
                 sh.updateRowsAxpy(rows[idx], coef[idx], x, deterministic=deterministic)
         return True
 
+    def pushGroups(self, rows, offsets, values, weights=None, deterministic: bool = False) -> bool:
+        """Grouped row push (an extension), the write side of ``pullSum``: ``offsets`` has g + 1 entries,
+        non-decreasing from 0 to len(rows); every row of ``rows[offsets[k]:offsets[k+1]]`` += ``values[k]``
+        -- times ``weights[i]`` for record i when ``weights`` (n,) is given -- in the caller's order.
+        ``values`` is (g, cols) or flat. It is ``pushRows`` of the n expanded rows without building or
+        sending them. ``offsets``, the shapes and -- by the partitioner -- every row are validated before
+        any shard is called. Records are bucketed by partition as ``pushRows``; each non-empty partition
+        gets one PartialMatrix.updateRowsGrouped over the sub-groups of its own rows, in the caller's
+        order: only the groups that have a record in that partition are sent, their value rows compacted.
+        A row lives in one partition, so a row's additions run in the caller's order under any
+        partitioning.
+
+        Bytes sent to a partition with n_p of the records in g_p of the groups: ``8 n_p + 8 (g_p + 1) +
+        g_p * cols * itemsize``, plus ``n_p * itemsize`` with ``weights`` -- against ``8 n_p + n_p * cols *
+        itemsize`` for ``pushRows`` of the expanded rows."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        if offsets.size < 1 or offsets[0] != 0 or offsets[-1] != rows.size or (np.diff(offsets) < 0).any():
+            raise ValueError("offsets must be non-decreasing from 0 to len(rows)")
+        g = offsets.size - 1
+        dtype = self.shards[0].np_dtype
+        values = np.ascontiguousarray(values, dtype=dtype)
+        if values.size != g * self.cols:
+            raise ValueError(f"values: {values.size} elements, expected {g} groups x {self.cols} columns")
+        values = values.reshape(g, self.cols)
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, dtype=dtype).reshape(-1)
+            if weights.size != rows.size:
+                raise ValueError(f"weights: {weights.size} values, expected {rows.size}")
+        owner = self.partitioner.partition_indices(rows)
+        order, off = bucket(owner, len(self.shards))
+        group = np.repeat(np.arange(g, dtype=np.int64), np.diff(offsets))  # the group of every record
+        for p, sh in enumerate(self.shards):
+            idx = order[off[p]:off[p + 1]]  # caller's order, so its groups are non-decreasing
+            if idx.size:
+                counts = np.bincount(group[idx], minlength=g)
+                has = np.flatnonzero(counts)  # the groups with a record here, ascending
+                sub = np.zeros(has.size + 1, dtype=np.int64)
+                np.cumsum(counts[has], out=sub[1:])
+                sh.updateRowsGrouped(rows[idx], sub, values[has], None if weights is None else weights[idx],
+                                     deterministic=deterministic)
+        return True
+
     def pushAdagrad(self, state: "BigMatrix", rows, grads, lr: float, eps: float = 1e-10) -> bool:
         """Adagrad row push (an extension): this matrix holds the weights and ``state`` -- a BigMatrix
         with the same partitioner, rows, cols and dtype -- the accumulated squared gradients. ``grads`` is

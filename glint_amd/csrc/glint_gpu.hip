@@ -1152,6 +1152,7 @@ void free_shard(glint_shard* s) {
     if (s->d_ctl) (void)hipFree(s->d_ctl);
     if (s->d_scratch) (void)hipFree(s->d_scratch);
     if (s->d_det) (void)hipFree(s->d_det);
+    if (s->d_grp) (void)hipFree(s->d_grp);
     if (s->det_stream) {
       (void)hipStreamSynchronize(s->det_stream);
       (void)hipStreamDestroy(s->det_stream);
@@ -1312,6 +1313,18 @@ inline int push_adagrad_args(const glint_shard* w, const glint_shard* h, const v
   if (n < 0 || n >= ((i64)1 << 32) - kSortTile) return GLINT_EINVAL;
   if (n > 0 && (!rows || !grads)) return GLINT_EINVAL;
   if (lr != lr || !(eps >= 0)) return GLINT_EINVAL;
+  return GLINT_OK;
+}
+
+// argument checks of glint_mat_push_rows_grouped / _dev: glint_mat_push_rows's shard, flags and record count,
+// a 31-bit group count, the arrays present when they have elements (grp_ptr always: it has g + 1); coef may
+// be NULL
+inline int push_grouped_args(const glint_shard* s, const void* rows, int64_t n, const void* grp_ptr, int64_t g,
+                             const void* vals, int flags) {
+  if (!s || s->part.cols == 0) return GLINT_EINVAL;
+  if (n < 0 || n >= ((i64)1 << 32) - kSortTile || g < 0 || g >= ((i64)1 << 31)) return GLINT_EINVAL;
+  if (flags & ~(GLINT_PUSH_DETERMINISTIC | GLINT_PUSH_UNORDERED)) return GLINT_EINVAL;
+  if (!grp_ptr || (n > 0 && !rows) || (g > 0 && !vals)) return GLINT_EINVAL;
   return GLINT_OK;
 }
 
@@ -1546,7 +1559,7 @@ std::atomic<unsigned> g_env_gen{1};
 
 extern "C" {
 
-int glint_version(void) { return 1000; }  // 0.10.0: glint_shard_fill / glint_shard_init_uniform / _dev
+int glint_version(void) { return 1100; }  // 0.11.0: glint_mat_push_rows_grouped / _dev
 
 int glint_reload_env(void) {
   g_env_gen.fetch_add(1, std::memory_order_acq_rel);
@@ -1957,6 +1970,15 @@ int glint_mat_push_rows_axpy_dev(glint_shard_t s, const int64_t* rows, int64_t n
   if (args_rc == GLINT_OK && n == 0) return GLINT_OK;
   return dev_call(s, args_rc, stream, [&](hipStream_t st) -> int {
     GLINT_DISPATCH(s->dtype, push_rows_axpy, s, (const i64*)rows, n, coef, x, q, flags, st);
+  });
+}
+
+int glint_mat_push_rows_grouped_dev(glint_shard_t s, const int64_t* rows, int64_t n, const int64_t* grp_ptr,
+                                    int64_t g, const void* vals, const void* coef, int flags, void* stream) {
+  const int args_rc = push_grouped_args(s, rows, n, grp_ptr, g, vals, flags);
+  return dev_call(s, args_rc, stream, [&](hipStream_t st) -> int {
+    GLINT_DISPATCH(s->dtype, push_rows_grouped, s, (const i64*)rows, n, (const i64*)grp_ptr, g, vals, coef, flags,
+                   st);
   });
 }
 
@@ -2628,7 +2650,7 @@ struct HostIn {  // one host array a call stages
 // the `extra` bytes behind them and, when the call is small enough, the pinned host block that mirrors
 // the scratch (pinned = true)
 struct Staged {
-  char* p[3] = {nullptr, nullptr, nullptr};
+  char* p[4] = {nullptr, nullptr, nullptr, nullptr};
   char* extra = nullptr;
   bool pinned = false;
   size_t in_bytes = 0;  // bytes of the staged input sections (the pinned block's first part)
@@ -2687,7 +2709,7 @@ struct HostBack {
 };
 
 // The staged part of a host-pointer call, on a shard entered and locked: the `in` sections are staged
-// (at most three) with `extra` device bytes behind them, body(staged, stream, back) launches on the
+// (at most four) with `extra` device bytes behind them, body(staged, stream, back) launches on the
 // shard's stream and names up to two copies back, and the call ends synchronised with the error state
 // read (finish). The body's launches record rejected records as the call's own (d_err_host). Any
 // failure once something is staged drains the stream first (launch_failed).
@@ -2978,6 +3000,30 @@ int glint_mat_push_rows_axpy(glint_shard_t s, const int64_t* rows, int64_t n, co
                     {x, (size_t)q * (size_t)s->part.cols * s->vsize}},
                    0, [&](const Staged& st, hipStream_t stream, HostBack*) -> int {
                      GLINT_DISPATCH(s->dtype, push_rows_axpy, s, (const i64*)st.p[0], n, st.p[1], st.p[2], q,
+                                    flags | kPushHostSequential, stream);
+                   });
+}
+
+// glint_mat_push_rows_grouped: grp_ptr and every row are checked before anything is staged (a rejected
+// message applies nothing), then rows, grp_ptr, coef (when given) and vals are staged in one block --
+// n * 8 + (g + 1) * 8 + n + g * cols values, never n * cols; every section starts 256-B aligned, so vals
+// takes the 16-B path when cols allow -- and the push runs on the shard's stream in message order
+// (kPushHostSequential). Nothing comes back but the error state.
+int glint_mat_push_rows_grouped(glint_shard_t s, const int64_t* rows, int64_t n, const int64_t* grp_ptr, int64_t g,
+                                const void* vals, const void* coef, int flags) {
+  if (int rc = push_grouped_args(s, rows, n, grp_ptr, g, vals, flags)) return rc;
+  if (grp_ptr[0] != 0 || grp_ptr[g] != n) return GLINT_EINVAL;
+  for (i64 k = 0; k < g; ++k)
+    if (grp_ptr[k + 1] < grp_ptr[k]) return GLINT_EINVAL;
+  if (n == 0) return GLINT_OK;
+  return host_call(s, s, {rows, nullptr, n}, false,
+                   {{rows, (size_t)n * 8},
+                    {grp_ptr, (size_t)(g + 1) * 8},
+                    {coef, coef ? (size_t)n * s->vsize : 0},
+                    {vals, (size_t)g * (size_t)s->part.cols * s->vsize}},
+                   0, [&](const Staged& st, hipStream_t stream, HostBack*) -> int {
+                     GLINT_DISPATCH(s->dtype, push_rows_grouped, s, (const i64*)st.p[0], n, (const i64*)st.p[1], g,
+                                    (const void*)st.p[3], coef ? (const void*)st.p[2] : nullptr,
                                     flags | kPushHostSequential, stream);
                    });
 }

@@ -74,6 +74,9 @@ struct glint_shard {
   size_t scratch_bytes = 0;
   void* d_det = nullptr;
   size_t det_bytes = 0;
+  // grouped row push (glint_rowgroup.hip): one u32 group id per record, written in front of the fold
+  void* d_grp = nullptr;
+  size_t grp_bytes = 0;
   // the deterministic tail folds the chains of its hottest elements on a second stream while the rest
   // of the push is sorted (glint_sort.hip); created on first use
   hipStream_t det_stream = nullptr;
@@ -527,6 +530,15 @@ int pull_pairs_dot(glint_shard* a, glint_shard* b, const i64* rows_a, const i64*
 template <typename V>
 int push_pairs_axpy(glint_shard* dst, glint_shard* src, const i64* rows_dst, const i64* rows_src, const void* coef,
                     i64 n, int flags, hipStream_t st);
+// grouped row push (glint_rowgroup.hip), instantiated for the same V: row rows[i] += vals[k] (g x cols, dense),
+// k the group of record i under grp_ptr (g + 1 entries, each clamped to [0, n] by the kernel; a record that
+// no group covers contributes nothing), times coef[i] when coef is given (n values; the product rounded
+// before the add), device pointers, in the order include/glint_gpu.h fixes; rows outside the partition are
+// skipped and recorded in err_of(s). The front end's launches, one launch that writes every record's group id
+// into s->d_grp and one fold launch on st, no host synchronisation.
+template <typename V>
+int push_rows_grouped(glint_shard* s, const i64* rows, i64 n, const i64* grp_ptr, i64 g, const void* vals,
+                      const void* coef, int flags, hipStream_t st);
 // shard fill and uniform init (glint_init.hip), for every dtype: the named rows' elements = the low vsize
 // bytes of `a` (uniform false), or the values include/glint_gpu.h fixes for (seed, global row, column)
 // with lo and w as bits of the shard's type in `a` and `b` (Float / Double only). list false names every

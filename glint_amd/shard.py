@@ -509,6 +509,64 @@ class PartialMatrix(_Shard):
                                                 flags), self.handle)
         return True
 
+    def updateRowsGrouped(self, rows, offsets, values, weights=None, deterministic: bool = False,
+                          sync: bool = True, unordered: bool = False) -> bool:
+        """Grouped row push (an extension; glint_mat_push_rows_grouped*), the write side of ``getRowsSum``:
+        ``offsets`` has g + 1 int64 entries, non-decreasing from 0 to len(rows), group k is
+        ``rows[offsets[k]:offsets[k+1]]``, and every row of group k += ``values[k]`` -- times
+        ``weights[i]`` for record i when ``weights`` is given. ``values`` is (g, cols) or flat, ``weights``
+        (n,) or None. It is ``updateRows`` with ``values[group of i]`` (``weights[i] * values[group of i]``,
+        the product rounded before the add: no fused multiply-add) as record i's row, rounding for
+        rounding, without those n rows ever being built or sent; without ``weights`` the value row's bits
+        are added as they are. Int/Long wrap. Order and errors as ``updateRows``: host arrays keep the push
+        order for Float/Double unless ``unordered`` and reject a message with a row outside the partition
+        before anything is applied; device tensors keep the order with ``deterministic``, skip such a row
+        and raise at the sync, and their ``offsets`` are clamped to [0, len(rows)] by the kernel (a record
+        that no group covers is not applied)."""
+        flags = _flags(deterministic, unordered)
+        dev = _is_torch_cuda(rows)
+        for name, t in (("offsets", offsets), ("values", values)) + ((("weights", weights),) if weights is not None
+                                                                     else ()):
+            if _is_torch_cuda(t) != dev:
+                raise TypeError(f"rows and {name}: mixing host arrays and device tensors")
+        if dev:
+            import torch
+            n = rows.numel()
+            if offsets.dtype != torch.int64 or not offsets.is_contiguous() or offsets.device != rows.device \
+                    or offsets.numel() < 1:
+                raise TypeError("offsets: expected a contiguous int64 CUDA tensor of g + 1 entries on rows' device")
+            g = offsets.numel() - 1
+            for name, t, want in (("values", values, g * self.cols), ("weights", weights, n)):
+                if t is None:
+                    continue
+                if t.dtype != self.torch_dtype or not t.is_contiguous() or t.device != rows.device:
+                    raise TypeError(f"{name}: expected a contiguous {self.torch_dtype} CUDA tensor on rows' device")
+                if t.numel() != want:
+                    raise ValueError(f"{name}: {t.numel()} elements, expected {want}")
+            self._check_dev(n, rows)
+            rc = self.lib.glint_mat_push_rows_grouped_dev(
+                self.handle, rows.data_ptr(), n, offsets.data_ptr(), g, values.data_ptr() if g else None,
+                weights.data_ptr() if weights is not None else None, flags, self._stream_of(rows))
+            self._dev_done(rc, rows, sync)
+            return True
+        r = _host(rows, np.int64).reshape(-1)
+        o = _host(offsets, np.int64).reshape(-1)
+        if o.size < 1:
+            raise ValueError("offsets needs g + 1 entries")
+        g = o.size - 1
+        v = _host(values, self.np_dtype).reshape(-1)
+        if v.size != g * self.cols:
+            raise ValueError(f"values: {v.size} elements, expected {g} groups x {self.cols} columns")
+        w = None
+        if weights is not None:
+            w = _host(weights, self.np_dtype).reshape(-1)
+            if w.size != r.size:
+                raise ValueError(f"weights: {w.size} values, expected {r.size}")
+        check(self.lib.glint_mat_push_rows_grouped(self.handle, r.ctypes.data, r.size, o.ctypes.data, g,
+                                                   v.ctypes.data if g else None,
+                                                   w.ctypes.data if w is not None else None, flags), self.handle)
+        return True
+
     def updateRowsAdagrad(self, state: "PartialMatrix", rows, grads, lr: float, eps: float = 1e-10,
                           sync: bool = True) -> bool:
         """Adagrad row push (an extension; glint_mat_push_rows_adagrad*): this shard holds the weights and

@@ -397,6 +397,41 @@ int glint_mat_pull_pairs_dot(glint_shard_t a, glint_shard_t b, const int64_t* ro
 int glint_mat_push_pairs_axpy(glint_shard_t dst, glint_shard_t src, const int64_t* rows_dst,
                               const int64_t* rows_src, const void* coef, int64_t n, int flags);
 
+/* Grouped row push (an extension: the reference has no such message): the write side of
+ * glint_mat_pull_rows_sum -- the backward pass of an embedding bag. The caller names n rows in g groups and
+ * sends ONE value row per group; every record adds its group's row, optionally times a coefficient of its
+ * own, so that g x cols values cross the link instead of the n x cols expanded rows glint_mat_push_rows
+ * would need.
+ *   grp_ptr   g + 1 int64, non-decreasing, grp_ptr[0] = 0 and grp_ptr[g] = n: group k is
+ *             rows[grp_ptr[k] .. grp_ptr[k+1]) (glint_mat_pull_rows_sum's rule);
+ *   vals      g x cols values of the shard's type, dense row-major (NO pitch): one row per group;
+ *   coef      n values of the shard's type, one per record; may be NULL.
+ * For i in push order, with k the group of record i, for c in [0, cols):
+ *   data[l(rows[i])][c] = data[l(rows[i])][c] + t_i[c].
+ * With coef == NULL, t_i[c] = vals[k][c]: the stored bits are used and no multiply is performed. Otherwise
+ * t_i[c] = coef[i] * vals[k][c], the product rounded before the add (no fused multiply-add). All arithmetic
+ * is in the shard's type; Int/Long wrap. The call is therefore glint_mat_push_rows(shard, rows, expanded, n,
+ * flags) with expanded[i] = t_i, rounding for rounding. That order is a function of the inputs only --
+ * never of pointer alignment, g, how records are batched over lanes, or the grid. Subnormals are kept;
+ * infinities and NaN follow IEEE (inf * 0 is NaN; a NaN's payload and sign are unspecified). Only `cols`
+ * elements of a row are read and written, never the pitch padding. A row may occur several times in a
+ * group, and in several groups; an empty group contributes nothing.
+ * Flags, order and sizes are glint_mat_push_rows's: only GLINT_PUSH_DETERMINISTIC and GLINT_PUSH_UNORDERED
+ * are accepted; Float/Double sums of repeated rows keep the push order unless GLINT_PUSH_UNORDERED is given;
+ * a row that occurs once is bit-exact in every mode; Int/Long are exact in every mode. Every row is checked
+ * before anything is applied: on a row outside the partition nothing is applied (GLINT_EOUTOFRANGE, the
+ * record's index in glint_shard_last_error). A slab with views is refused, as for every host-pointer call.
+ * GLINT_EINVAL: a NULL or vector shard; n < 0, n >= 2^32 - 2048, g < 0, g >= 2^31; any other flag; a NULL
+ * grp_ptr; NULL rows with n > 0; NULL vals with g > 0; and -- in this host call only, before anything is
+ * staged -- a grp_ptr that breaks the rule above. n == 0 launches nothing and returns GLINT_OK. Staged to
+ * the device in one block: rows, grp_ptr, coef when given, and vals (which starts 16-B aligned there) --
+ * 8 n + 8 (g + 1) + n * sizeof V + g * cols * sizeof V bytes; nothing of size n x cols is ever staged, and
+ * nothing is copied back. Device scratch: the row push's, and one 32-bit group id per record. Kernel timing:
+ * the front end counts as glint_mat_push_rows's does (the launch that writes the group ids belongs to it) and
+ * the one fold launch under GLINT_K_PUSH_ROWS. */
+int glint_mat_push_rows_grouped(glint_shard_t shard, const int64_t* rows, int64_t n, const int64_t* grp_ptr,
+                                int64_t g, const void* vals, const void* coef, int flags);
+
 /* Top-k row pull (an extension: the reference has no such message): for each of q query vectors, the k
  * rows of the shard that score highest against it -- nearest-row search, candidate retrieval -- answered
  * with q x k (row, score) pairs whatever the shard's size.
@@ -532,6 +567,22 @@ int glint_mat_pull_pairs_dot_dev(glint_shard_t a, glint_shard_t b, const int64_t
  * GLINT_EINVAL for either shard. */
 int glint_mat_push_pairs_axpy_dev(glint_shard_t dst, glint_shard_t src, const int64_t* rows_dst,
                                   const int64_t* rows_src, const void* coef, int64_t n, int flags, void* stream);
+
+/* glint_mat_push_rows_grouped, device-resident: the same contributions, stream-ordered on `stream` with no
+ * host synchronisation (a device call like glint_mat_push_rows_dev). A row outside the partition is skipped
+ * and reported by glint_shard_sync (the lowest such record index); the other records are applied. Int/Long
+ * sums are exact. Float/Double: every contribution is bit-exact in every mode, and a row that occurs once
+ * in the push is bit-exact; sums of repeated rows keep the push order with GLINT_PUSH_DETERMINISTIC, else
+ * runs longer than 128 records are split and their partial sums added with atomics.
+ * grp_ptr is not checked on the host: the kernel clamps every value it reads to [0, n]. If the clamped
+ * array c is non-decreasing, record i belongs to the group k with c[k] <= i < c[k+1], or to none; a record
+ * that no group covers contributes nothing -- the row's bits are as if the record were absent -- and is not
+ * reported. If the clamped array decreases somewhere, which group a record gets is unspecified; the kernel
+ * still never reads outside grp_ptr[0 .. g], the g rows of vals, rows or coef.
+ * vals is read by 16 B when it is 16-B aligned and cols * sizeof V is a multiple of 16, else element by
+ * element; coef element by element: the same bits either way. */
+int glint_mat_push_rows_grouped_dev(glint_shard_t shard, const int64_t* rows, int64_t n, const int64_t* grp_ptr,
+                                    int64_t g, const void* vals, const void* coef, int flags, void* stream);
 
 /* glint_vec_push_dev / glint_mat_push_dev behind a device-side gate: the push is enqueued at once,
  * and when it runs it applies NOTHING if the 64-bit device word *gate is nonzero (a route status word,
@@ -708,7 +759,8 @@ enum glint_kernel_id {
   GLINT_K_PUSH_ORDERED = 7, /* the order-preserving push of message-sized pushes (one launch) */
   /* the per-destination fold of a whole-row push (glint_mat_push_rows*), and the one fold launch of a
    * non-empty Adagrad row push (glint_mat_push_rows_adagrad*), recorded on its weights shard only. Also
-   * the one launch of a shard fill or uniform init (glint_shard_fill*, glint_shard_init_uniform*) */
+   * the one launch of a shard fill or uniform init (glint_shard_fill*, glint_shard_init_uniform*), and the
+   * one fold launch of a non-empty grouped row push (glint_mat_push_rows_grouped*) */
   GLINT_K_PUSH_ROWS = 8,
   /* the sparse row pull (glint_mat_pull_rows_sparse*): its emit kernel, and under the same id its
    * count kernel and the launches of its scan, so the sum is the pull's whole device time */

@@ -5,6 +5,7 @@ the JNI shim sees. One JSON line per measurement on stdout.
 
     python tools/measure_paths.py [--quick] [--sparse] [--rowsum] [--dot] [--axpy [--out FILE]] [--topk [--out FILE]]
                                   [--adagrad [--out FILE]] [--pairs [--out FILE]] [--init [--out FILE]]
+                                  [--groups [--out FILE]]
 
 --sparse runs only the sparse-row-pull leg (dense getRows against getRowsSparse on a cfg5 shard).
 --rowsum runs only the grouped row-sum leg (getRowsSum against a dense row pull plus a reduction by the
@@ -25,6 +26,9 @@ its lines to profiles/pairs/pairs.jsonl (or FILE).
 against glint_shard_zero's memset, and against generating the table by the caller plus a row push, on a
 cfg5-shaped Double and a word2vec-shaped Float shard) and appends its lines to profiles/init/init.jsonl (or
 FILE).
+--groups runs only the grouped row push leg (updateRowsGrouped against expanding the value rows by the caller
+plus a row push, on a word2vec-shaped Float and a cfg5-shaped Double shard) and appends its lines to
+profiles/groups/groups.jsonl (or FILE).
 """
 import ctypes as C
 import json
@@ -751,6 +755,141 @@ def pairs_leg(rng, out_path):
         torch.cuda.empty_cache()
 
 
+def groups_leg(rng, out_path):
+    """Grouped row push on a word2vec / CBOW-shaped 2^17 x 128 Float shard and cfg5's per-GPU 2^17 x 512
+    Double shard: g = 2^12 and 2^14 groups of 8 rows (n = 2^15 and 2^17 records), rows Zipf(1.0), value rows
+    1e-3 x standard normal, with and without per-record weights. The call under test runs on one shard
+    (s1), the baseline -- what a caller does today -- on another (s2) with the same content, on alternating
+    rounds of one process; the baseline never runs the code under test.
+    Device baseline: values.index_select(0, group), times the weights when weighted, in torch, then
+    glint_mat_push_rows_dev. Host baseline: np.repeat, times the weights, then glint_mat_push_rows; wall
+    clock. Device legs: a HIP event pair around each call; the fold alone by its prof id, and its
+    algorithmic bytes over that time as a fraction of the HBM peak (the g x cols value rows are re-read from
+    cache, so those bytes overstate HBM traffic). After each case the two shards are compared: the default
+    order flags split long runs, so they agree to rounding, not bit for bit. One JSON line per (shape, g,
+    weighted), also appended to out_path."""
+    shard_rows, rounds, hbm_peak_gbs, per = 1 << 17, 5, 8000.0, 8
+    part = glint_amd.RangePartition(0, 0, shard_rows)
+    all_rows = torch.arange(shard_rows, dtype=torch.int64, device=dev)
+
+    def ev_ms(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b)
+
+    def wall_ms(fn):
+        t0 = time.perf_counter()
+        fn()
+        return (time.perf_counter() - t0) * 1e3
+
+    def stats(ms):
+        return {"mean": float(np.mean(ms)), "min": float(np.min(ms)), "max": float(np.max(ms))}
+
+    def rounds_of(legs):
+        """legs: name -> (timer, fn), run in the order given inside every round; round 0 warms up."""
+        t = {k: [] for k in legs}
+        for rnd in range(rounds + 1):
+            for k, (timer, fn) in legs.items():
+                torch.cuda.synchronize()
+                v = timer(fn)
+                if rnd:
+                    t[k].append(v)
+        return {k: stats(v) for k, v in t.items()}
+
+    Path(out_path).parent.mkdir(parents=True, exist_ok=True)
+    for dtype, cols in (("float", 128), ("double", 512)):
+        s1, s2 = (glint_amd.PartialMatrix(part, cols, dtype, 0) for _ in range(2))
+        tdt, npd, vs = s1.torch_dtype, s1.np_dtype, np.dtype(s1.np_dtype).itemsize
+        tol = 1e-10 if dtype == "double" else 1e-2
+        v = torch.randn((shard_rows, cols), dtype=tdt, device=dev)
+        s1.updateRows(all_rows, v)
+        s2.updateRows(all_rows, v)
+        del v
+        for g in (1 << 12, 1 << 14):
+            n = g * per
+            rows = zipf_keys(rng, shard_rows, n, 1.0)
+            offsets = np.arange(g + 1, dtype=np.int64) * per
+            group = np.repeat(np.arange(g, dtype=np.int64), per)
+            vals = (rng.standard_normal((g, cols)) * 1e-3).astype(npd)
+            wts = rng.random(n).astype(npd)
+            d_rows, d_off, d_group, d_vals, d_wts = (torch.from_numpy(x).to(dev) for x in (rows, offsets, group, vals, wts))
+            distinct = int(np.unique(rows).size)
+            for weighted in (False, True):
+                pw, dw = (wts.ctypes.data, d_wts.data_ptr()) if weighted else (None, None)
+
+                def dev_grouped():
+                    assert lib.glint_mat_push_rows_grouped_dev(s1.handle, d_rows.data_ptr(), n, d_off.data_ptr(), g,
+                                                               d_vals.data_ptr(), dw, 0, stream) == 0
+
+                def dev_base():
+                    T = d_vals.index_select(0, d_group)
+                    if weighted:
+                        T = d_wts[:, None] * T
+                    assert lib.glint_mat_push_rows_dev(s2.handle, d_rows.data_ptr(), T.data_ptr(), n, 0, stream) == 0
+
+                def host_grouped():
+                    assert lib.glint_mat_push_rows_grouped(s1.handle, rows.ctypes.data, n, offsets.ctypes.data, g,
+                                                           vals.ctypes.data, pw, 0) == 0
+
+                def host_base():
+                    T = np.repeat(vals, per, axis=0)
+                    if weighted:
+                        T = wts[:, None] * T
+                    assert lib.glint_mat_push_rows(s2.handle, rows.ctypes.data, T.ctypes.data, n, 0) == 0
+
+                m = rounds_of({"host_base": (wall_ms, host_base), "host_grouped": (wall_ms, host_grouped),
+                               "dev_base": (ev_ms, dev_base), "dev_grouped": (ev_ms, dev_grouped)})
+                for sh in (s1, s2):
+                    lib.glint_prof_reset(sh.handle)
+                    lib.glint_prof_enable(sh.handle, 1)
+                for _ in range(3):  # (both legs: the two shards stay comparable)
+                    dev_grouped()
+                    dev_base()
+                torch.cuda.synchronize()
+                k_ms = kernel_ms(s1.handle, N.GLINT_K_PUSH_ROWS)
+                base_k_ms = kernel_ms(s2.handle, N.GLINT_K_PUSH_ROWS)  # the row push's fold over the expanded rows
+                for sh in (s1, s2):
+                    lib.glint_prof_enable(sh.handle, 0)
+                for sh in (s1, s2):
+                    sh.sync(stream)
+                g1, g2 = s1.getRows(all_rows), s2.getRows(all_rows)
+                diff = ((g1 - g2).abs() / g2.abs().clamp_min(1.0)).max().item()
+                del g1, g2
+                assert diff < tol, diff  # sums of up to thousands of terms per hot row, in other orders
+                idx_bytes = n * 4 + (g + 1) * 8 + (n * vs if weighted else 0)
+                k_bytes = (n + 2 * distinct) * cols * vs + idx_bytes
+                link = n * 8 + (g + 1) * 8 + (n * vs if weighted else 0) + g * cols * vs
+                line = dict(
+                    op="mat_push_rows_grouped", dtype=dtype, weighted=weighted, pattern="rows zipf1.0, groups of 8",
+                    shape=[shard_rows, cols], groups=g, records=n, distinct_rows=distinct, rounds=rounds,
+                    host_grouped_ms=m["host_grouped"], host_baseline_ms=m["host_base"],
+                    host_speedup=m["host_base"]["mean"] / m["host_grouped"]["mean"],
+                    host_grouped_bytes_over_link=link, host_baseline_bytes_over_link=n * 8 + n * cols * vs,
+                    dev_grouped_ms=m["dev_grouped"], dev_baseline_ms=m["dev_base"],
+                    dev_speedup=m["dev_base"]["mean"] / m["dev_grouped"]["mean"],
+                    fold_kernel_ms=k_ms, fold_bytes=k_bytes, fold_GBps=k_bytes / (k_ms * 1e-3) / 1e9,
+                    fold_fraction_of_hbm_peak=k_bytes / (k_ms * 1e-3) / 1e9 / hbm_peak_gbs, hbm_peak_GBps=hbm_peak_gbs,
+                    baseline_fold_kernel_ms=base_k_ms, max_relative_difference=diff,
+                    note="baseline = the caller expands values to n x cols (index_select in torch on the device, "
+                         "np.repeat on the host), times the weights when weighted, then glint_mat_push_rows*. host_*: C "
+                         "calls on pageable numpy arrays, synchronous, wall ms. dev_*: one HIP event pair per call "
+                         "(front end and fold), default order flags. Legs alternate inside each of `rounds` rounds "
+                         "after one warm-up round. fold_kernel_ms: the fold alone (glint_prof, GLINT_K_PUSH_ROWS on "
+                         "the shard under test); baseline_fold_kernel_ms: the row push's fold over the expanded rows, the "
+                         "same id on the baseline's shard. fold_bytes = (records + 2 * distinct_rows) * cols * sizeof V plus "
+                         "the per-record index, the group pointer and the weights; the g x cols value rows are "
+                         "re-read from cache, so this overstates HBM traffic")
+                emit(**line)
+                with open(out_path, "a") as f:
+                    f.write(json.dumps(line) + "\n")
+        for sh in (s1, s2):
+            sh.destroy()
+        torch.cuda.empty_cache()
+
+
 def init_leg(rng, out_path):
     """Shard fill and uniform init on cfg5's per-GPU shard (2^17 x 512 Double) and a word2vec-shaped one
     (2^17 x 128 Float): the whole shard, and a list of 2^14 distinct rows in random order. The calls under
@@ -1026,6 +1165,11 @@ def main():
         out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
             str(Path(__file__).resolve().parent.parent / "profiles" / "adagrad" / "adagrad_push.jsonl")
         adagrad_leg(np.random.default_rng(42), out)
+        return
+    if "--groups" in sys.argv:
+        out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
+            str(Path(__file__).resolve().parent.parent / "profiles" / "groups" / "groups.jsonl")
+        groups_leg(np.random.default_rng(42), out)
         return
     if "--pairs" in sys.argv:
         out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
