@@ -67,6 +67,9 @@ SIGNATURES = {
     "glint_mat_push_rows_axpy_dev": (_I, [_P, _P, _I64, _P, _P, _I64, _I, _P]),
     "glint_mat_push_rows_adagrad": (_I, [_P, _P, _P, _P, _I64, C.c_double, C.c_double]),
     "glint_mat_push_rows_adagrad_dev": (_I, [_P, _P, _P, _P, _I64, C.c_double, C.c_double, _P]),
+    "glint_mat_push_rows_adam": (_I, [_P, _P, _P, _P, _I64, C.c_double, C.c_double, C.c_double, C.c_double, _I64]),
+    "glint_mat_push_rows_adam_dev": (_I, [_P, _P, _P, _P, _I64, C.c_double, C.c_double, C.c_double, C.c_double,
+                                          _I64, _P]),
     "glint_mat_pull_pairs_dot": (_I, [_P, _P, _P, _P, _I64, _P]),
     "glint_mat_pull_pairs_dot_dev": (_I, [_P, _P, _P, _P, _I64, _P, _P]),
     "glint_mat_push_pairs_axpy": (_I, [_P, _P, _P, _P, _P, _I64, _I]),

@@ -27,7 +27,7 @@ HIP_SOURCES = [CSRC / "glint_gpu.hip", CSRC / "glint_sort.hip", CSRC / "glint_ro
                CSRC / "glint_exchange.hip", CSRC / "glint_rows.hip", CSRC / "glint_sparse.hip",
                CSRC / "glint_rowsum.hip", CSRC / "glint_rowdot.hip", CSRC / "glint_rowaxpy.hip",
                CSRC / "glint_topk.hip", CSRC / "glint_rowadagrad.hip", CSRC / "glint_pairs.hip",
-               CSRC / "glint_init.hip", CSRC / "glint_rowgroup.hip"]
+               CSRC / "glint_init.hip", CSRC / "glint_rowgroup.hip", CSRC / "glint_rowadam.hip"]
 # plain C++: the push planners, the top-k pull's level plan and the uniform init's value contract
 PLAN_HEADERS = [CSRC / "glint_push_plan.h", CSRC / "glint_bin_plan.h", CSRC / "glint_topk_plan.h",
                 CSRC / "glint_init_plan.h"]

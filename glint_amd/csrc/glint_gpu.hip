@@ -1296,6 +1296,14 @@ inline int push_axpy_args(const glint_shard* s, const void* rows, int64_t n, con
   return GLINT_OK;
 }
 
+// Whether shards w and h hold the same rows: one dtype, device, size and partition (kind, start, and index
+// / parts for cyclic). cols and pitch are the caller's to compare.
+inline bool same_rows(const glint_shard* w, const glint_shard* h) {
+  const PartDesc &a = w->part, &b = h->part;
+  return h->dtype == w->dtype && h->device == w->device && a.size == b.size && a.kind == b.kind &&
+         a.start == b.start && (a.kind == 0 || (a.cidx == b.cidx && a.cparts == b.cparts));
+}
+
 // argument checks of glint_mat_push_rows_adagrad / _dev: a Float or Double matrix shard, a second shard
 // of the same type, device and partition that shares no memory with it (the same handle, or two views of
 // one slab that overlap), glint_mat_push_rows's sizes, lr a number and eps >= 0 (a NaN eps fails the test)
@@ -1303,16 +1311,30 @@ inline int push_adagrad_args(const glint_shard* w, const glint_shard* h, const v
                              int64_t n, double lr, double eps) {
   if (!w || !h || w == h || w->part.cols == 0) return GLINT_EINVAL;
   if (w->dtype != GLINT_F32 && w->dtype != GLINT_F64) return GLINT_EINVAL;
-  const PartDesc &a = w->part, &b = h->part;
-  if (h->dtype != w->dtype || h->device != w->device || a.cols != b.cols || a.pitch != b.pitch || a.size != b.size ||
-      a.kind != b.kind || a.start != b.start || (a.kind != 0 && (a.cidx != b.cidx || a.cparts != b.cparts)))
-    return GLINT_EINVAL;
+  if (!same_rows(w, h) || w->part.cols != h->part.cols || w->part.pitch != h->part.pitch) return GLINT_EINVAL;
   const uintptr_t wa = (uintptr_t)w->data, ha = (uintptr_t)h->data;
   const uintptr_t bytes = (uintptr_t)w->elems * w->vsize;  // (h's too: same size, pitch and type)
   if (wa < ha + bytes && ha < wa + bytes) return GLINT_EINVAL;
   if (n < 0 || n >= ((i64)1 << 32) - kSortTile) return GLINT_EINVAL;
   if (n > 0 && (!rows || !grads)) return GLINT_EINVAL;
   if (lr != lr || !(eps >= 0)) return GLINT_EINVAL;
+  return GLINT_OK;
+}
+
+// argument checks of glint_mat_push_rows_adam / _dev: push_adagrad_args' with a state shard of 2 * cols
+// columns (the packed moments; its pitch and byte size are its own), both betas in [0, 1) (a NaN fails
+// the test) and step >= 1
+inline int push_adam_args(const glint_shard* w, const glint_shard* s, const void* rows, const void* grads, int64_t n,
+                          double lr, double beta1, double beta2, double eps, int64_t step) {
+  if (!w || !s || w == s || w->part.cols == 0) return GLINT_EINVAL;
+  if (w->dtype != GLINT_F32 && w->dtype != GLINT_F64) return GLINT_EINVAL;
+  if (!same_rows(w, s) || s->part.cols != 2 * w->part.cols || s->part.pitch < s->part.cols) return GLINT_EINVAL;
+  const uintptr_t wa = (uintptr_t)w->data, sa = (uintptr_t)s->data;
+  if (wa < sa + (uintptr_t)s->elems * s->vsize && sa < wa + (uintptr_t)w->elems * w->vsize) return GLINT_EINVAL;
+  if (n < 0 || n >= ((i64)1 << 32) - kSortTile) return GLINT_EINVAL;
+  if (n > 0 && (!rows || !grads)) return GLINT_EINVAL;
+  if (lr != lr || !(eps >= 0)) return GLINT_EINVAL;
+  if (!(0 <= beta1 && beta1 < 1) || !(0 <= beta2 && beta2 < 1) || step < 1) return GLINT_EINVAL;
   return GLINT_OK;
 }
 
@@ -1559,7 +1581,7 @@ std::atomic<unsigned> g_env_gen{1};
 
 extern "C" {
 
-int glint_version(void) { return 1100; }  // 0.11.0: glint_mat_push_rows_grouped / _dev
+int glint_version(void) { return 1200; }  // 0.12.0: glint_mat_push_rows_adam / _dev
 
 int glint_reload_env(void) {
   g_env_gen.fetch_add(1, std::memory_order_acq_rel);
@@ -1990,6 +2012,18 @@ int glint_mat_push_rows_adagrad_dev(glint_shard_t weights, glint_shard_t state, 
     if (weights->dtype == GLINT_F64)
       return push_rows_adagrad<double>(weights, state, (const i64*)rows, grads, n, lr, eps, st);
     return push_rows_adagrad<float>(weights, state, (const i64*)rows, grads, n, lr, eps, st);
+  });
+}
+
+int glint_mat_push_rows_adam_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows, const void* grads,
+                                 int64_t n, double lr, double beta1, double beta2, double eps, int64_t step,
+                                 void* stream) {
+  const int args_rc = push_adam_args(weights, state, rows, grads, n, lr, beta1, beta2, eps, step);
+  if (args_rc == GLINT_OK && n == 0) return GLINT_OK;
+  return dev_call2(weights, state, args_rc, stream, [&](hipStream_t st) -> int {
+    if (weights->dtype == GLINT_F64)
+      return push_rows_adam<double>(weights, state, (const i64*)rows, grads, n, lr, beta1, beta2, eps, step, st);
+    return push_rows_adam<float>(weights, state, (const i64*)rows, grads, n, lr, beta1, beta2, eps, step, st);
   });
 }
 
@@ -3044,6 +3078,26 @@ int glint_mat_push_rows_adagrad(glint_shard_t weights, glint_shard_t state, cons
                      if (weights->dtype == GLINT_F64)
                        return push_rows_adagrad<double>(weights, state, d_rows, st.p[1], n, lr, eps, stream);
                      return push_rows_adagrad<float>(weights, state, d_rows, st.p[1], n, lr, eps, stream);
+                   });
+}
+
+// glint_mat_push_rows_adam: glint_mat_push_rows_adagrad's host side word for word -- every row checked
+// against the weights shard under both locks before anything is staged, rows and grads staged in one
+// block, the push on the weights shard's stream behind an event on the state shard's, the call ends
+// synchronised. Nothing comes back but the error state.
+int glint_mat_push_rows_adam(glint_shard_t weights, glint_shard_t state, const int64_t* rows, const void* grads,
+                             int64_t n, double lr, double beta1, double beta2, double eps, int64_t step) {
+  if (int rc = push_adam_args(weights, state, rows, grads, n, lr, beta1, beta2, eps, step)) return rc;
+  if (n == 0) return GLINT_OK;
+  return host_call(weights, state, {rows, nullptr, n}, false,
+                   {{rows, (size_t)n * 8}, {grads, (size_t)n * (size_t)weights->part.cols * weights->vsize}}, 0,
+                   [&](const Staged& st, hipStream_t stream, HostBack*) -> int {
+                     const i64* d_rows = (const i64*)st.p[0];
+                     if (weights->dtype == GLINT_F64)
+                       return push_rows_adam<double>(weights, state, d_rows, st.p[1], n, lr, beta1, beta2, eps, step,
+                                                     stream);
+                     return push_rows_adam<float>(weights, state, d_rows, st.p[1], n, lr, beta1, beta2, eps, step,
+                                                  stream);
                    });
 }
 

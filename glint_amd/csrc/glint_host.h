@@ -514,6 +514,15 @@ int push_rows_axpy(glint_shard* s, const i64* rows, i64 n, const void* coef, con
 template <typename V>
 int push_rows_adagrad(glint_shard* weights, glint_shard* state, const i64* rows, const void* grads, i64 n, double lr,
                       double eps, hipStream_t st);
+// Adam row push (glint_rowadam.hip), instantiated for float and double: per distinct row of the push, G as
+// above, then one lazy Adam step of the weights row and of the moments row (`state` packs m in columns
+// [0, cols) and v in [cols, 2 * cols); it has `weights`' type and partition and its own pitch), in the order
+// include/glint_gpu.h fixes, the scalars settled in double from lr, beta1, beta2, eps and step. Rows
+// outside the partition are skipped and recorded in err_of(weights). The front end's launches (weights'
+// scratch) and one fold launch on st, no host synchronisation; under both shards' locks.
+template <typename V>
+int push_rows_adam(glint_shard* weights, glint_shard* state, const i64* rows, const void* grads, i64 n, double lr,
+                   double beta1, double beta2, double eps, i64 step, hipStream_t st);
 // row-pair dot pull (glint_pairs.hip), instantiated for V in {int, long long, float, double}: out[i] = the
 // dot of row rows_a[i] of `a` with row rows_b[i] of `b` (device pointers), each row array translated with
 // its own shard's partition, in the row dot pull's order; `b` has a's type, device and cols and may be

@@ -600,6 +600,41 @@ class PartialMatrix(_Shard):
                                                    float(lr), float(eps)), self.handle)
         return True
 
+    def updateRowsAdam(self, state: "PartialMatrix", rows, grads, lr: float, step: int, beta1: float = 0.9,
+                       beta2: float = 0.999, eps: float = 1e-8, sync: bool = True) -> bool:
+        """Adam row push (an extension; glint_mat_push_rows_adam*): this shard holds the weights and
+        ``state`` -- a PartialMatrix of the same type, device and partition with ``2 * cols`` columns --
+        both moments, ``m`` in columns ``[0, cols)`` and ``v`` in ``[cols, 2 * cols)``; a zeroed shard is
+        the initial state. ``grads`` is (n, cols) or flat, dense row-major. Per distinct row of ``rows``:
+        ``G`` = its gradient rows added to +0 in push order, then ``m = beta1 * m + (1 - beta1) * G``,
+        ``v = beta2 * v + (1 - beta2) * G * G`` and ``weights -= (alpha * m) / (sqrt(v) / sqrt(c2) + eps)``
+        with ``alpha = lr / (1 - beta1 ** step)`` and ``c2 = 1 - beta2 ** step``, every operation rounded
+        on its own in the shard's type (include/glint_gpu.h has the contract). This is lazy Adam:
+        duplicates are coalesced, then one step is taken; ``step`` is the caller's global count from 1,
+        and a row that is not named keeps its moments. There are no order flags: the call is
+        deterministic. Errors as ``updateRowsAdagrad``."""
+        if not isinstance(state, PartialMatrix):
+            raise TypeError("state: expected a PartialMatrix")
+        if np.dtype(self.np_dtype).kind != "f":
+            raise TypeError(f"updateRowsAdam needs a Float or Double shard, not {np.dtype(self.np_dtype).name}")
+        if _is_torch_cuda(rows) != _is_torch_cuda(grads):
+            raise TypeError("rows and grads: mixing host arrays and device tensors")
+        scalars = (float(lr), float(beta1), float(beta2), float(eps), int(step))
+        if _is_torch_cuda(rows):
+            n = rows.numel()
+            self._check_dev(n, rows, values=grads, value_elems=n * self.cols)
+            rc = self.lib.glint_mat_push_rows_adam_dev(self.handle, state.handle, rows.data_ptr(), grads.data_ptr(),
+                                                       n, *scalars, self._stream_of(rows))
+            self._dev_done(rc, rows, sync)
+            return True
+        r = _host(rows, np.int64).reshape(-1)
+        g = _host(grads, self.np_dtype).reshape(-1)
+        if g.size != r.size * self.cols:
+            raise ValueError(f"grads: {g.size} elements, expected {r.size} rows x {self.cols} columns")
+        check(self.lib.glint_mat_push_rows_adam(self.handle, state.handle, r.ctypes.data, g.ctypes.data, r.size,
+                                                *scalars), self.handle)
+        return True
+
     def _axpy_q(self, xshape, cshape, n: int) -> int:
         """q of updateRowsAxpy for vectors of shape ``xshape`` and coefficients of shape ``cshape``."""
         if xshape == (self.cols,):

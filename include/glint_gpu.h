@@ -340,6 +340,48 @@ int glint_mat_push_rows_axpy(glint_shard_t shard, const int64_t* rows, int64_t n
 int glint_mat_push_rows_adagrad(glint_shard_t weights, glint_shard_t state, const int64_t* rows, const void* grads,
                                 int64_t n, double lr, double eps);
 
+/* Adam row push (an extension: the reference has no such message): lazy Adam next to the rows, on the
+ * Adagrad row push's frame. `weights` is a Float or Double matrix shard of type V; `state` is a matrix
+ * shard of the same dtype, device, size and partition with state.cols == 2 * weights.cols that packs both
+ * moments: row l holds m in columns [0, cols) and v in [cols, 2 * cols), so a zeroed shard is the right
+ * initial state. One push crosses the link with n x cols gradients and nothing else.
+ *   grads  n x cols values of V, dense row-major, no pitch (glint_mat_push_rows's vals).
+ * The scalars are settled once on the host, in double: c1 = 1 - pow(beta1, (double)step) and c2 = 1 -
+ * pow(beta2, (double)step) with the C library's pow, alpha = lr / c1, rc2 = sqrt(c2), a1 = 1 - beta1,
+ * a2 = 1 - beta2. Then beta1, beta2, a1, a2, alpha, rc2 and eps are each rounded once to V: b1, b2, a1, a2,
+ * alpha, rc2, eps below. For every distinct local row l the push names:
+ *   1. G[c] = (((+0 + g_i0[c]) + g_i1[c]) + ...) over the records i0 < i1 < ... with l(rows[i]) == l: the
+ *      sum runs in push order, in V, from +0 (the Adagrad push's step 1).
+ *   2. Per column, with m = state[l][c], v = state[l][cols + c] and w = weights[l][c], every operation in V
+ *      and rounded on its own (no fused multiply-add, no reassociation):
+ *        t1 = b1 * m;   t2 = a1 * G;   m' = t1 + t2
+ *        q  = G * G;    t3 = b2 * v;   t4 = a2 * q;   v' = t3 + t4
+ *        r  = sqrt(v'); s = r / rc2;   d = s + eps
+ *        u  = alpha * m';   p = u / d;   w' = w - p
+ *      m' is stored to state[l][c], v' to state[l][cols + c] and w' to weights[l][c].
+ *   3. sqrt and / are IEEE correctly rounded; subnormal inputs and results are kept; infinities and NaN
+ *      follow IEEE (a NaN's payload and sign are unspecified): G = 0, v = 0, eps = 0 gives 0 / 0 = NaN.
+ * This is lazy (sparse) Adam as the sparse optimizers of the ML frameworks define it -- duplicates are
+ * coalesced, then one step is taken, with a global `step` the caller counts from 1 -- not one step per
+ * record. A row the push does not name is neither read nor written in either shard, so its moments do not
+ * decay; neither is the pitch padding of either shard. No run is ever split and no atomic is used: there
+ * are no flags, and the answer is a function of the inputs only, never of pointer alignment, the slice
+ * path or the grid.
+ * Locks, ordering, errors and slabs are glint_mat_push_rows_adagrad's: both shards' locks are held, the
+ * call is ordered after both shards' earlier work and is synchronous for both; every row is checked before
+ * anything is staged, and a row outside the partition returns GLINT_EOUTOFRANGE (the record's index in
+ * glint_shard_last_error(weights)) with both shards unchanged. A slab with views is refused for either
+ * shard.
+ * GLINT_EINVAL: a NULL, vector, Int or Long `weights`; a NULL `state`, the same handle as `weights`, one
+ * that overlaps it in memory, or one that differs from it in dtype, device, size or partition (kind, start,
+ * and index / parts for cyclic); state.cols != 2 * weights.cols; n < 0, n >= 2^32 - 2048; NULL rows or grads
+ * with n > 0; a NaN lr; !(eps >= 0); !(0 <= beta1 && beta1 < 1), likewise beta2 (a NaN beta fails the
+ * test); step < 1. n == 0 launches nothing and returns GLINT_OK. Staged to the device: rows and grads in
+ * one block; nothing is copied back. Kernel timing: the one fold launch counts under GLINT_K_PUSH_ROWS on
+ * `weights`; nothing is recorded on `state`. */
+int glint_mat_push_rows_adam(glint_shard_t weights, glint_shard_t state, const int64_t* rows, const void* grads,
+                             int64_t n, double lr, double beta1, double beta2, double eps, int64_t step);
+
 /* Row-pair dot pull (an extension: the reference has no such message): the read half of a two-table
  * scoring step -- skip-gram with negative sampling, matrix factorisation, any two-tower model -- where
  * the other operand is not a vector the caller sends but a row of a second shard on the same device.
@@ -546,6 +588,16 @@ int glint_mat_push_rows_axpy_dev(glint_shard_t shard, const int64_t* rows, int64
  * the views'). */
 int glint_mat_push_rows_adagrad_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows,
                                     const void* grads, int64_t n, double lr, double eps, void* stream);
+
+/* glint_mat_push_rows_adam, device-resident: the same step with the same bits, stream-ordered on `stream`
+ * with no host synchronisation, after both shards' host-pointer work; both shards are marked for their
+ * next sync. A row outside the partition is skipped -- it contributes to no G -- and is reported by
+ * glint_shard_sync(weights, ...) as the lowest such record index; every other row is stepped. grads is
+ * read by 16 B when it is 16-B aligned (and cols allow), else element by element: the same bits either
+ * way. A slab that has views is GLINT_EINVAL for either shard. */
+int glint_mat_push_rows_adam_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows, const void* grads,
+                                 int64_t n, double lr, double beta1, double beta2, double eps, int64_t step,
+                                 void* stream);
 
 /* glint_mat_pull_pairs_dot, device-resident: the same dots with the same bits, one launch, stream-ordered
  * on `stream` with no host synchronisation, after both shards' host-pointer work; both shards are marked
@@ -758,7 +810,8 @@ enum glint_kernel_id {
   GLINT_K_PUSH_BINNED = 6,  /* the binned unordered-push pipeline (count, partition, apply) */
   GLINT_K_PUSH_ORDERED = 7, /* the order-preserving push of message-sized pushes (one launch) */
   /* the per-destination fold of a whole-row push (glint_mat_push_rows*), and the one fold launch of a
-   * non-empty Adagrad row push (glint_mat_push_rows_adagrad*), recorded on its weights shard only. Also
+   * non-empty Adagrad or Adam row push (glint_mat_push_rows_adagrad*, glint_mat_push_rows_adam*), recorded
+   * on its weights shard only. Also
    * the one launch of a shard fill or uniform init (glint_shard_fill*, glint_shard_init_uniform*), and the
    * one fold launch of a non-empty grouped row push (glint_mat_push_rows_grouped*) */
   GLINT_K_PUSH_ROWS = 8,

@@ -5,7 +5,7 @@ the JNI shim sees. One JSON line per measurement on stdout.
 
     python tools/measure_paths.py [--quick] [--sparse] [--rowsum] [--dot] [--axpy [--out FILE]] [--topk [--out FILE]]
                                   [--adagrad [--out FILE]] [--pairs [--out FILE]] [--init [--out FILE]]
-                                  [--groups [--out FILE]]
+                                  [--groups [--out FILE]] [--adam [--out FILE]]
 
 --sparse runs only the sparse-row-pull leg (dense getRows against getRowsSparse on a cfg5 shard).
 --rowsum runs only the grouped row-sum leg (getRowsSum against a dense row pull plus a reduction by the
@@ -29,6 +29,9 @@ FILE).
 --groups runs only the grouped row push leg (updateRowsGrouped against expanding the value rows by the caller
 plus a row push, on a word2vec-shaped Float and a cfg5-shaped Double shard) and appends its lines to
 profiles/groups/groups.jsonl (or FILE).
+--adam runs only the Adam row push leg (updateRowsAdam against coalescing, row pulls of weights and moments,
+the step and two row pushes by the caller, on cfg5 shards, with the Adagrad fold on the same rows beside it)
+and appends its lines to profiles/adam/adam_push.jsonl (or FILE).
 """
 import ctypes as C
 import json
@@ -566,6 +569,171 @@ def adagrad_leg(rng, out_path):
         with open(out_path, "a") as f:
             f.write(json.dumps(line) + "\n")
     for sh in (wa, sa, wb, sb):
+        sh.destroy()
+
+
+# The two Adam legs agree to rounding, not bit for bit: the baseline sums a row's gradients in another order
+# and adds deltas. Largest disagreement measured over both sizes (DESIGN.md "Adam row push"), asserted at
+# 100 x: absolute for the weights and the first moments, relative for the second moments.
+ADAM_AGREE_MEASURED = {"w": 1.8e-12, "m": 3.5e-13, "v": 8.5e-11}
+ADAM_AGREE_BOUND = {k: 100 * v for k, v in ADAM_AGREE_MEASURED.items()}
+
+
+def adam_leg(rng, out_path):
+    """The Adagrad leg's method and shapes with one more table: 2^17 x 512 Double weights and a 2^17 x 1024
+    moments shard per pair, 2^14 and 2^16 Zipf(1.0) rows of gradients. The leg under test steps one pair of
+    shards, its baseline another pair, on alternating rounds of one process; both pairs take the same
+    steps with the same step numbers.
+    Device: glint_mat_push_rows_adam_dev against what a caller does today -- torch.unique + index_add_ to
+    coalesce, glint_mat_pull_rows_dev of the weights and of the moments, the step in torch, two
+    glint_mat_push_rows_dev of deltas -- a HIP event pair around each; the fold kernel alone by its prof
+    id, and its bytes (n x cols gradients plus a read and a write of distinct x 3 cols) over that time as a
+    fraction of the HBM peak; beside it the Adagrad fold on the same rows, on a third pair. Host:
+    glint_mat_push_rows_adam against the same done with numpy and the host calls, wall time. The baselines
+    never run the code under test; after each n the two pairs are compared to ADAM_AGREE_BOUND. One JSON
+    line per n, also appended to out_path."""
+    shard_rows, cols, rounds = 1 << 17, 512, 5
+    lr, b1, b2, eps, hbm_peak_gbs = 0.05, 0.9, 0.999, 1e-8, 8000.0
+    part = glint_amd.RangePartition(0, 0, shard_rows)
+    wa, wb, wg, hg = (glint_amd.PartialMatrix(part, cols, "double", 0) for _ in range(4))
+    sa, sb = (glint_amd.PartialMatrix(part, 2 * cols, "double", 0) for _ in range(2))
+    all_rows = torch.arange(shard_rows, dtype=torch.int64, device=dev)
+    steps = {"a": 0, "b": 0}  # the next call on a pair is step steps[pair] + 1
+
+    def scalars(pair):
+        steps[pair] += 1
+        t = steps[pair]
+        return t, lr / (1.0 - b1 ** t), (1.0 - b2 ** t) ** 0.5
+
+    def ev_ms(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b)
+
+    def wall_ms(fn):
+        t0 = time.perf_counter()
+        fn()
+        return (time.perf_counter() - t0) * 1e3
+
+    def stats(ms):
+        return {"mean": float(np.mean(ms)), "min": float(np.min(ms)), "max": float(np.max(ms))}
+
+    Path(out_path).parent.mkdir(parents=True, exist_ok=True)
+    for n in (1 << 14, 1 << 16):
+        rows = zipf_keys(rng, shard_rows, n, 1.0)
+        g = rng.standard_normal((n, cols))
+        d_rows, d_g = torch.from_numpy(rows).to(dev), torch.from_numpy(g).to(dev)
+        distinct = int(np.unique(rows).size)
+
+        def dev_adam():
+            t, _, _ = scalars("a")
+            assert lib.glint_mat_push_rows_adam_dev(wa.handle, sa.handle, d_rows.data_ptr(), d_g.data_ptr(), n, lr,
+                                                    b1, b2, eps, t, stream) == 0
+
+        def dev_base():
+            _, alpha, rc2 = scalars("b")
+            uniq, inv = torch.unique(d_rows, return_inverse=True)
+            u = uniq.numel()
+            G = torch.zeros((u, cols), dtype=torch.float64, device=dev).index_add_(0, inv, d_g)
+            w = torch.empty_like(G)
+            mv = torch.empty((u, 2 * cols), dtype=torch.float64, device=dev)
+            assert lib.glint_mat_pull_rows_dev(wb.handle, uniq.data_ptr(), w.data_ptr(), u, stream) == 0
+            assert lib.glint_mat_pull_rows_dev(sb.handle, uniq.data_ptr(), mv.data_ptr(), u, stream) == 0
+            m2 = b1 * mv[:, :cols] + (1.0 - b1) * G
+            v2 = b2 * mv[:, cols:] + (1.0 - b2) * (G * G)
+            dw = -((alpha * m2) / (torch.sqrt(v2) / rc2 + eps))
+            ds = torch.cat([m2, v2], 1) - mv
+            assert lib.glint_mat_push_rows_dev(sb.handle, uniq.data_ptr(), ds.data_ptr(), u, 0, stream) == 0
+            assert lib.glint_mat_push_rows_dev(wb.handle, uniq.data_ptr(), dw.data_ptr(), u, 0, stream) == 0
+            # (the temporaries are freed into torch's allocator, which reuses them on this stream only)
+
+        def host_adam():
+            t, _, _ = scalars("a")
+            assert lib.glint_mat_push_rows_adam(wa.handle, sa.handle, rows.ctypes.data, g.ctypes.data, n, lr, b1, b2,
+                                                eps, t) == 0
+
+        def host_base():
+            _, alpha, rc2 = scalars("b")
+            uniq, inv = np.unique(rows, return_inverse=True)
+            G = np.zeros((uniq.size, cols))
+            np.add.at(G, inv, g)
+            w, mv = np.empty_like(G), np.empty((uniq.size, 2 * cols))
+            assert lib.glint_mat_pull_rows(wb.handle, uniq.ctypes.data, w.ctypes.data, uniq.size) == 0
+            assert lib.glint_mat_pull_rows(sb.handle, uniq.ctypes.data, mv.ctypes.data, uniq.size) == 0
+            m2 = b1 * mv[:, :cols] + (1.0 - b1) * G
+            v2 = b2 * mv[:, cols:] + (1.0 - b2) * (G * G)
+            dw = -((alpha * m2) / (np.sqrt(v2) / rc2 + eps))
+            ds = np.concatenate([m2, v2], 1) - mv
+            assert lib.glint_mat_push_rows(sb.handle, uniq.ctypes.data, ds.ctypes.data, uniq.size, 0) == 0
+            assert lib.glint_mat_push_rows(wb.handle, uniq.ctypes.data, dw.ctypes.data, uniq.size, 0) == 0
+
+        t = {k: [] for k in ("host_adam", "host_base", "dev_adam", "dev_base")}
+        for rnd in range(rounds + 1):  # round 0 warms up; the two legs alternate inside every round
+            got = {"host_base": wall_ms(host_base), "host_adam": wall_ms(host_adam)}
+            torch.cuda.synchronize()
+            got["dev_base"] = ev_ms(dev_base)
+            got["dev_adam"] = ev_ms(dev_adam)
+            if rnd:
+                for k, v in got.items():
+                    t[k].append(v)
+        assert steps["a"] == steps["b"]
+        lib.glint_prof_reset(wa.handle)  # the fold alone, mirrored on the baseline's shards
+        lib.glint_prof_enable(wa.handle, 1)
+        for _ in range(3):
+            dev_adam()
+            dev_base()
+        torch.cuda.synchronize()
+        fold_ms = kernel_ms(wa.handle, N.GLINT_K_PUSH_ROWS)
+        lib.glint_prof_enable(wa.handle, 0)
+        lib.glint_prof_reset(wg.handle)  # the Adagrad fold on the same rows, for scale
+        lib.glint_prof_enable(wg.handle, 1)
+        for _ in range(4):
+            assert lib.glint_mat_push_rows_adagrad_dev(wg.handle, hg.handle, d_rows.data_ptr(), d_g.data_ptr(), n, lr,
+                                                       eps, stream) == 0
+        torch.cuda.synchronize()
+        adagrad_fold_ms = kernel_ms(wg.handle, N.GLINT_K_PUSH_ROWS)
+        lib.glint_prof_enable(wg.handle, 0)
+        for sh in (wa, sa, wb, sb, wg, hg):
+            sh.sync(stream)
+        dw = (wa.getRows(all_rows) - wb.getRows(all_rows)).abs().max().item()
+        sa_, sb_ = sa.getRows(all_rows), sb.getRows(all_rows)
+        dm = (sa_[:, :cols] - sb_[:, :cols]).abs().max().item()
+        dv = ((sa_[:, cols:] - sb_[:, cols:]).abs() / sb_[:, cols:].abs().clamp_min(1e-300)).max().item()
+        del sa_, sb_
+        agree = {"w": dw, "m": dm, "v": dv}
+        print(f"adam legs disagree by {agree}; bound {ADAM_AGREE_BOUND}", file=sys.stderr, flush=True)
+        assert all(agree[k] <= ADAM_AGREE_BOUND[k] for k in agree), (agree, ADAM_AGREE_BOUND)
+        m = {k: stats(v) for k, v in t.items()}
+        fold_bytes = (n + 6 * distinct) * cols * 8
+        line = dict(
+            op="mat_push_rows_adam", pattern="zipf1.0 rows", shape=[shard_rows, cols], rows=n,
+            distinct_rows=distinct, rounds=rounds, lr=lr, beta1=b1, beta2=b2, eps=eps, steps_taken=steps["a"],
+            host_adam_ms=m["host_adam"], host_baseline_ms=m["host_base"],
+            host_speedup=m["host_base"]["mean"] / m["host_adam"]["mean"],
+            host_adam_bytes_staged=n * 8 + n * cols * 8,
+            host_baseline_bytes_over_link=2 * distinct * 8 + 6 * distinct * cols * 8,
+            dev_adam_ms=m["dev_adam"], dev_baseline_ms=m["dev_base"],
+            dev_speedup=m["dev_base"]["mean"] / m["dev_adam"]["mean"],
+            fold_kernel_ms=fold_ms, fold_bytes=fold_bytes, fold_GBps=fold_bytes / (fold_ms * 1e-3) / 1e9,
+            fold_fraction_of_hbm_peak=fold_bytes / (fold_ms * 1e-3) / 1e9 / hbm_peak_gbs, hbm_peak_GBps=hbm_peak_gbs,
+            adagrad_fold_kernel_ms=adagrad_fold_ms, fold_over_adagrad_fold=fold_ms / adagrad_fold_ms,
+            max_abs_weight_difference=dw, max_abs_m_difference=dm, max_relative_v_difference=dv,
+            agreement_bound=ADAM_AGREE_BOUND,
+            note="host_*: C calls on pageable numpy arrays, synchronous, wall ms; baseline = np.unique + np.add.at, "
+                 "glint_mat_pull_rows of weights and moments, the step in numpy, two glint_mat_push_rows of deltas. "
+                 "dev_*: one HIP event pair per call; baseline = torch.unique + index_add_, two "
+                 "glint_mat_pull_rows_dev, the step in torch, two glint_mat_push_rows_dev. "
+                 "Legs alternate inside each of `rounds` rounds after one warm-up round. fold_kernel_ms: the fold "
+                 "alone (glint_prof, GLINT_K_PUSH_ROWS on the weights shard); fold_bytes = (rows + 6 * "
+                 "distinct_rows) * cols * 8. adagrad_fold_kernel_ms: the Adagrad push's fold on the same rows and "
+                 "gradients, on a pair of its own")
+        emit(**line)
+        with open(out_path, "a") as f:
+            f.write(json.dumps(line) + "\n")
+    for sh in (wa, sa, wb, sb, wg, hg):
         sh.destroy()
 
 
@@ -1165,6 +1333,11 @@ def main():
         out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
             str(Path(__file__).resolve().parent.parent / "profiles" / "adagrad" / "adagrad_push.jsonl")
         adagrad_leg(np.random.default_rng(42), out)
+        return
+    if "--adam" in sys.argv:
+        out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
+            str(Path(__file__).resolve().parent.parent / "profiles" / "adam" / "adam_push.jsonl")
+        adam_leg(np.random.default_rng(42), out)
         return
     if "--groups" in sys.argv:
         out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
