@@ -13,11 +13,11 @@ from .errors import (ArrayIndexOutOfBoundsException, GlintDeviceError,  # noqa: 
                      IndexOutOfBoundsException, ModelCreationException)
 from .partitioning import (CyclicPartition, CyclicPartitioner, RangePartition,  # noqa: E402
                            RangePartitioner)
-from .shard import PartialMatrix, PartialVector  # noqa: E402
+from .shard import PartialMatrix, PartialVector, from_bfloat16, to_bfloat16  # noqa: E402
 from .client import BigMatrix, BigVector, Client  # noqa: E402
 
 __all__ = [
     "PartialVector", "PartialMatrix", "RangePartition", "RangePartitioner", "CyclicPartition",
     "CyclicPartitioner", "Client", "BigVector", "BigMatrix", "IndexOutOfBoundsException",
-    "ArrayIndexOutOfBoundsException", "GlintDeviceError", "ModelCreationException",
+    "ArrayIndexOutOfBoundsException", "GlintDeviceError", "ModelCreationException", "to_bfloat16", "from_bfloat16",
 ]

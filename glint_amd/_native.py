@@ -25,6 +25,7 @@ GLINT_K_PULL_ROWS_SUM = 10
 GLINT_K_PULL_ROWS_DOT = 11
 GLINT_K_PUSH_ROWS_AXPY = 12
 GLINT_K_COUNT = 13
+GLINT_WIRE_F16, GLINT_WIRE_BF16, GLINT_WIRE_F32 = 0, 1, 2
 GLINT_DOT_MAX_QUERIES, GLINT_DOT_QUERY_TILE = 1024, 4
 GLINT_AXPY_MAX_VECTORS = 64
 GLINT_TOPK_MAX_K, GLINT_TOPK_MAX_QUERIES, GLINT_TOPK_TILE = 1024, 64, 4096
@@ -76,6 +77,11 @@ SIGNATURES = {
     "glint_mat_push_pairs_axpy_dev": (_I, [_P, _P, _P, _P, _P, _I64, _I, _P]),
     "glint_mat_push_rows_grouped": (_I, [_P, _P, _I64, _P, _I64, _P, _P, _I]),
     "glint_mat_push_rows_grouped_dev": (_I, [_P, _P, _I64, _P, _I64, _P, _P, _I, _P]),
+    "glint_wire_supported": (_I, [_I, _I]),
+    "glint_mat_pull_rows_as": (_I, [_P, _P, _P, _I64, _I]),
+    "glint_mat_pull_rows_as_dev": (_I, [_P, _P, _P, _I64, _I, _P]),
+    "glint_mat_push_rows_as": (_I, [_P, _P, _P, _I64, _I, _I]),
+    "glint_mat_push_rows_as_dev": (_I, [_P, _P, _P, _I64, _I, _I, _P]),
     "glint_mat_pull_topk": (_I, [_P, _P, _I64, _I64, _P, _P]),
     "glint_mat_pull_topk_dev": (_I, [_P, _P, _I64, _I64, _P, _P, _P]),
     "glint_shard_last_error": (_I, [_P, C.POINTER(_I64)]),

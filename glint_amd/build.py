@@ -27,10 +27,12 @@ HIP_SOURCES = [CSRC / "glint_gpu.hip", CSRC / "glint_sort.hip", CSRC / "glint_ro
                CSRC / "glint_exchange.hip", CSRC / "glint_rows.hip", CSRC / "glint_sparse.hip",
                CSRC / "glint_rowsum.hip", CSRC / "glint_rowdot.hip", CSRC / "glint_rowaxpy.hip",
                CSRC / "glint_topk.hip", CSRC / "glint_rowadagrad.hip", CSRC / "glint_pairs.hip",
-               CSRC / "glint_init.hip", CSRC / "glint_rowgroup.hip", CSRC / "glint_rowadam.hip"]
-# plain C++: the push planners, the top-k pull's level plan and the uniform init's value contract
+               CSRC / "glint_init.hip", CSRC / "glint_rowgroup.hip", CSRC / "glint_rowadam.hip",
+               CSRC / "glint_rowwire.hip"]
+# plain C++: the push planners, the top-k pull's level plan, the uniform init's value contract and the
+# narrow-format row transport's conversion contract
 PLAN_HEADERS = [CSRC / "glint_push_plan.h", CSRC / "glint_bin_plan.h", CSRC / "glint_topk_plan.h",
-                CSRC / "glint_init_plan.h"]
+                CSRC / "glint_init_plan.h", CSRC / "glint_wire_plan.h"]
 HIP_HEADERS = [CSRC / "glint_kernels.h", CSRC / "glint_device.h", CSRC / "glint_host.h", CSRC / "glint_dot.h",
                CSRC / "glint_axpy.h",
                ROOT / "include" / "glint_gpu.h", *PLAN_HEADERS]
@@ -230,6 +232,28 @@ def build_init_probe(force: bool = False, verbose: bool = False) -> Path:
     return INIT_PROBE
 
 
+WIRE_PROBE_SRC = ROOT / "tests" / "c" / "wire_probe.cpp"
+WIRE_PROBE = ROOT / "tests" / "c" / "build" / "libwire_probe.so"
+
+
+def build_wire_probe(force: bool = False, verbose: bool = False) -> Path:
+    """The narrow-format row transport's conversion contract (glint_wire_plan.h: the supported pairs and the
+    integer narrowing and widening of each) as a host-only library: what tests/test_wire_cpu.py loads.
+    Compiled by g++ alone."""
+    deps = [WIRE_PROBE_SRC, CSRC / "glint_wire_plan.h"]
+    if not force and not _stale(WIRE_PROBE, deps):
+        return WIRE_PROBE
+    WIRE_PROBE.parent.mkdir(parents=True, exist_ok=True)
+    tmp = WIRE_PROBE.with_suffix(".so.tmp")
+    cxx = shutil.which("g++") or "c++"
+    cmd = [cxx, "-O2", "-std=c++17", "-Wall", "-Werror", "-fPIC", "-shared", "-o", str(tmp), str(WIRE_PROBE_SRC)]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True, cwd=str(ROOT))
+    os.replace(tmp, WIRE_PROBE)
+    return WIRE_PROBE
+
+
 def build_all(force: bool = False, verbose: bool = False) -> None:
     build_gpu_lib(force=force, verbose=verbose)
     build_oracle(force=force, verbose=verbose)
@@ -239,6 +263,7 @@ def build_all(force: bool = False, verbose: bool = False) -> None:
     build_sweep_probe(force=force, verbose=verbose)
     build_topk_probe(force=force, verbose=verbose)
     build_init_probe(force=force, verbose=verbose)
+    build_wire_probe(force=force, verbose=verbose)
 
 
 if __name__ == "__main__":

@@ -11,6 +11,9 @@ Mirrors the reference's client factory and asynchronous models, minus the Akka t
 * ``BigMatrix.push/pull`` -- AsyncBigMatrix (AsyncBigMatrix.scala:53-170), including the row pull.
 * ``BigMatrix.pushRows`` -- an extension with no AsyncBigMatrix counterpart: the row pull's write
   side, whole rows added without expanding them into (row, col, value) triplets.
+* ``BigMatrix.pullRowsAs`` / ``BigMatrix.pushRowsAs`` -- extensions: the row pull and the row push with the
+  rows crossing the link as float16 or bfloat16 (Float) or float32 (Double), rounded / widened on the shards
+  (PartialMatrix.getRowsAs / updateRowsAs).
 * ``BigMatrix.pushAxpy`` -- an extension: rows += coefficients times caller vectors, the contribution
   rows rebuilt on the shards (PartialMatrix.updateRowsAxpy) instead of sent.
 * ``BigMatrix.pushAdagrad`` -- an extension: gradient rows summed per distinct row, then one Adagrad step
@@ -43,7 +46,7 @@ import numpy as np
 
 from .errors import ModelCreationException
 from .partitioning import CyclicPartitioner, RangePartitioner
-from .shard import PartialMatrix, PartialVector, resolve_dtype
+from .shard import PartialMatrix, PartialVector, resolve_dtype, resolve_wire
 
 
 def bucket(owner: np.ndarray, nparts: int):
@@ -176,6 +179,45 @@ class BigMatrix(_InitMixin):
             if idx.size:
                 sh.updateRows(rows[idx], values[idx], deterministic=deterministic)
         return True
+
+    def pushRowsAs(self, rows, values, wire: str, deterministic: bool = False) -> bool:
+        """Narrow-format row push (an extension): ``pushRows`` of rows that arrive in the wire type ``wire``
+        ('float16' or 'bfloat16' for a Float matrix, 'float32' for a Double one) and are widened on the
+        shards, so half the bytes cross the link. ``values`` is an (n, cols) or flat numpy array of float16,
+        of uint16 bfloat16 bit patterns (``to_bfloat16``) or of float32; another dtype raises ValueError.
+        All rows are validated before any shard is called; bucketed by partition as ``pushRows``, one
+        PartialMatrix.updateRowsAs per non-empty partition."""
+        np_wire = resolve_wire(wire)[1]
+        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        values = np.asarray(values)
+        if values.dtype != np_wire:
+            raise ValueError(f"values: dtype {values.dtype}, expected {np.dtype(np_wire).name} for wire type {wire!r}")
+        if values.size != rows.size * self.cols:
+            raise ValueError(f"values: {values.size} elements, expected {rows.size} rows x {self.cols} columns")
+        values = np.ascontiguousarray(values).reshape(rows.size, self.cols)
+        owner = self.partitioner.partition_indices(rows)
+        order, off = bucket(owner, len(self.shards))
+        for p, sh in enumerate(self.shards):
+            idx = order[off[p]:off[p + 1]]
+            if idx.size:
+                sh.updateRowsAs(rows[idx], values[idx], wire, deterministic=deterministic)
+        return True
+
+    def pullRowsAs(self, rows, wire: str) -> np.ndarray:
+        """Narrow-format row pull (an extension): ``pull(rows)`` rounded on the shards to the wire type
+        ``wire``, as an (n, cols) array of float16, of uint16 bfloat16 bit patterns (``from_bfloat16``) or of
+        float32, in the caller's order. A row lives in one partition, so the bits are the shard's. Bucketed
+        by partition as ``pull``; one PartialMatrix.getRowsAs per non-empty partition."""
+        np_wire = resolve_wire(wire)[1]
+        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        owner = self.partitioner.partition_indices(rows)
+        order, off = bucket(owner, len(self.shards))
+        out = np.zeros((rows.size, self.cols), dtype=np_wire)
+        for p, sh in enumerate(self.shards):
+            idx = order[off[p]:off[p + 1]]
+            if idx.size:
+                out[idx] = sh.getRowsAs(rows[idx], wire)
+        return out
 
     def pushAxpy(self, rows, coef, x, deterministic: bool = False) -> bool:
         """Row axpy push (an extension): row rows[i] += sum over j of ``coef[i, j] * x[j]``, in the

@@ -789,6 +789,7 @@ using namespace glint;
 
 #include "glint_host.h"
 #include "glint_init_plan.h"
+#include "glint_wire_plan.h"
 
 namespace {
 
@@ -1287,6 +1288,23 @@ inline int push_rows_args(const glint_shard* s, const void* rows, const void* va
   return GLINT_OK;
 }
 
+// argument checks of glint_mat_pull_rows_as / _dev: a matrix shard of a type that pairs with `wire`
+// (glint_wire_plan.h), a 31-bit request count, the two arrays present when there are rows
+inline int pull_rows_as_args(const glint_shard* s, const void* rows, const void* out, int64_t n, int wire) {
+  if (!s || s->part.cols == 0 || !wire_supported(s->dtype, wire)) return GLINT_EINVAL;
+  if (n < 0 || n >= ((i64)1 << 31)) return GLINT_EINVAL;
+  if (n > 0 && (!rows || !out)) return GLINT_EINVAL;
+  return GLINT_OK;
+}
+
+// argument checks of glint_mat_push_rows_as / _dev: glint_mat_push_rows's, and a shard type that pairs with
+// `wire`
+inline int push_rows_as_args(const glint_shard* s, const void* rows, const void* vals, int64_t n, int wire,
+                             int flags) {
+  if (int rc = push_rows_args(s, rows, vals, n, flags)) return rc;
+  return wire_supported(s->dtype, wire) ? GLINT_OK : GLINT_EINVAL;
+}
+
 // argument checks of glint_mat_push_rows_axpy / _dev: glint_mat_push_rows's, 1 to GLINT_AXPY_MAX_VECTORS
 // vectors, the three arrays present when there are records
 inline int push_axpy_args(const glint_shard* s, const void* rows, int64_t n, const void* coef, const void* x,
@@ -1581,7 +1599,9 @@ std::atomic<unsigned> g_env_gen{1};
 
 extern "C" {
 
-int glint_version(void) { return 1200; }  // 0.12.0: glint_mat_push_rows_adam / _dev
+int glint_version(void) { return 1300; }  // 0.13.0: glint_mat_pull_rows_as / glint_mat_push_rows_as / _dev
+
+int glint_wire_supported(int dtype, int wire) { return wire_supported(dtype, wire) ? 1 : 0; }
 
 int glint_reload_env(void) {
   g_env_gen.fetch_add(1, std::memory_order_acq_rel);
@@ -2001,6 +2021,22 @@ int glint_mat_push_rows_grouped_dev(glint_shard_t s, const int64_t* rows, int64_
   return dev_call(s, args_rc, stream, [&](hipStream_t st) -> int {
     GLINT_DISPATCH(s->dtype, push_rows_grouped, s, (const i64*)rows, n, (const i64*)grp_ptr, g, vals, coef, flags,
                    st);
+  });
+}
+
+int glint_mat_pull_rows_as_dev(glint_shard_t s, const int64_t* rows, void* out, int64_t n, int wire, void* stream) {
+  const int args_rc = pull_rows_as_args(s, rows, out, n, wire);
+  if (args_rc == GLINT_OK && n == 0) return GLINT_OK;
+  return dev_call(s, args_rc, stream,
+                  [&](hipStream_t st) -> int { return pull_rows_wire(s, (const i64*)rows, out, n, wire, st); });
+}
+
+int glint_mat_push_rows_as_dev(glint_shard_t s, const int64_t* rows, const void* vals, int64_t n, int wire, int flags,
+                               void* stream) {
+  const int args_rc = push_rows_as_args(s, rows, vals, n, wire, flags);
+  if (args_rc == GLINT_OK && n == 0) return GLINT_OK;
+  return dev_call(s, args_rc, stream, [&](hipStream_t st) -> int {
+    return push_rows_wire(s, (const i64*)rows, vals, n, wire, flags, st);
   });
 }
 
@@ -3059,6 +3095,37 @@ int glint_mat_push_rows_grouped(glint_shard_t s, const int64_t* rows, int64_t n,
                      GLINT_DISPATCH(s->dtype, push_rows_grouped, s, (const i64*)st.p[0], n, (const i64*)st.p[1], g,
                                     (const void*)st.p[3], coef ? (const void*)st.p[2] : nullptr,
                                     flags | kPushHostSequential, stream);
+                   });
+}
+
+// glint_mat_pull_rows_as: every row is checked before anything is staged (a rejected call writes nothing),
+// then rows is staged, the one kernel rounds the requested rows to the wire type into the staging block
+// behind them (256-B aligned there, so the 16-B path is taken when cols allow) and n * cols * sizeof W bytes
+// come back -- never n * cols * sizeof V. No ring path.
+int glint_mat_pull_rows_as(glint_shard_t s, const int64_t* rows, void* out, int64_t n, int wire) {
+  if (int rc = pull_rows_as_args(s, rows, out, n, wire)) return rc;
+  if (n == 0) return GLINT_OK;
+  const size_t out_bytes = (size_t)n * (size_t)s->part.cols * (size_t)wire_size(wire);
+  return host_call(s, s, {rows, nullptr, n}, false, {{rows, (size_t)n * 8}}, out_bytes,
+                   [&](const Staged& st, hipStream_t stream, HostBack* back) -> int {
+                     back[0] = {out, st.extra, out_bytes, true};
+                     return pull_rows_wire(s, (const i64*)st.p[0], st.extra, n, wire, stream);
+                   });
+}
+
+// glint_mat_push_rows_as: every row is checked before anything is enqueued (a rejected message applies
+// nothing), then rows and the narrow vals are staged in one block -- n * 8 + n * cols * sizeof W bytes, never
+// n * cols * sizeof V, and no widened copy is built on the device either: the fold widens each contribution as
+// it loads it -- and the push runs on the shard's stream in message order (kPushHostSequential). Nothing comes
+// back but the error state.
+int glint_mat_push_rows_as(glint_shard_t s, const int64_t* rows, const void* vals, int64_t n, int wire, int flags) {
+  if (int rc = push_rows_as_args(s, rows, vals, n, wire, flags)) return rc;
+  if (n == 0) return GLINT_OK;
+  return host_call(s, s, {rows, nullptr, n}, false,
+                   {{rows, (size_t)n * 8}, {vals, (size_t)n * (size_t)s->part.cols * (size_t)wire_size(wire)}}, 0,
+                   [&](const Staged& st, hipStream_t stream, HostBack*) -> int {
+                     return push_rows_wire(s, (const i64*)st.p[0], st.p[1], n, wire, flags | kPushHostSequential,
+                                           stream);
                    });
 }
 

@@ -548,6 +548,15 @@ int push_pairs_axpy(glint_shard* dst, glint_shard* src, const i64* rows_dst, con
 template <typename V>
 int push_rows_grouped(glint_shard* s, const i64* rows, i64 n, const i64* grp_ptr, i64 g, const void* vals,
                       const void* coef, int flags, hipStream_t st);
+// narrow-format row transport (glint_rowwire.hip), for the (dtype, wire) pairs glint_wire_plan.h lists (any
+// other pair: GLINT_EINVAL), device pointers. pull_rows_wire: out (n x cols values of the wire type, dense) =
+// the requested rows rounded to the wire type; a row outside the partition answers zero bits and is recorded
+// in err_of(s); one launch on st. push_rows_wire: push_rows of the rows `vals` (n x cols values of the wire
+// type, dense) widened to the shard's type, the widening done at the fold's contribution load; rows outside
+// the partition are skipped and recorded in err_of(s); the front end's launches and one fold launch on st.
+// No host synchronisation.
+int pull_rows_wire(glint_shard* s, const i64* rows, void* out, i64 n, int wire, hipStream_t st);
+int push_rows_wire(glint_shard* s, const i64* rows, const void* vals, i64 n, int wire, int flags, hipStream_t st);
 // shard fill and uniform init (glint_init.hip), for every dtype: the named rows' elements = the low vsize
 // bytes of `a` (uniform false), or the values include/glint_gpu.h fixes for (seed, global row, column)
 // with lo and w as bits of the shard's type in `a` and `b` (Float / Double only). list false names every

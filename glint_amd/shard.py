@@ -77,6 +77,45 @@ def _host(x, dtype) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(x, dtype=dtype))
 
 
+# wire types of the narrow-format row transport (glint_mat_pull_rows_as / glint_mat_push_rows_as):
+# name -> (GLINT_WIRE_* code, numpy dtype of host arrays, torch dtype name of device tensors). numpy has no
+# bfloat16, so host arrays hold its 16-bit patterns (to_bfloat16 / from_bfloat16).
+_WIRES = {
+    "float16": (N.GLINT_WIRE_F16, np.float16, "float16"),
+    "bfloat16": (N.GLINT_WIRE_BF16, np.uint16, "bfloat16"),
+    "float32": (N.GLINT_WIRE_F32, np.float32, "float32"),
+}
+
+
+def resolve_wire(wire) -> tuple:
+    """Map a wire type name to (GLINT_WIRE_* code, numpy dtype, torch dtype name)."""
+    if not isinstance(wire, str) or wire not in _WIRES:
+        raise ValueError(f"unsupported wire type {wire!r} ('float16', 'bfloat16' or 'float32')")
+    return _WIRES[wire]
+
+
+def to_bfloat16(x) -> np.ndarray:
+    """float32 array -> its bfloat16 bit patterns (uint16), the narrowing glint_wire_plan.h fixes: round to
+    nearest even on the float's bits u, ``(u + 0x7FFF + ((u >> 16) & 1)) >> 16``; overflow gives an infinity,
+    subnormals are kept, a NaN stays a (quiet) NaN."""
+    x = np.asarray(x)
+    if x.dtype != np.float32:
+        raise TypeError(f"to_bfloat16 takes float32, not {x.dtype}")
+    u = np.ascontiguousarray(x).view(np.uint32).astype(np.uint64)  # 64 bits: the sum below cannot wrap
+    c = np.uint64
+    r = (u + c(0x7FFF) + ((u >> c(16)) & c(1))) >> c(16)
+    nan = (u & c(0x7FFFFFFF)) > c(0x7F800000)
+    return np.where(nan, (u >> c(16)) | c(0x40), r).astype(np.uint16)
+
+
+def from_bfloat16(b) -> np.ndarray:
+    """bfloat16 bit patterns (uint16) -> the equal float32 values: exact, the pattern is the float's upper half."""
+    b = np.asarray(b)
+    if b.dtype != np.uint16:
+        raise TypeError(f"from_bfloat16 takes uint16 bit patterns, not {b.dtype}")
+    return (np.ascontiguousarray(b).astype(np.uint32) << np.uint32(16)).view(np.float32)
+
+
 class HostBuffer:
     """Pinned, device-mapped host memory from glint_host_alloc: the buffers a server answers pulls
     from. A message-sized pull whose ``out`` lies in one is answered by the kernel straight into it
@@ -316,18 +355,21 @@ class _Shard:
         import torch
         return getattr(torch, np.dtype(self.np_dtype).name)
 
-    def _check_dev(self, n: int, keys, cols=None, values=None, out=None, out_elems=None, value_elems=None) -> None:
+    def _check_dev(self, n: int, keys, cols=None, values=None, out=None, out_elems=None, value_elems=None,
+                   wire_dtype=None) -> None:
         """Device-resident arguments: every tensor on the shard's GPU, contiguous, of the dtype the
-        kernels read (keys/rows int64, cols int32, values/out the shard's type) and long enough --
-        the kernels take raw pointers, so a mismatch would read or write past a buffer."""
+        kernels read (keys/rows int64, cols int32, values/out the shard's type, or ``wire_dtype`` for a
+        narrow-format call) and long enough -- the kernels take raw pointers, so a mismatch would read or
+        write past a buffer."""
         import torch
+        vdt = self.torch_dtype if wire_dtype is None else wire_dtype
         spec = [("keys", keys, torch.int64, n)]
         if cols is not None:
             spec.append(("cols", cols, torch.int32, n))
         if values is not None:
-            spec.append(("values", values, self.torch_dtype, n if value_elems is None else value_elems))
+            spec.append(("values", values, vdt, n if value_elems is None else value_elems))
         if out is not None:
-            spec.append(("out", out, self.torch_dtype, n if out_elems is None else out_elems))
+            spec.append(("out", out, vdt, n if out_elems is None else out_elems))
         for name, t, dt, want in spec:
             if not _is_torch_cuda(t):
                 raise TypeError(f"{name}: expected a CUDA tensor (mixing host arrays and device tensors)")
@@ -476,6 +518,39 @@ class PartialMatrix(_Shard):
         if v.size != r.size * self.cols:
             raise ValueError(f"values: {v.size} elements, expected {r.size} rows x {self.cols} columns")
         check(self.lib.glint_mat_push_rows(self.handle, r.ctypes.data, v.ctypes.data, r.size, flags), self.handle)
+        return True
+
+    def updateRowsAs(self, rows, values, wire: str, deterministic: bool = False, sync: bool = True,
+                     unordered: bool = False) -> bool:
+        """Narrow-format row push (an extension; glint_mat_push_rows_as*): ``updateRows`` of rows that arrive in
+        the wire type ``wire`` -- 'float16' or 'bfloat16' for a Float shard, 'float32' for a Double shard --
+        widened exactly on the shard, inside the fold, so half the bytes are staged. ``values`` is (n, cols) or
+        flat: a numpy array of float16, of uint16 bfloat16 bit patterns (``to_bfloat16``) or of float32, or a
+        torch device tensor of that type; another dtype raises ValueError. Order and flags as ``updateRows``."""
+        code, np_wire, torch_name = resolve_wire(wire)
+        flags = _flags(deterministic, unordered)
+        if _is_torch_cuda(rows):
+            import torch
+            wdt = getattr(torch, torch_name)
+            if _is_torch_cuda(values) and values.dtype != wdt:
+                raise ValueError(f"values: dtype {values.dtype}, expected {wdt} for wire type {wire!r}")
+            n = rows.numel()
+            self._check_dev(n, rows, values=values, value_elems=n * self.cols, wire_dtype=wdt)
+            rc = self.lib.glint_mat_push_rows_as_dev(self.handle, rows.data_ptr(), values.data_ptr(), n, code, flags,
+                                                     self._stream_of(rows))
+            self._dev_done(rc, rows, sync)
+            return True
+        if _is_torch_cuda(values):
+            raise TypeError("values: a device tensor with host rows (mixing host arrays and device tensors)")
+        r = _host(rows, np.int64).reshape(-1)
+        v = np.asarray(values)
+        if v.dtype != np_wire:
+            raise ValueError(f"values: dtype {v.dtype}, expected {np.dtype(np_wire).name} for wire type {wire!r}")
+        v = np.ascontiguousarray(v).reshape(-1)
+        if v.size != r.size * self.cols:
+            raise ValueError(f"values: {v.size} elements, expected {r.size} rows x {self.cols} columns")
+        check(self.lib.glint_mat_push_rows_as(self.handle, r.ctypes.data, v.ctypes.data, r.size, code, flags),
+              self.handle)
         return True
 
     def updateRowsAxpy(self, rows, coef, x, deterministic: bool = False, sync: bool = True,
@@ -684,6 +759,35 @@ class PartialMatrix(_Shard):
         res = self._host_out(out, (r.size, self.cols))
         check(self.lib.glint_mat_pull_rows(self.handle, r.ctypes.data, res.ctypes.data, r.size), self.handle)
         return res
+
+    def getRowsAs(self, rows, wire: str, out=None, sync: bool = True):
+        """Narrow-format row pull (an extension; glint_mat_pull_rows_as*): ``getRows`` rounded on the shard to
+        the wire type ``wire`` -- 'float16' or 'bfloat16' for a Float shard, 'float32' for a Double shard --
+        one round-to-nearest-even of each stored value, so half the bytes are copied back. Host rows give an
+        (n, cols) numpy array of float16, of uint16 bfloat16 bit patterns (``from_bfloat16`` widens them) or of
+        float32; device rows a torch tensor of that type."""
+        code, np_wire, torch_name = resolve_wire(wire)
+        if _is_torch_cuda(rows):
+            import torch
+            wdt = getattr(torch, torch_name)
+            if out is None:
+                out = torch.empty((rows.numel(), self.cols), dtype=wdt, device=rows.device)
+            elif _is_torch_cuda(out) and out.dtype != wdt:
+                raise ValueError(f"out: dtype {out.dtype}, expected {wdt} for wire type {wire!r}")
+            self._check_dev(rows.numel(), rows, out=out, out_elems=rows.numel() * self.cols, wire_dtype=wdt)
+            rc = self.lib.glint_mat_pull_rows_as_dev(self.handle, rows.data_ptr(), out.data_ptr(), rows.numel(), code,
+                                                     self._stream_of(rows))
+            self._dev_done(rc, rows, sync)
+            return out
+        r = _host(rows, np.int64).reshape(-1)
+        shape = (r.size, self.cols)
+        if out is None:
+            out = np.empty(shape, dtype=np_wire)
+        elif not isinstance(out, np.ndarray) or out.dtype != np_wire or out.shape != shape \
+                or not out.flags.c_contiguous or not out.flags.writeable:
+            raise ValueError(f"out must be a writable C-contiguous {np.dtype(np_wire).name} array of shape {shape}")
+        check(self.lib.glint_mat_pull_rows_as(self.handle, r.ctypes.data, out.ctypes.data, r.size, code), self.handle)
+        return out
 
     def getRowsSparse(self, rows, cap: Optional[int] = None, sync: bool = True):
         """The non-zero elements of the requested rows as a CSR triple ``(indptr, cols, values)`` (an

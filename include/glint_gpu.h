@@ -474,6 +474,59 @@ int glint_mat_push_pairs_axpy(glint_shard_t dst, glint_shard_t src, const int64_
 int glint_mat_push_rows_grouped(glint_shard_t shard, const int64_t* rows, int64_t n, const int64_t* grp_ptr,
                                 int64_t g, const void* vals, const void* coef, int flags);
 
+/* Narrow-format row transport (an extension: the reference has no such message): whole rows cross the link
+ * in a narrower floating type W than the shard's type V, while the shard keeps full precision -- a
+ * full-precision master table whose rows and gradient rows travel as half or bfloat16. A pull rounds on the
+ * device, a push widens inside its fold, so sizeof W bytes per element are staged or copied back, never
+ * sizeof V.
+ * Pairs (V, W): (Float, F16), (Float, BF16), (Double, F32); glint_wire_supported answers 1 for these and 0 for
+ * everything else (any Int or Long shard, any unknown code) and never fails. The conversions are stated, in
+ * integer arithmetic, by glint_amd/csrc/glint_wire_plan.h:
+ *   narrowing V -> W (a pull): one IEEE round-to-nearest-even of the stored value straight to W. Results that
+ *     are subnormal in W are kept, never flushed; a magnitude that rounds beyond W's largest finite value
+ *     becomes the infinity of its sign; infinities and the sign of a zero are kept; a value too small for W's
+ *     smallest subnormal becomes the zero of its sign, and the tie at half the smallest subnormal goes to zero
+ *     (the even result); a NaN becomes a NaN of W, payload and sign unspecified. For BF16 the non-NaN rule on
+ *     the float's bits u is (u + 0x7FFF + ((u >> 16) & 1)) >> 16.
+ *   widening W -> V (a push): exact. W's subnormals become the equal V values, -0 stays -0, infinities stay
+ *     infinities, a NaN becomes a NaN, payload and sign unspecified.
+ * F16 and BF16 values are 16-bit patterns (IEEE binary16; the upper half of a binary32), F32 values floats. */
+enum glint_wire { GLINT_WIRE_F16 = 0, GLINT_WIRE_BF16 = 1, GLINT_WIRE_F32 = 2 };
+int glint_wire_supported(int dtype, int wire); /* 1 or 0; never fails */
+
+/* glint_mat_pull_rows in the wire type `wire`: out is n x cols values of W, dense row-major (NO pitch), in the
+ * caller's order -- a row requested twice is answered twice -- and out[i][c] = narrow(the stored element): the
+ * bits equal narrowing what glint_mat_pull_rows returns. Only `cols` elements of a row are read, never the
+ * pitch padding, and nothing beyond n * cols * sizeof W bytes of out is written. No flags, no atomics, one
+ * launch; the answer is a function of the shard and rows only, never of out's alignment.
+ * The shard is entered as by the other extensions' host calls (the open ring batch flushed, after enqueued
+ * messages and the last device-resident call; a slab with views refused); there is no ring path. Every row is
+ * checked before anything is staged: for the lowest i with rows[i] outside the partition the call returns
+ * GLINT_EOUTOFRANGE (i in glint_shard_last_error) with nothing written. Staged to the device: 8 n bytes;
+ * copied back: n * cols * sizeof W bytes -- never n * cols * sizeof V.
+ * GLINT_EINVAL: a NULL or vector shard; a (dtype, wire) pair that is not supported; n < 0; n >= 2^31; NULL rows
+ * or out with n > 0. n == 0 launches nothing and returns GLINT_OK. Kernel timing: the one launch counts under
+ * GLINT_K_MAT_PULL_ROWS. */
+int glint_mat_pull_rows_as(glint_shard_t shard, const int64_t* rows, void* out, int64_t n, int wire);
+
+/* glint_mat_push_rows of rows that arrive in the wire type `wire`: vals is n x cols values of W, dense
+ * row-major (NO pitch), and the call is glint_mat_push_rows(shard, rows, widened, n, flags) with
+ * widened[i][c] = widen(vals[i][c]), rounding for rounding: the sums run in V, the shard's element is a sum's
+ * first term and the contributions are added in list order. Flags, order, the size limit (n < 2^32 - 2048),
+ * the row check and the error reporting are glint_mat_push_rows's: repeated rows keep the push order unless
+ * GLINT_PUSH_UNORDERED is given, a row that occurs once is bit-exact in every mode, and on a row outside the
+ * partition nothing is applied (GLINT_EOUTOFRANGE, the record's index in glint_shard_last_error). A slab with
+ * views is refused. Only `cols` elements of a row are read and written, never the pitch padding.
+ * Staged to the device in one block: 8 n + n * cols * sizeof W bytes. Nothing of size n * cols * sizeof V is
+ * staged or built in device scratch: the widening happens at the contribution load inside the fold. Nothing
+ * is copied back.
+ * GLINT_EINVAL: a NULL or vector shard; a (dtype, wire) pair that is not supported; n < 0; n >= 2^32 - 2048;
+ * NULL rows or vals with n > 0; GLINT_PUSH_VALIDATE or an unknown flag. n == 0 launches nothing and returns
+ * GLINT_OK. Kernel timing: the front end counts as glint_mat_push_rows's does and the one fold launch under
+ * GLINT_K_PUSH_ROWS. */
+int glint_mat_push_rows_as(glint_shard_t shard, const int64_t* rows, const void* vals, int64_t n, int wire,
+                           int flags);
+
 /* Top-k row pull (an extension: the reference has no such message): for each of q query vectors, the k
  * rows of the shard that score highest against it -- nearest-row search, candidate retrieval -- answered
  * with q x k (row, score) pairs whatever the shard's size.
@@ -635,6 +688,25 @@ int glint_mat_push_pairs_axpy_dev(glint_shard_t dst, glint_shard_t src, const in
  * element; coef element by element: the same bits either way. */
 int glint_mat_push_rows_grouped_dev(glint_shard_t shard, const int64_t* rows, int64_t n, const int64_t* grp_ptr,
                                     int64_t g, const void* vals, const void* coef, int flags, void* stream);
+
+/* glint_mat_pull_rows_as, device-resident: the same bits, one launch, stream-ordered on `stream` with no host
+ * synchronisation (a device call like glint_mat_pull_rows_dev). A row outside the partition is answered with
+ * zeros -- bit pattern 0, written without a load -- and reported by glint_shard_sync as the lowest such
+ * request index; the other rows are served. When cols * sizeof V is a multiple of 16 and out is 8-B aligned,
+ * a lane turns 16 B of shard row into 8 B of out; else the kernel goes element by element. out may have any
+ * W-element alignment: the same bits either way. */
+int glint_mat_pull_rows_as_dev(glint_shard_t shard, const int64_t* rows, void* out, int64_t n, int wire,
+                               void* stream);
+/* glint_mat_push_rows_as, device-resident: the same contributions, stream-ordered on `stream` with no host
+ * synchronisation (a device call like glint_mat_push_rows_dev). A row outside the partition is skipped and
+ * reported by glint_shard_sync (the lowest such record index); the other records are applied. A row that
+ * occurs once in the push is bit-exact; sums of repeated rows keep the push order with
+ * GLINT_PUSH_DETERMINISTIC, else runs longer than 128 records are split and their partial sums added with
+ * atomics. vals is read by 8 B per lane -- the columns of the lane's 16 B of shard row -- when it is 8-B
+ * aligned and cols * sizeof V is a multiple of 16, else element by element; it may have any W-element
+ * alignment: the same bits either way. */
+int glint_mat_push_rows_as_dev(glint_shard_t shard, const int64_t* rows, const void* vals, int64_t n, int wire,
+                               int flags, void* stream);
 
 /* glint_vec_push_dev / glint_mat_push_dev behind a device-side gate: the push is enqueued at once,
  * and when it runs it applies NOTHING if the 64-bit device word *gate is nonzero (a route status word,
@@ -805,7 +877,7 @@ enum glint_kernel_id {
   GLINT_K_PUSH_SCATTER = 1, /* LDS-aggregated atomic push of the unordered tail */
   GLINT_K_VEC_PULL = 2,
   GLINT_K_MAT_PULL = 3,
-  GLINT_K_MAT_PULL_ROWS = 4,
+  GLINT_K_MAT_PULL_ROWS = 4, /* also the one launch of a narrow-format row pull (glint_mat_pull_rows_as*) */
   GLINT_K_PUSH_CHECK = 5,   /* order / affinity check over the keys in front of push_apply */
   GLINT_K_PUSH_BINNED = 6,  /* the binned unordered-push pipeline (count, partition, apply) */
   GLINT_K_PUSH_ORDERED = 7, /* the order-preserving push of message-sized pushes (one launch) */
@@ -813,7 +885,8 @@ enum glint_kernel_id {
    * non-empty Adagrad or Adam row push (glint_mat_push_rows_adagrad*, glint_mat_push_rows_adam*), recorded
    * on its weights shard only. Also
    * the one launch of a shard fill or uniform init (glint_shard_fill*, glint_shard_init_uniform*), and the
-   * one fold launch of a non-empty grouped row push (glint_mat_push_rows_grouped*) */
+   * one fold launch of a non-empty grouped row push (glint_mat_push_rows_grouped*) or narrow-format row push
+   * (glint_mat_push_rows_as*) */
   GLINT_K_PUSH_ROWS = 8,
   /* the sparse row pull (glint_mat_pull_rows_sparse*): its emit kernel, and under the same id its
    * count kernel and the launches of its scan, so the sum is the pull's whole device time */
