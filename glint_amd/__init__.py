@@ -14,9 +14,11 @@ from .errors import (ArrayIndexOutOfBoundsException, GlintDeviceError,  # noqa: 
 from .partitioning import (CyclicPartition, CyclicPartitioner, RangePartition,  # noqa: E402
                            RangePartitioner)
 from .shard import PartialMatrix, PartialVector, from_bfloat16, to_bfloat16  # noqa: E402
+from .sampler import Sampler  # noqa: E402
 from .client import BigMatrix, BigVector, Client  # noqa: E402
 
 __all__ = [
+    "Sampler",
     "PartialVector", "PartialMatrix", "RangePartition", "RangePartitioner", "CyclicPartition",
     "CyclicPartitioner", "Client", "BigVector", "BigMatrix", "IndexOutOfBoundsException",
     "ArrayIndexOutOfBoundsException", "GlintDeviceError", "ModelCreationException", "to_bfloat16", "from_bfloat16",

@@ -32,6 +32,7 @@ GLINT_TOPK_MAX_K, GLINT_TOPK_MAX_QUERIES, GLINT_TOPK_TILE = 1024, 64, 4096
 GLINT_ROUTE_RANGE, GLINT_ROUTE_CYCLIC = 0, 1
 GLINT_RING_SLOTS, GLINT_ZERO_COPY_MAX = 16, 4096
 GLINT_SPARSE_SCAN_TILE = 1024
+GLINT_SAMPLE_MAX_TRIES, GLINT_SAMPLE_COARSE = 8, 4096
 
 # every symbol include/glint_gpu.h declares, with its C signature
 _P = C.c_void_p
@@ -110,6 +111,13 @@ SIGNATURES = {
     "glint_scatter_rows_dev": (_I, [_P, _P, _I64, _I64, _P, _P]),
     "glint_copy_segments_dev": (_I, [_P, _P, C.POINTER(_I64), _I, _P]),
     "glint_send_matrix_dev": (_I, [_P, _P, _I32, _I32, _P, _P, _P]),
+    "glint_sampler_create": (_I, [_I, _P, _I64, _I64, C.POINTER(_I64), C.POINTER(_P)]),
+    "glint_sampler_create_dev": (_I, [_I, _P, _I64, _I64, _P, C.POINTER(_I64), C.POINTER(_P)]),
+    "glint_sampler_create_from_shard": (_I, [_P, C.POINTER(_I64), C.POINTER(_P)]),
+    "glint_sampler_destroy": (_I, [_P]),
+    "glint_sampler_info": (_I, [_P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I)]),
+    "glint_sampler_draw": (_I, [_P, C.c_uint64, C.c_uint64, _I64, _P, _I64, _P]),
+    "glint_sampler_draw_dev": (_I, [_P, C.c_uint64, C.c_uint64, _I64, _P, _I64, _P, _P]),
     "glint_prof_enable": (_I, [_P, _I]),
     "glint_prof_read": (_I, [_P, _I, C.POINTER(C.c_double), C.POINTER(_I64)]),
     "glint_prof_read_launches": (_I, [_P, _I, C.POINTER(C.c_double), _I64, C.POINTER(_I64)]),

@@ -28,11 +28,11 @@ HIP_SOURCES = [CSRC / "glint_gpu.hip", CSRC / "glint_sort.hip", CSRC / "glint_ro
                CSRC / "glint_rowsum.hip", CSRC / "glint_rowdot.hip", CSRC / "glint_rowaxpy.hip",
                CSRC / "glint_topk.hip", CSRC / "glint_rowadagrad.hip", CSRC / "glint_pairs.hip",
                CSRC / "glint_init.hip", CSRC / "glint_rowgroup.hip", CSRC / "glint_rowadam.hip",
-               CSRC / "glint_rowwire.hip"]
-# plain C++: the push planners, the top-k pull's level plan, the uniform init's value contract and the
-# narrow-format row transport's conversion contract
+               CSRC / "glint_rowwire.hip", CSRC / "glint_sample.hip"]
+# plain C++: the push planners, the top-k pull's level plan, the uniform init's value contract, the
+# narrow-format row transport's conversion contract and the row sampler's value contract
 PLAN_HEADERS = [CSRC / "glint_push_plan.h", CSRC / "glint_bin_plan.h", CSRC / "glint_topk_plan.h",
-                CSRC / "glint_init_plan.h", CSRC / "glint_wire_plan.h"]
+                CSRC / "glint_init_plan.h", CSRC / "glint_wire_plan.h", CSRC / "glint_sample_plan.h"]
 HIP_HEADERS = [CSRC / "glint_kernels.h", CSRC / "glint_device.h", CSRC / "glint_host.h", CSRC / "glint_dot.h",
                CSRC / "glint_axpy.h",
                ROOT / "include" / "glint_gpu.h", *PLAN_HEADERS]
@@ -254,6 +254,28 @@ def build_wire_probe(force: bool = False, verbose: bool = False) -> Path:
     return WIRE_PROBE
 
 
+SAMPLER_PROBE_SRC = ROOT / "tests" / "c" / "sampler_probe.cpp"
+SAMPLER_PROBE = ROOT / "tests" / "c" / "build" / "libsampler_probe.so"
+
+
+def build_sampler_probe(force: bool = False, verbose: bool = False) -> Path:
+    """The row sampler's value contract (glint_sample_plan.h: the attempt, the search and the exclusion rule
+    over a host cdf) as a host-only library: what tests/test_sampler_cpu.py loads. Compiled by g++ alone."""
+    deps = [SAMPLER_PROBE_SRC, CSRC / "glint_sample_plan.h", CSRC / "glint_init_plan.h"]
+    if not force and not _stale(SAMPLER_PROBE, deps):
+        return SAMPLER_PROBE
+    SAMPLER_PROBE.parent.mkdir(parents=True, exist_ok=True)
+    tmp = SAMPLER_PROBE.with_suffix(".so.tmp")
+    cxx = shutil.which("g++") or "c++"
+    cmd = [cxx, "-O2", "-std=c++17", "-Wall", "-Werror", "-Wno-unknown-pragmas", "-fPIC", "-shared", "-o", str(tmp),
+           str(SAMPLER_PROBE_SRC)]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True, cwd=str(ROOT))
+    os.replace(tmp, SAMPLER_PROBE)
+    return SAMPLER_PROBE
+
+
 def build_all(force: bool = False, verbose: bool = False) -> None:
     build_gpu_lib(force=force, verbose=verbose)
     build_oracle(force=force, verbose=verbose)
@@ -264,6 +286,7 @@ def build_all(force: bool = False, verbose: bool = False) -> None:
     build_topk_probe(force=force, verbose=verbose)
     build_init_probe(force=force, verbose=verbose)
     build_wire_probe(force=force, verbose=verbose)
+    build_sampler_probe(force=force, verbose=verbose)
 
 
 if __name__ == "__main__":

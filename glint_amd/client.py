@@ -618,5 +618,15 @@ class Client:
                                            lambda part, dev: PartialMatrix(part, cols, dtype, dev))
         return BigMatrix(partitioner, shards, rows, cols)
 
+    def sampler(self, weights, firstKey: int = 0, device: Optional[int] = None):
+        """A seeded weighted row sampler (glint_amd.sampler.Sampler; an extension) over integer ``weights``,
+        entry i the weight of key ``firstKey + i``, on ``device`` or the client's first device."""
+        from .sampler import Sampler
+        if device is None:
+            if not self.devices:
+                raise ModelCreationException("Cannot create a sampler without active parameter servers")
+            device = self.devices[0]
+        return Sampler(weights, firstKey, device)
+
 
 __all__ = ["Client", "BigVector", "BigMatrix", "bucket", "RangePartitioner", "CyclicPartitioner"]

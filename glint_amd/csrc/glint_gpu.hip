@@ -1599,7 +1599,7 @@ std::atomic<unsigned> g_env_gen{1};
 
 extern "C" {
 
-int glint_version(void) { return 1300; }  // 0.13.0: glint_mat_pull_rows_as / glint_mat_push_rows_as / _dev
+int glint_version(void) { return 1400; }  // 0.14.0: glint_sampler_* (the seeded weighted row sampler)
 
 int glint_wire_supported(int dtype, int wire) { return wire_supported(dtype, wire) ? 1 : 0; }
 
@@ -2928,6 +2928,21 @@ int glint_shard_fill(glint_shard_t s, const int64_t* rows, int64_t n, const void
 int glint_shard_init_uniform(glint_shard_t s, const int64_t* rows, int64_t n, uint64_t seed, double lo, double hi) {
   InitSpec sp{};
   return host_init(s, uniform_args(s, rows, n, seed, lo, hi, &sp), rows, n, sp);
+}
+
+// A sampler over a counts shard (glint_sample.hip builds it): the shard is entered as by the host-pointer
+// calls and only read; the build runs on the shard's stream and ends synchronised.
+int glint_sampler_create_from_shard(glint_shard_t s, int64_t* first_bad, glint_sampler_t* out) {
+  if (out) *out = nullptr;
+  if (first_bad) *first_bad = -1;
+  if (!out || !s || s->part.cols != 0 || s->part.kind != 0 || (s->dtype != GLINT_I32 && s->dtype != GLINT_I64) ||
+      s->part.size < 1)
+    return GLINT_EINVAL;
+  ShardLock lk(s);
+  DeviceGuard g(s->device);
+  if (int rc = host_enter(s, HostEntry::OrderFlush)) return rc;
+  return sampler_build(s->device, s->data, s->dtype == GLINT_I32, s->part.size, s->part.start, s->stream, first_bad,
+                       out);
 }
 
 int glint_vec_push(glint_shard_t s, const int64_t* keys, const void* vals, int64_t n, int flags) {

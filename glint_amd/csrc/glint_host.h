@@ -565,6 +565,13 @@ int push_rows_wire(glint_shard* s, const i64* rows, const void* vals, i64 n, int
 // synchronisation.
 int shard_init(glint_shard* s, const i64* rows, i64 n, bool list, bool uniform, u64 seed, u64 a, u64 b,
                hipStream_t st);
+// row sampler (glint_sample.hip): builds a sampler over the m weights at w (device memory of `device`, the
+// current device; Int when w32, else Long) as include/glint_gpu.h fixes, entry i standing for key first_key +
+// i. The weight check, the scan and the coarse table are enqueued on st and the call ends with st
+// synchronised; w is only read. *out stays NULL on any error; *first_bad (may be NULL) = the lowest index of
+// a weight outside [0, 2^32) when that is the error (GLINT_EOUTOFRANGE).
+int sampler_build(int device, const void* w, bool w32, i64 m, i64 first_key, hipStream_t st, int64_t* first_bad,
+                  glint_sampler** out);
 // sparse row pull (glint_sparse.hip), instantiated for the same V. sparse_count_scan: row_ptr[0..n]
 // (device) = exclusive prefix of the requested rows' non-zero counts; rows outside the partition
 // count 0 and are recorded in err_of(s); the scan's scratch is s->d_det. sparse_emit: the entries

@@ -868,6 +868,67 @@ int glint_copy_segments_dev(const void* src, void* dst, const int64_t* segs, int
 int glint_send_matrix_dev(const int64_t* counts, const int64_t* cells, int32_t nparts, int32_t ncells,
                           const uint64_t* bad_dev, int64_t* send, void* stream);
 
+/* ---- row sampler (device) ------------------------------------------------------------------ *
+ * Seeded weighted sampling of rows on the device (an extension: the word2vec forks of the reference draw
+ * their negatives on the servers from a seed; the reference itself has no such message): what a skip-gram
+ * or two-tower step needs besides the pair calls, so that no sampled id crosses the link. A sampler is an
+ * immutable table on one device, built once from integer weights; it is not a shard. Every draw is a
+ * function of the table, the seed and the draw's counter only, so the scoring call and the later adjusting
+ * call regenerate the same negatives from (seed, first), on any rank, in any batch split.
+ * Table: m weights w[0 .. m), 1 <= m < 2^31, each 0 <= w[i] < 2^32, their total T >= 1 (T < 2^63: no sum
+ * overflows, in any order). cdf[i] = w[0] + ... + w[i] (inclusive) in 64 bits. Entry i stands for the
+ * global key first_key + i.
+ * One attempt, for draw counter d (uint64), attempt t (uint32) and seed (uint64):
+ *   (o0, o1, o2, o3) = Philox4x32-10(counter (lo32(d), hi32(d), t, 1), key (lo32(seed), hi32(seed)))
+ * -- counter word 3 is 1 where glint_shard_init_uniform has 0, so the two streams of one seed are disjoint --
+ *   r = o0 | (uint64)o1 << 32;  x = floor(r * T / 2^64), the high 64 bits of the 128-bit product (0 <= x < T);
+ *   idx = the smallest i with cdf[i] > x.
+ * A zero-weight entry is never drawn; runs of equal cdf values are followed to their end.
+ * One draw: draw i of a call has counter d = first + i (mod 2^64). Without exclusion it is attempt 0. With
+ * exclusion the caller passes `exclude`, ceil(n / per) global keys, and per >= 1: draw i avoids forb =
+ * exclude[i / per] (the positive that the `per` negatives are drawn for). Attempts t = 0 .. GLINT_SAMPLE_MAX_TRIES
+ * - 1 are made in order and the first whose key differs from forb is the draw; if all hit forb the draw is
+ * the next entry of non-zero weight after it, cyclically (the smallest i with cdf[i] > cdf[forb] mod T), so a
+ * draw equals forb only when forb is the table's only non-zero entry. A forb outside [first_key, first_key +
+ * m) excludes nothing. The answer is a function of (weights, first_key, seed, first, i, exclude, per) only:
+ * never of n, of how a range of counters is split over calls, of the grid, of pointer alignment or of the
+ * shape of the search (glint_amd/csrc/glint_sample_plan.h states it as code).
+ * Creates (synchronous, one-time calls): glint_sampler_create stages host weights; _create_dev reads device
+ * memory after the work already on `stream`; _create_from_shard reads a range vector shard of Int or Long
+ * -- counts accumulated by ordinary pushes -- entered as by the host-pointer calls (the open ring batch
+ * flushed, after enqueued messages and the last device-resident call, a slab with views refused), with the
+ * shard's start as first_key and its size as m; the shard is only read. The weights are checked on the
+ * device: for the lowest i with w[i] < 0 or w[i] >= 2^32 the create returns GLINT_EOUTOFRANGE and stores i in
+ * *first_bad (which may be NULL; -1 is stored otherwise). GLINT_EINVAL: a NULL `out` or weights pointer, m <
+ * 1, m >= 2^31, T == 0; from a shard: a NULL, matrix, Float, Double or cyclic shard. No handle is produced
+ * on any error (*out = NULL). The table costs 8 m bytes plus the coarse table; nothing else of the
+ * build is kept (a sampler that has served a host draw also keeps that call's stream and staging buffer, at
+ * most 2^22 draws' worth).
+ * Draws: out receives n global keys. exclude == NULL: no exclusion, per is ignored. GLINT_EINVAL: a NULL
+ * sampler; n < 0; n >= 2^31; a NULL out with n > 0; a non-NULL exclude with per < 1. n == 0 launches nothing.
+ * glint_sampler_draw (host pointers) stages exclude (8 ceil(n / per) bytes), copies back 8 n bytes and ends
+ * synchronised; host calls on one sampler are serialised internally. glint_sampler_draw_dev (device
+ * pointers) is one launch on `stream`: no host synchronisation, no scratch, no lock -- a sampler is
+ * immutable, so any number of streams may draw from it at once; destroy it after they have drained.
+ * Kernel timing: a sampler is not a shard and has no kernel id; time it with events on `stream`. */
+typedef struct glint_sampler* glint_sampler_t;
+#define GLINT_SAMPLE_MAX_TRIES 8
+/* Entries of the coarse table the search narrows in first (tests size their cases by it; the bits never
+ * depend on it). */
+#define GLINT_SAMPLE_COARSE 4096
+int glint_sampler_create(int device, const int64_t* weights, int64_t m, int64_t first_key, int64_t* first_bad,
+                         glint_sampler_t* out);
+int glint_sampler_create_dev(int device, const int64_t* weights_dev, int64_t m, int64_t first_key, void* stream,
+                             int64_t* first_bad, glint_sampler_t* out);
+int glint_sampler_create_from_shard(glint_shard_t counts, int64_t* first_bad, glint_sampler_t* out);
+int glint_sampler_destroy(glint_sampler_t sampler);
+/* Any of the four may be NULL. total = T. */
+int glint_sampler_info(glint_sampler_t sampler, int64_t* m, int64_t* first_key, int64_t* total, int* device);
+int glint_sampler_draw(glint_sampler_t sampler, uint64_t seed, uint64_t first, int64_t n, const int64_t* exclude,
+                       int64_t per, int64_t* out);
+int glint_sampler_draw_dev(glint_sampler_t sampler, uint64_t seed, uint64_t first, int64_t n,
+                           const int64_t* exclude, int64_t per, int64_t* out, void* stream);
+
 /* ---- kernel timing ------------------------------------------------------------------------- *
  * With profiling on, every kernel launch of the shard is bracketed by HIP events recorded on the
  * stream it is launched on; glint_prof_read waits for them and returns the summed device time and

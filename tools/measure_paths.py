@@ -5,7 +5,7 @@ the JNI shim sees. One JSON line per measurement on stdout.
 
     python tools/measure_paths.py [--quick] [--sparse] [--rowsum] [--dot] [--axpy [--out FILE]] [--topk [--out FILE]]
                                   [--adagrad [--out FILE]] [--pairs [--out FILE]] [--init [--out FILE]]
-                                  [--groups [--out FILE]] [--adam [--out FILE]]
+                                  [--groups [--out FILE]] [--adam [--out FILE]] [--sampler [--out FILE]]
 
 --sparse runs only the sparse-row-pull leg (dense getRows against getRowsSparse on a cfg5 shard).
 --rowsum runs only the grouped row-sum leg (getRowsSum against a dense row pull plus a reduction by the
@@ -32,6 +32,9 @@ profiles/groups/groups.jsonl (or FILE).
 --adam runs only the Adam row push leg (updateRowsAdam against coalescing, row pulls of weights and moments,
 the step and two row pushes by the caller, on cfg5 shards, with the Adagrad fold on the same rows beside it)
 and appends its lines to profiles/adam/adam_push.jsonl (or FILE).
+--sampler runs only the row sampler leg (glint_sampler_draw_dev against torch.rand plus torch.searchsorted over a
+device cdf, at m = 2^20 Zipf counts and n = 2^24 draws, with and without exclusion; the creates and the host
+draw by wall clock) and appends its lines to profiles/sampler/sampler.jsonl (or FILE).
 """
 import ctypes as C
 import json
@@ -1180,6 +1183,101 @@ def init_leg(rng, out_path):
         s2.destroy()
 
 
+def sampler_leg(rng, out_path):
+    """The row sampler at word2vec size: m = 2^20 Zipf(1.0) counts, n = 2^24 draws, without exclusion and with
+    it at per = 5 (the positives drawn from the same table, so the hot keys are excluded often). HIP-event time
+    of glint_sampler_draw_dev against what a device caller does today -- torch.rand, a scale to the total and
+    torch.searchsorted over a device cdf; with exclusion, one redraw of the draws that hit their positive --
+    alternating inside each of 5 rounds of one process after one warm-up round. Also the wall time of the
+    creates (host weights, device weights) and of a host draw of the same n. One JSON line per case, also
+    appended to out_path."""
+    m, n, per, rounds = 1 << 20, 1 << 24, 5, 5
+    counts = np.maximum((1 << 24) // rng.permutation(np.arange(1, m + 1, dtype=np.int64)), 1)  # ~ 1 / rank, shuffled
+    d_counts = torch.from_numpy(counts).to(dev)
+    cdf = torch.cumsum(d_counts, 0)
+    total = int(cdf[-1])
+
+    def ev_ms(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b)
+
+    def wall_ms(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, r
+
+    def stats(ms):
+        return {"mean": float(np.mean(ms)), "min": float(np.min(ms)), "max": float(np.max(ms))}
+
+    create_host, create_dev = [], []
+    for rnd in range(3):
+        ms, s = wall_ms(lambda: glint_amd.Sampler(counts, device=0))
+        s.destroy()
+        create_host.append(ms)
+        ms, s = wall_ms(lambda: glint_amd.Sampler(d_counts))
+        create_dev.append(ms)
+        if rnd < 2:
+            s.destroy()
+    assert s.info() == (m, 0, total, 0)
+    out = torch.empty(n, dtype=torch.int64, device=dev)
+    pos = s.draw(-(-n // per), 1, 1 << 40, out=torch.empty(-(-n // per), dtype=torch.int64, device=dev))
+    pos_rep = pos.repeat_interleave(per)[:n]
+    seed = [0]
+    Path(out_path).parent.mkdir(parents=True, exist_ok=True)
+    for label, ex in (("plain", None), ("exclude_per5", pos)):
+        def draw():
+            seed[0] += 1
+            assert lib.glint_sampler_draw_dev(s.handle, seed[0], seed[0] * n, n, None if ex is None else ex.data_ptr(),
+                                              per, out.data_ptr(), stream) == 0
+
+        def base_once():
+            x = (torch.rand(n, dtype=torch.float64, device=dev) * total).to(torch.int64)
+            return torch.searchsorted(cdf, x, right=True)
+
+        def base():
+            idx = base_once()
+            if ex is not None:
+                idx = torch.where(idx == pos_rep, base_once(), idx)
+            return idx
+
+        def host_draw():
+            return s.draw(n, 7, 0, exclude=None if ex is None else pos.cpu().numpy(), per=per)
+
+        t = {"draw": [], "base": [], "host": []}
+        for rnd in range(rounds + 1):
+            for k, fn in (("draw", draw), ("base", base)):
+                torch.cuda.synchronize()
+                v = ev_ms(fn)
+                if rnd:
+                    t[k].append(v)
+            if rnd in (1, 2):
+                t["host"].append(wall_ms(host_draw)[0])
+        got = out.cpu().numpy()
+        assert got.min() >= 0 and got.max() < m and (counts[got[:100000]] > 0).all()
+        if ex is not None:
+            assert not bool((out == pos_rep).any())  # (every excluded key has company in this table)
+        r = {k: stats(v) for k, v in t.items()}
+        line = dict(op="sampler_draw", m=m, n=n, exclusion=label, per=per if ex is not None else None, rounds=rounds,
+                    library=os.path.basename(os.environ.get("GLINT_GPU_LIB", "in-tree")),
+                    draw_dev_ms=r["draw"], device_baseline_ms=r["base"], host_draw_wall_ms=r["host"],
+                    Gdraws_per_s=n / (r["draw"]["mean"] * 1e-3) / 1e9,
+                    speedup_device=r["base"]["mean"] / r["draw"]["mean"],
+                    create_host_wall_ms=stats(create_host[1:]), create_dev_wall_ms=stats(create_dev[1:]),
+                    link_bytes={"draw_dev": 0, "host_draw": 8 * n + (8 * (-(-n // per)) if ex is not None else 0)},
+                    note="the baseline draws float64 uniforms (53 bits, not reproducible across batch splits) and, with "
+                         "exclusion, redraws once; it also writes and reads n x 8 B of uniforms in HBM")
+        emit(**line)
+        with open(out_path, "a") as f:
+            f.write(json.dumps(line) + "\n")
+    s.destroy()
+
+
 def topk_leg(rng, out_path):
     """cfg5 per GPU: a 2^17 x 512 Double shard, the k = 16 best rows against q = 1, 8 and 64 query vectors.
     Host: glint_mat_pull_topk against glint_mat_pull_rows_dot over arange(size) + np.argpartition, wall time;
@@ -1319,6 +1417,11 @@ def topk_leg(rng, out_path):
 
 
 def main():
+    if "--sampler" in sys.argv:
+        out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
+            str(Path(__file__).resolve().parent.parent / "profiles" / "sampler" / "sampler.jsonl")
+        sampler_leg(np.random.default_rng(42), out)
+        return
     if "--topk" in sys.argv:
         out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
             str(Path(__file__).resolve().parent.parent / "profiles" / "topk" / "topk_pull.jsonl")
