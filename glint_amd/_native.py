@@ -28,6 +28,7 @@ GLINT_K_COUNT = 13
 GLINT_WIRE_F16, GLINT_WIRE_BF16, GLINT_WIRE_F32 = 0, 1, 2
 GLINT_DOT_MAX_QUERIES, GLINT_DOT_QUERY_TILE = 1024, 4
 GLINT_AXPY_MAX_VECTORS = 64
+GLINT_ROWWISE_KEEP_STRIPS = 4
 GLINT_TOPK_MAX_K, GLINT_TOPK_MAX_QUERIES, GLINT_TOPK_TILE = 1024, 64, 4096
 GLINT_ROUTE_RANGE, GLINT_ROUTE_CYCLIC = 0, 1
 GLINT_RING_SLOTS, GLINT_ZERO_COPY_MAX = 16, 4096
@@ -72,6 +73,8 @@ SIGNATURES = {
     "glint_mat_push_rows_adam": (_I, [_P, _P, _P, _P, _I64, C.c_double, C.c_double, C.c_double, C.c_double, _I64]),
     "glint_mat_push_rows_adam_dev": (_I, [_P, _P, _P, _P, _I64, C.c_double, C.c_double, C.c_double, C.c_double,
                                           _I64, _P]),
+    "glint_mat_push_rows_adagrad_rowwise": (_I, [_P, _P, _P, _P, _I64, C.c_double, C.c_double]),
+    "glint_mat_push_rows_adagrad_rowwise_dev": (_I, [_P, _P, _P, _P, _I64, C.c_double, C.c_double, _P]),
     "glint_mat_pull_pairs_dot": (_I, [_P, _P, _P, _P, _I64, _P]),
     "glint_mat_pull_pairs_dot_dev": (_I, [_P, _P, _P, _P, _I64, _P, _P]),
     "glint_mat_push_pairs_axpy": (_I, [_P, _P, _P, _P, _P, _I64, _I]),

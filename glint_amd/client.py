@@ -19,6 +19,8 @@ Mirrors the reference's client factory and asynchronous models, minus the Akka t
 * ``BigMatrix.pushAdagrad`` -- an extension: gradient rows summed per distinct row, then one Adagrad step
   of this matrix and of a second one that holds the accumulators, on the shards
   (PartialMatrix.updateRowsAdagrad).
+* ``BigMatrix.pushAdagradRowwise`` -- an extension: row-wise Adagrad, one accumulator per row held in a
+  ``BigVector`` with this matrix's partitioner (PartialMatrix.updateRowsAdagradRowwise).
 * ``BigMatrix.pushAdam`` -- an extension: the same with one lazy Adam step, the second matrix holding both
   moments of a row side by side in ``2 * cols`` columns (PartialMatrix.updateRowsAdam).
 * ``BigMatrix.pullSum`` -- an extension: the sums of groups of rows, reduced on the shards
@@ -312,6 +314,37 @@ class BigMatrix(_InitMixin):
             idx = order[off[p]:off[p + 1]]
             if idx.size:
                 sh.updateRowsAdagrad(state.shards[p], rows[idx], grads[idx], lr, eps)
+        return True
+
+    def pushAdagradRowwise(self, state: "BigVector", rows, grads, lr: float, eps: float = 1e-10) -> bool:
+        """Row-wise Adagrad row push (an extension): this matrix holds the weights and ``state`` -- a
+        BigVector with the same partitioner, ``size == rows`` and dtype -- one accumulator per row (zeros
+        to start with), so the optimizer state is ``1 / cols`` of the table. ``grads`` is (n, cols) or
+        flat. Per distinct row: its gradient rows are summed in the caller's order, then ``state += mean(G
+        * G)`` and ``weights -= (lr / (sqrt(state) + eps)) * G`` on the shard that holds the row
+        (PartialMatrix.updateRowsAdagradRowwise). ``state``, the shapes and -- by the partitioner -- every
+        row are validated before any shard is called. Bucketed by partition as ``pushRows``; one
+        PartialMatrix.updateRowsAdagradRowwise per non-empty partition, with its rows and gradient rows in
+        the caller's order and that partition's state shard. A row lives in one partition, so the bits are
+        the shard's."""
+        if not isinstance(state, BigVector):
+            raise ValueError("state: expected a BigVector")
+        dtype = self.shards[0].np_dtype
+        if state.size != self.rows or len(state.shards) != len(self.shards) \
+                or np.dtype(state.shards[0].np_dtype) != np.dtype(dtype) \
+                or not _same_partitioner(state.partitioner, self.partitioner):
+            raise ValueError("state: expected a vector with this matrix's partitioner, rows and dtype")
+        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        grads = np.ascontiguousarray(grads, dtype=dtype)
+        if grads.size != rows.size * self.cols:
+            raise ValueError(f"grads: {grads.size} elements, expected {rows.size} rows x {self.cols} columns")
+        grads = grads.reshape(rows.size, self.cols)
+        owner = self.partitioner.partition_indices(rows)
+        order, off = bucket(owner, len(self.shards))
+        for p, sh in enumerate(self.shards):
+            idx = order[off[p]:off[p + 1]]
+            if idx.size:
+                sh.updateRowsAdagradRowwise(state.shards[p], rows[idx], grads[idx], lr, eps)
         return True
 
     def pushAdam(self, state: "BigMatrix", rows, grads, lr: float, step: int, beta1: float = 0.9,

@@ -1356,6 +1356,22 @@ inline int push_adam_args(const glint_shard* w, const glint_shard* s, const void
   return GLINT_OK;
 }
 
+// argument checks of glint_mat_push_rows_adagrad_rowwise / _dev: push_adagrad_args' with a state that is
+// a vector shard (one accumulator per row) of the weights' type, device, size and partition; the two byte
+// ranges, each of its own shard's size, may not overlap
+inline int push_adagrad_rowwise_args(const glint_shard* w, const glint_shard* h, const void* rows, const void* grads,
+                                     int64_t n, double lr, double eps) {
+  if (!w || !h || w == h || w->part.cols == 0 || h->part.cols != 0) return GLINT_EINVAL;
+  if (w->dtype != GLINT_F32 && w->dtype != GLINT_F64) return GLINT_EINVAL;
+  if (!same_rows(w, h)) return GLINT_EINVAL;
+  const uintptr_t wa = (uintptr_t)w->data, ha = (uintptr_t)h->data;
+  if (wa < ha + (uintptr_t)h->elems * h->vsize && ha < wa + (uintptr_t)w->elems * w->vsize) return GLINT_EINVAL;
+  if (n < 0 || n >= ((i64)1 << 32) - kSortTile) return GLINT_EINVAL;
+  if (n > 0 && (!rows || !grads)) return GLINT_EINVAL;
+  if (lr != lr || !(eps >= 0)) return GLINT_EINVAL;
+  return GLINT_OK;
+}
+
 // argument checks of glint_mat_push_rows_grouped / _dev: glint_mat_push_rows's shard, flags and record count,
 // a 31-bit group count, the arrays present when they have elements (grp_ptr always: it has g + 1); coef may
 // be NULL
@@ -1599,7 +1615,7 @@ std::atomic<unsigned> g_env_gen{1};
 
 extern "C" {
 
-int glint_version(void) { return 1400; }  // 0.14.0: glint_sampler_* (the seeded weighted row sampler)
+int glint_version(void) { return 1500; }  // 0.15.0: glint_mat_push_rows_adagrad_rowwise* (one accumulator per row)
 
 int glint_wire_supported(int dtype, int wire) { return wire_supported(dtype, wire) ? 1 : 0; }
 
@@ -2060,6 +2076,17 @@ int glint_mat_push_rows_adam_dev(glint_shard_t weights, glint_shard_t state, con
     if (weights->dtype == GLINT_F64)
       return push_rows_adam<double>(weights, state, (const i64*)rows, grads, n, lr, beta1, beta2, eps, step, st);
     return push_rows_adam<float>(weights, state, (const i64*)rows, grads, n, lr, beta1, beta2, eps, step, st);
+  });
+}
+
+int glint_mat_push_rows_adagrad_rowwise_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows,
+                                            const void* grads, int64_t n, double lr, double eps, void* stream) {
+  const int args_rc = push_adagrad_rowwise_args(weights, state, rows, grads, n, lr, eps);
+  if (args_rc == GLINT_OK && n == 0) return GLINT_OK;
+  return dev_call2(weights, state, args_rc, stream, [&](hipStream_t st) -> int {
+    if (weights->dtype == GLINT_F64)
+      return push_rows_adagrad_rowwise<double>(weights, state, (const i64*)rows, grads, n, lr, eps, st);
+    return push_rows_adagrad_rowwise<float>(weights, state, (const i64*)rows, grads, n, lr, eps, st);
   });
 }
 
@@ -3180,6 +3207,24 @@ int glint_mat_push_rows_adam(glint_shard_t weights, glint_shard_t state, const i
                                                      stream);
                      return push_rows_adam<float>(weights, state, d_rows, st.p[1], n, lr, beta1, beta2, eps, step,
                                                   stream);
+                   });
+}
+
+// glint_mat_push_rows_adagrad_rowwise: glint_mat_push_rows_adagrad's host side word for word -- every row
+// checked against the weights shard under both locks before anything is staged, rows and grads staged in
+// one block, the push on the weights shard's stream behind the state vector's (its flushed ring entries
+// and open batch included), the call ends synchronised. Nothing comes back but the error state.
+int glint_mat_push_rows_adagrad_rowwise(glint_shard_t weights, glint_shard_t state, const int64_t* rows,
+                                        const void* grads, int64_t n, double lr, double eps) {
+  if (int rc = push_adagrad_rowwise_args(weights, state, rows, grads, n, lr, eps)) return rc;
+  if (n == 0) return GLINT_OK;
+  return host_call(weights, state, {rows, nullptr, n}, false,
+                   {{rows, (size_t)n * 8}, {grads, (size_t)n * (size_t)weights->part.cols * weights->vsize}}, 0,
+                   [&](const Staged& st, hipStream_t stream, HostBack*) -> int {
+                     const i64* d_rows = (const i64*)st.p[0];
+                     if (weights->dtype == GLINT_F64)
+                       return push_rows_adagrad_rowwise<double>(weights, state, d_rows, st.p[1], n, lr, eps, stream);
+                     return push_rows_adagrad_rowwise<float>(weights, state, d_rows, st.p[1], n, lr, eps, stream);
                    });
 }
 

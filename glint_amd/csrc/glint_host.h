@@ -523,6 +523,15 @@ int push_rows_adagrad(glint_shard* weights, glint_shard* state, const i64* rows,
 template <typename V>
 int push_rows_adam(glint_shard* weights, glint_shard* state, const i64* rows, const void* grads, i64 n, double lr,
                    double beta1, double beta2, double eps, i64 step, hipStream_t st);
+// row-wise Adagrad row push (glint_rowadagrad_rowwise.hip), instantiated for float and double: per distinct
+// row of the push, G as above, ss = the row dot pull's self-dot of G, then state element += ss / cols and
+// weights row -= (lr / (sqrt(state element) + eps)) * G, in the order include/glint_gpu.h fixes; `state` is
+// a vector shard of `weights`' type, size and partition. Rows outside the partition are skipped and
+// recorded in err_of(weights). The front end's launches (weights' scratch) and one fold launch on st, no
+// host synchronisation; under both shards' locks.
+template <typename V>
+int push_rows_adagrad_rowwise(glint_shard* weights, glint_shard* state, const i64* rows, const void* grads, i64 n,
+                              double lr, double eps, hipStream_t st);
 // row-pair dot pull (glint_pairs.hip), instantiated for V in {int, long long, float, double}: out[i] = the
 // dot of row rows_a[i] of `a` with row rows_b[i] of `b` (device pointers), each row array translated with
 // its own shard's partition, in the row dot pull's order; `b` has a's type, device and cols and may be

@@ -675,6 +675,40 @@ class PartialMatrix(_Shard):
                                                    float(lr), float(eps)), self.handle)
         return True
 
+    def updateRowsAdagradRowwise(self, state: "PartialVector", rows, grads, lr: float, eps: float = 1e-10,
+                                 sync: bool = True) -> bool:
+        """Row-wise Adagrad row push (an extension; glint_mat_push_rows_adagrad_rowwise*): this shard holds
+        the weights and ``state`` -- a PartialVector of the same type, device and partition -- one
+        accumulator per row, so the optimizer state is ``1 / cols`` of the table; a zeroed vector is the
+        initial state. ``grads`` is (n, cols) or flat, dense row-major. Per distinct row of ``rows``: ``G``
+        = its gradient rows added to +0 in push order, ``ss`` = the self-dot of ``G`` in ``getRowsDot``'s
+        order, then ``state += ss / cols`` and ``weights -= (lr / (sqrt(state) + eps)) * G``, every
+        operation rounded on its own in the shard's type (include/glint_gpu.h has the contract):
+        duplicates are coalesced, then one step is taken. There are no order flags: the call is
+        deterministic. Errors as ``updateRowsAdagrad``."""
+        if not isinstance(state, PartialVector):
+            raise TypeError("state: expected a PartialVector")
+        if np.dtype(self.np_dtype).kind != "f":
+            raise TypeError("updateRowsAdagradRowwise needs a Float or Double shard, not "
+                            f"{np.dtype(self.np_dtype).name}")
+        if _is_torch_cuda(rows) != _is_torch_cuda(grads):
+            raise TypeError("rows and grads: mixing host arrays and device tensors")
+        if _is_torch_cuda(rows):
+            n = rows.numel()
+            self._check_dev(n, rows, values=grads, value_elems=n * self.cols)
+            rc = self.lib.glint_mat_push_rows_adagrad_rowwise_dev(self.handle, state.handle, rows.data_ptr(),
+                                                                  grads.data_ptr(), n, float(lr), float(eps),
+                                                                  self._stream_of(rows))
+            self._dev_done(rc, rows, sync)
+            return True
+        r = _host(rows, np.int64).reshape(-1)
+        g = _host(grads, self.np_dtype).reshape(-1)
+        if g.size != r.size * self.cols:
+            raise ValueError(f"grads: {g.size} elements, expected {r.size} rows x {self.cols} columns")
+        check(self.lib.glint_mat_push_rows_adagrad_rowwise(self.handle, state.handle, r.ctypes.data, g.ctypes.data,
+                                                           r.size, float(lr), float(eps)), self.handle)
+        return True
+
     def updateRowsAdam(self, state: "PartialMatrix", rows, grads, lr: float, step: int, beta1: float = 0.9,
                        beta2: float = 0.999, eps: float = 1e-8, sync: bool = True) -> bool:
         """Adam row push (an extension; glint_mat_push_rows_adam*): this shard holds the weights and

@@ -382,6 +382,59 @@ int glint_mat_push_rows_adagrad(glint_shard_t weights, glint_shard_t state, cons
 int glint_mat_push_rows_adam(glint_shard_t weights, glint_shard_t state, const int64_t* rows, const void* grads,
                              int64_t n, double lr, double beta1, double beta2, double eps, int64_t step);
 
+/* Row-wise Adagrad row push (an extension: the reference has no such message): Adagrad with one
+ * accumulator per row, fed with the mean of the row's squared gradient -- the embedding frameworks' choice
+ * for very large tables -- so that the optimizer state is 1 / cols of the table. `weights` is a Float or
+ * Double matrix shard of type V; `state` is a VECTOR shard (cols == 0) of the same dtype, device, size and
+ * partition: element l of `state` is the accumulator of local row l. A zeroed vector is the right initial
+ * state; any other initial value is written with glint_shard_fill. One push crosses the link with n x cols
+ * gradients and nothing else.
+ *   grads  n x cols values of V, dense row-major, no pitch (glint_mat_push_rows_adagrad's grads).
+ * lr and eps are rounded once on the host to V: lr_V, eps_V; C = (V)cols, rounded once. For every distinct
+ * local row l the push names:
+ *   1. G[c] = (((+0 + g_i0[c]) + g_i1[c]) + ...) over the records i0 < i1 < ... with l(rows[i]) == l: the
+ *      sum runs in push order, in V, from +0 (the Adagrad push's step 1).
+ *   2. ss = the row dot pull's self-dot of G, with exactly the arithmetic stated at glint_mat_pull_rows_dot:
+ *      E = 16 / sizeof(V) when cols * sizeof(V) is a multiple of 16, else 1; column c belongs to lane
+ *      (c / E) % 64; each lane starts from +0 and adds acc = acc + (G[c] * G[c]) in ascending c, the product
+ *      rounded before the add; then the xor butterfly d = 32 .. 1. ss is a function of (type, cols, G) only.
+ *   3. The row scalars, with h = state[l], every operation in V and rounded on its own:
+ *        s = ss / C;  h' = h + s;  r = sqrt(h');  d = r + eps_V;  k = lr_V / d
+ *      s = ss / C is a division, not a multiplication by a reciprocal, and k = lr_V / d is one division per
+ *      row: one multiplier per row, as the frameworks define the step.
+ *   4. Per column, with w = weights[l][c]:  p = k * G[c];  w' = w - p  (no fused multiply-add: fma(-k, G, w)
+ *      is not the contract's). h' is stored to state[l] once, and w' to weights[l][c].
+ *   5. sqrt and / are IEEE correctly rounded; subnormal inputs and results are kept; infinities and NaN
+ *      follow IEEE (a NaN's payload and sign are unspecified). The row is coupled: one NaN gradient element
+ *      makes ss, h' and every w' of that row NaN. An overflowing G * G makes h' infinite and k zero, so
+ *      p = 0 * G, which is NaN where G is infinite. G = 0, h = 0, eps = 0 gives k = lr / 0 and p = inf * 0 =
+ *      NaN.
+ * Duplicates are coalesced, then one step is taken -- not one step per record. The step needs a row's whole
+ * sum, so no run is ever split and no atomic is used: there are no flags, and the answer is a function of
+ * the inputs only, never of the alignment of grads, of how wide rows are handled, or of the grid. A row the
+ * push does not name is neither read nor written in either shard, and the pitch padding of `weights` is
+ * never touched.
+ * Locks, ordering, errors and slabs are glint_mat_push_rows_adagrad's: both shards' locks are held, the
+ * call is ordered after both shards' earlier work -- the vector shard's ring entries and open batch
+ * included -- and is synchronous for both; every row is checked against `weights` before anything is
+ * staged, and a row outside the partition returns GLINT_EOUTOFRANGE (the record's index in
+ * glint_shard_last_error(weights)) with both shards unchanged. A slab with views is refused for either
+ * shard.
+ * GLINT_EINVAL: a NULL, vector, Int or Long `weights`; a NULL `state`, one that is a matrix, one that
+ * differs from `weights` in dtype, device, size or partition (kind, start, and index / parts for cyclic),
+ * or one that shares memory with it; n < 0, n >= 2^32 - 2048; NULL rows or grads with n > 0; a NaN lr;
+ * !(eps >= 0). n == 0 launches nothing and returns GLINT_OK. Staged to the device: rows and grads in one
+ * block; nothing is copied back. Kernel timing: the front end counts as the row push's does and the one
+ * fold launch counts under GLINT_K_PUSH_ROWS on `weights`; nothing is recorded on `state`.
+ * Known limit: a run is one wave's chain for the whole row, not one per column slice, so a push dominated
+ * by one hot row is bound by it more than the Adagrad row push is. */
+/* Strips (64 lanes x E columns each) of a row that the fold keeps in registers between summing the
+ * gradients and updating the weights: a row of more strips -- cols > 64 * E * this -- sums its run a second
+ * time instead (tests size their cases by it; the bits never depend on it). */
+#define GLINT_ROWWISE_KEEP_STRIPS 4
+int glint_mat_push_rows_adagrad_rowwise(glint_shard_t weights, glint_shard_t state, const int64_t* rows,
+                                        const void* grads, int64_t n, double lr, double eps);
+
 /* Row-pair dot pull (an extension: the reference has no such message): the read half of a two-table
  * scoring step -- skip-gram with negative sampling, matrix factorisation, any two-tower model -- where
  * the other operand is not a vector the caller sends but a row of a second shard on the same device.
@@ -651,6 +704,15 @@ int glint_mat_push_rows_adagrad_dev(glint_shard_t weights, glint_shard_t state, 
 int glint_mat_push_rows_adam_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows, const void* grads,
                                  int64_t n, double lr, double beta1, double beta2, double eps, int64_t step,
                                  void* stream);
+
+/* glint_mat_push_rows_adagrad_rowwise, device-resident: the same step with the same bits, stream-ordered on
+ * `stream` with no host synchronisation, after both shards' host-pointer work; both shards are marked for
+ * their next sync. A row outside the partition is skipped -- it contributes to no G -- and is reported by
+ * glint_shard_sync(weights, ...) as the lowest such record index; every other row is stepped. grads is
+ * read by 16 B when it is 16-B aligned (and cols allow), else element by element: the same bits either
+ * way. A slab that has views is GLINT_EINVAL for either shard. */
+int glint_mat_push_rows_adagrad_rowwise_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows,
+                                            const void* grads, int64_t n, double lr, double eps, void* stream);
 
 /* glint_mat_pull_pairs_dot, device-resident: the same dots with the same bits, one launch, stream-ordered
  * on `stream` with no host synchronisation, after both shards' host-pointer work; both shards are marked
@@ -943,8 +1005,8 @@ enum glint_kernel_id {
   GLINT_K_PUSH_BINNED = 6,  /* the binned unordered-push pipeline (count, partition, apply) */
   GLINT_K_PUSH_ORDERED = 7, /* the order-preserving push of message-sized pushes (one launch) */
   /* the per-destination fold of a whole-row push (glint_mat_push_rows*), and the one fold launch of a
-   * non-empty Adagrad or Adam row push (glint_mat_push_rows_adagrad*, glint_mat_push_rows_adam*), recorded
-   * on its weights shard only. Also
+   * non-empty Adagrad, row-wise Adagrad or Adam row push (glint_mat_push_rows_adagrad*,
+   * glint_mat_push_rows_adagrad_rowwise*, glint_mat_push_rows_adam*), recorded on its weights shard only. Also
    * the one launch of a shard fill or uniform init (glint_shard_fill*, glint_shard_init_uniform*), and the
    * one fold launch of a non-empty grouped row push (glint_mat_push_rows_grouped*) or narrow-format row push
    * (glint_mat_push_rows_as*) */

@@ -6,6 +6,7 @@ the JNI shim sees. One JSON line per measurement on stdout.
     python tools/measure_paths.py [--quick] [--sparse] [--rowsum] [--dot] [--axpy [--out FILE]] [--topk [--out FILE]]
                                   [--adagrad [--out FILE]] [--pairs [--out FILE]] [--init [--out FILE]]
                                   [--groups [--out FILE]] [--adam [--out FILE]] [--sampler [--out FILE]]
+                                  [--rowwise [--out FILE]]
 
 --sparse runs only the sparse-row-pull leg (dense getRows against getRowsSparse on a cfg5 shard).
 --rowsum runs only the grouped row-sum leg (getRowsSum against a dense row pull plus a reduction by the
@@ -32,6 +33,10 @@ profiles/groups/groups.jsonl (or FILE).
 --adam runs only the Adam row push leg (updateRowsAdam against coalescing, row pulls of weights and moments,
 the step and two row pushes by the caller, on cfg5 shards, with the Adagrad fold on the same rows beside it)
 and appends its lines to profiles/adam/adam_push.jsonl (or FILE).
+--rowwise runs only the row-wise Adagrad row push leg (updateRowsAdagradRowwise against coalescing, the mean of
+squares, pulls of weight rows and accumulators, the step and two pushes by the caller, on a cfg5 weights shard
+and an accumulator vector, with the Adagrad fold on the same rows beside it) and appends its lines to
+profiles/rowwise_adagrad/rowwise_push.jsonl (or FILE).
 --sampler runs only the row sampler leg (glint_sampler_draw_dev against torch.rand plus torch.searchsorted over a
 device cdf, at m = 2^20 Zipf counts and n = 2^24 draws, with and without exclusion; the creates and the host
 draw by wall clock) and appends its lines to profiles/sampler/sampler.jsonl (or FILE).
@@ -740,6 +745,170 @@ def adam_leg(rng, out_path):
         sh.destroy()
 
 
+# The two row-wise Adagrad legs agree to rounding, not bit for bit: the baseline sums a row's gradients and
+# their squares in another order and adds deltas. The bound comes from the format, not from a run: a sum of m
+# doubles in another order moves by at most about m * 2^-53 of the sum of magnitudes, m is under 10^4 here and
+# a weight or an accumulator takes under 100 such steps of order 1, which gives 1e-10; asserted at 10 x that,
+# absolute for the weights and relative for the accumulators.
+ROWWISE_AGREE_BOUND = {"w": 1e-9, "h": 1e-9}
+
+
+def rowwise_leg(rng, out_path):
+    """The Adagrad leg's method and shapes with a vector for the state: 2^17 x 512 Double weights and a 2^17
+    Double accumulator vector per pair, 2^14 and 2^16 Zipf(1.0) rows of gradients. The leg under test steps
+    one pair of shards, its baseline another pair, on alternating rounds of one process.
+    Device: glint_mat_push_rows_adagrad_rowwise_dev against what a caller does today -- torch.unique +
+    index_add_ to coalesce, the mean of squares, glint_mat_pull_rows_dev of the weights and glint_vec_pull_dev
+    of the accumulators, the step in torch, a glint_vec_push_dev and a glint_mat_push_rows_dev of deltas -- a
+    HIP event pair around each; the fold kernel alone by its prof id, and its bytes (two reads of n x cols
+    gradients at most, plus a read and a write of distinct x cols weights) over that time; beside it the
+    Adagrad row push's fold on the same rows and gradients, on a third pair. Host:
+    glint_mat_push_rows_adagrad_rowwise against the same done with numpy and the host calls, wall time. The
+    baselines never run the code under test; after each n the two pairs are compared to ROWWISE_AGREE_BOUND.
+    One JSON line per n, also appended to out_path."""
+    shard_rows, cols, rounds = 1 << 17, 512, 5
+    lr, eps, hbm_peak_gbs = 0.05, 1e-8, 8000.0
+    part = glint_amd.RangePartition(0, 0, shard_rows)
+    wa, wb, wg, hg = (glint_amd.PartialMatrix(part, cols, "double", 0) for _ in range(4))
+    sa, sb = (glint_amd.PartialVector(part, "double", 0) for _ in range(2))
+    all_rows = torch.arange(shard_rows, dtype=torch.int64, device=dev)
+
+    def ev_ms(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b)
+
+    def wall_ms(fn):
+        t0 = time.perf_counter()
+        fn()
+        return (time.perf_counter() - t0) * 1e3
+
+    def stats(ms):
+        return {"mean": float(np.mean(ms)), "min": float(np.min(ms)), "max": float(np.max(ms))}
+
+    Path(out_path).parent.mkdir(parents=True, exist_ok=True)
+    for n in (1 << 14, 1 << 16):
+        rows = zipf_keys(rng, shard_rows, n, 1.0)
+        g = rng.standard_normal((n, cols))
+        d_rows, d_g = torch.from_numpy(rows).to(dev), torch.from_numpy(g).to(dev)
+        uniq_np, counts = np.unique(rows, return_counts=True)
+        distinct, longest = int(uniq_np.size), int(counts.max())
+
+        def dev_rowwise():
+            assert lib.glint_mat_push_rows_adagrad_rowwise_dev(wa.handle, sa.handle, d_rows.data_ptr(),
+                                                               d_g.data_ptr(), n, lr, eps, stream) == 0
+
+        def dev_base():
+            uniq, inv = torch.unique(d_rows, return_inverse=True)
+            u = uniq.numel()
+            G = torch.zeros((u, cols), dtype=torch.float64, device=dev).index_add_(0, inv, d_g)
+            w = torch.empty_like(G)
+            h = torch.empty(u, dtype=torch.float64, device=dev)
+            assert lib.glint_mat_pull_rows_dev(wb.handle, uniq.data_ptr(), w.data_ptr(), u, stream) == 0
+            assert lib.glint_vec_pull_dev(sb.handle, uniq.data_ptr(), h.data_ptr(), u, stream) == 0
+            s = (G * G).mean(1)
+            dw = -((lr / (torch.sqrt(h + s) + eps))[:, None] * G)
+            assert lib.glint_vec_push_dev(sb.handle, uniq.data_ptr(), s.data_ptr(), u, 0, stream) == 0
+            assert lib.glint_mat_push_rows_dev(wb.handle, uniq.data_ptr(), dw.data_ptr(), u, 0, stream) == 0
+            # (the temporaries are freed into torch's allocator, which reuses them on this stream only)
+
+        def host_rowwise():
+            assert lib.glint_mat_push_rows_adagrad_rowwise(wa.handle, sa.handle, rows.ctypes.data, g.ctypes.data, n,
+                                                           lr, eps) == 0
+
+        def host_base():
+            uniq, inv = np.unique(rows, return_inverse=True)
+            G = np.zeros((uniq.size, cols))
+            np.add.at(G, inv, g)
+            w, h = np.empty_like(G), np.empty(uniq.size)
+            assert lib.glint_mat_pull_rows(wb.handle, uniq.ctypes.data, w.ctypes.data, uniq.size) == 0
+            assert lib.glint_vec_pull(sb.handle, uniq.ctypes.data, h.ctypes.data, uniq.size) == 0
+            s = (G * G).mean(1)
+            dw = -((lr / (np.sqrt(h + s) + eps))[:, None] * G)
+            assert lib.glint_vec_push(sb.handle, uniq.ctypes.data, s.ctypes.data, uniq.size, 0) == 0
+            assert lib.glint_mat_push_rows(wb.handle, uniq.ctypes.data, dw.ctypes.data, uniq.size, 0) == 0
+
+        def host_adagrad():  # the Adagrad row push's host call on the same rows: the same bytes staged
+            assert lib.glint_mat_push_rows_adagrad(wg.handle, hg.handle, rows.ctypes.data, g.ctypes.data, n, lr,
+                                                   eps) == 0
+
+        t = {k: [] for k in ("host_rowwise", "host_base", "host_adagrad", "dev_rowwise", "dev_base")}
+        for rnd in range(rounds + 1):  # round 0 warms up; the legs alternate inside every round
+            got = {"host_base": wall_ms(host_base), "host_rowwise": wall_ms(host_rowwise),
+                   "host_adagrad": wall_ms(host_adagrad)}
+            torch.cuda.synchronize()
+            got["dev_base"] = ev_ms(dev_base)
+            got["dev_rowwise"] = ev_ms(dev_rowwise)
+            if rnd:
+                for k, v in got.items():
+                    t[k].append(v)
+        lib.glint_prof_reset(wa.handle)  # the fold alone, mirrored on the baseline's shards
+        lib.glint_prof_enable(wa.handle, 1)
+        for _ in range(4):
+            dev_rowwise()
+            dev_base()
+        torch.cuda.synchronize()
+        fold_ms = kernel_ms(wa.handle, N.GLINT_K_PUSH_ROWS)
+        lib.glint_prof_enable(wa.handle, 0)
+        lib.glint_prof_reset(wg.handle)  # the Adagrad row push's fold on the same rows, with its cols-wide state
+        lib.glint_prof_enable(wg.handle, 1)
+        for _ in range(4):
+            assert lib.glint_mat_push_rows_adagrad_dev(wg.handle, hg.handle, d_rows.data_ptr(), d_g.data_ptr(), n, lr,
+                                                       eps, stream) == 0
+        torch.cuda.synchronize()
+        adagrad_fold_ms = kernel_ms(wg.handle, N.GLINT_K_PUSH_ROWS)
+        lib.glint_prof_enable(wg.handle, 0)
+        for sh in (wa, sa, wb, sb, wg, hg):
+            sh.sync(stream)
+        dw = (wa.getRows(all_rows) - wb.getRows(all_rows)).abs().max().item()
+        ha_, hb_ = sa.get(all_rows), sb.get(all_rows)
+        dh = ((ha_ - hb_).abs() / hb_.abs().clamp_min(1e-300)).max().item()
+        del ha_, hb_
+        agree = {"w": dw, "h": dh}
+        print(f"rowwise legs disagree by {agree}; bound {ROWWISE_AGREE_BOUND}", file=sys.stderr, flush=True)
+        assert all(agree[k] <= ROWWISE_AGREE_BOUND[k] for k in agree), (agree, ROWWISE_AGREE_BOUND)
+        m = {k: stats(v) for k, v in t.items()}
+        shard_bytes = (2 * distinct * cols + 2 * distinct) * 8
+        adagrad_shard_bytes = 4 * distinct * cols * 8
+        line = dict(
+            op="mat_push_rows_adagrad_rowwise", pattern="zipf1.0 rows", shape=[shard_rows, cols], rows=n,
+            distinct_rows=distinct, longest_run=longest, rounds=rounds, lr=lr, eps=eps,
+            keep_strips=N.GLINT_ROWWISE_KEEP_STRIPS, lib=os.environ.get("GLINT_GPU_LIB", "in-tree"),
+            host_rowwise_ms=m["host_rowwise"], host_baseline_ms=m["host_base"],
+            host_speedup=m["host_base"]["mean"] / m["host_rowwise"]["mean"],
+            host_adagrad_ms=m["host_adagrad"], host_rowwise_bytes_staged=n * 8 + n * cols * 8,
+            host_baseline_bytes_over_link=4 * distinct * 8 + 2 * distinct * cols * 8,
+            dev_rowwise_ms=m["dev_rowwise"], dev_baseline_ms=m["dev_base"],
+            dev_speedup=m["dev_base"]["mean"] / m["dev_rowwise"]["mean"],
+            fold_kernel_ms=fold_ms, fold_gradient_bytes=n * cols * 8, fold_shard_bytes=shard_bytes,
+            fold_GBps=(n * cols * 8 + shard_bytes) / (fold_ms * 1e-3) / 1e9,
+            fold_fraction_of_hbm_peak=(n * cols * 8 + shard_bytes) / (fold_ms * 1e-3) / 1e9 / hbm_peak_gbs,
+            hbm_peak_GBps=hbm_peak_gbs,
+            adagrad_fold_kernel_ms=adagrad_fold_ms, adagrad_fold_shard_bytes=adagrad_shard_bytes,
+            fold_over_adagrad_fold=fold_ms / adagrad_fold_ms,
+            state_bytes_per_row={"rowwise_adagrad": 8, "adagrad": cols * 8, "adam": 2 * cols * 8},
+            max_abs_weight_difference=dw, max_relative_state_difference=dh, agreement_bound=ROWWISE_AGREE_BOUND,
+            note="host_*: C calls on pageable numpy arrays, synchronous, wall ms; baseline = np.unique + np.add.at, "
+                 "the mean of squares, glint_mat_pull_rows and glint_vec_pull, the step in numpy, glint_vec_push "
+                 "and glint_mat_push_rows of deltas. dev_*: one HIP event pair per call; baseline = torch.unique + "
+                 "index_add_, the same with the _dev calls. Legs alternate inside each of `rounds` rounds after "
+                 "one warm-up round. host_adagrad_ms: glint_mat_push_rows_adagrad on the same rows and gradients, on "
+                 "the third pair. fold_kernel_ms: the fold alone (glint_prof, GLINT_K_PUSH_ROWS on the weights "
+                 "shard); fold_gradient_bytes = rows * cols * 8, read once (rows of at most keep_strips strips) or "
+                 "twice; fold_shard_bytes = (2 * distinct * cols + 2 * distinct) * 8; fold_GBps counts the "
+                 "gradients once. adagrad_fold_kernel_ms: the Adagrad row push's fold (glint_rowadagrad.hip, the "
+                 "parent commit's source unchanged) on the same rows and gradients in the same process, on a pair "
+                 "of its own; its shard bytes are 4 * distinct * cols * 8")
+        emit(**line)
+        with open(out_path, "a") as f:
+            f.write(json.dumps(line) + "\n")
+    for sh in (wa, sa, wb, sb, wg, hg):
+        sh.destroy()
+
+
 def pairs_leg(rng, out_path):
     """Two tables per shape -- cfg5's per-GPU 2^17 x 512 Double, and word2vec-shaped 2^17 x 128 Float (short
     rows under one wave per pair) -- and n = 2^14 and 2^16 pairs, rows_a Zipf(1.0), rows_b uniform. The legs
@@ -1441,6 +1610,11 @@ def main():
         out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
             str(Path(__file__).resolve().parent.parent / "profiles" / "adam" / "adam_push.jsonl")
         adam_leg(np.random.default_rng(42), out)
+        return
+    if "--rowwise" in sys.argv:
+        out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
+            str(Path(__file__).resolve().parent.parent / "profiles" / "rowwise_adagrad" / "rowwise_push.jsonl")
+        rowwise_leg(np.random.default_rng(42), out)
         return
     if "--groups" in sys.argv:
         out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
