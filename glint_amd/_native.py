@@ -73,6 +73,8 @@ SIGNATURES = {
     "glint_mat_push_rows_adam": (_I, [_P, _P, _P, _P, _I64, C.c_double, C.c_double, C.c_double, C.c_double, _I64]),
     "glint_mat_push_rows_adam_dev": (_I, [_P, _P, _P, _P, _I64, C.c_double, C.c_double, C.c_double, C.c_double,
                                           _I64, _P]),
+    "glint_mat_push_rows_ftrl": (_I, [_P, _P, _P, _P, _I64, C.c_double, C.c_double, C.c_double, C.c_double]),
+    "glint_mat_push_rows_ftrl_dev": (_I, [_P, _P, _P, _P, _I64, C.c_double, C.c_double, C.c_double, C.c_double, _P]),
     "glint_mat_push_rows_adagrad_rowwise": (_I, [_P, _P, _P, _P, _I64, C.c_double, C.c_double]),
     "glint_mat_push_rows_adagrad_rowwise_dev": (_I, [_P, _P, _P, _P, _I64, C.c_double, C.c_double, _P]),
     "glint_mat_pull_pairs_dot": (_I, [_P, _P, _P, _P, _I64, _P]),

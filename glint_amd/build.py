@@ -28,7 +28,8 @@ HIP_SOURCES = [CSRC / "glint_gpu.hip", CSRC / "glint_sort.hip", CSRC / "glint_ro
                CSRC / "glint_rowsum.hip", CSRC / "glint_rowdot.hip", CSRC / "glint_rowaxpy.hip",
                CSRC / "glint_topk.hip", CSRC / "glint_rowadagrad.hip", CSRC / "glint_pairs.hip",
                CSRC / "glint_init.hip", CSRC / "glint_rowgroup.hip", CSRC / "glint_rowadam.hip",
-               CSRC / "glint_rowwire.hip", CSRC / "glint_sample.hip", CSRC / "glint_rowadagrad_rowwise.hip"]
+               CSRC / "glint_rowwire.hip", CSRC / "glint_sample.hip", CSRC / "glint_rowadagrad_rowwise.hip",
+               CSRC / "glint_rowftrl.hip"]
 # plain C++: the push planners, the top-k pull's level plan, the uniform init's value contract, the
 # narrow-format row transport's conversion contract and the row sampler's value contract
 PLAN_HEADERS = [CSRC / "glint_push_plan.h", CSRC / "glint_bin_plan.h", CSRC / "glint_topk_plan.h",

@@ -23,6 +23,9 @@ Mirrors the reference's client factory and asynchronous models, minus the Akka t
   ``BigVector`` with this matrix's partitioner (PartialMatrix.updateRowsAdagradRowwise).
 * ``BigMatrix.pushAdam`` -- an extension: the same with one lazy Adam step, the second matrix holding both
   moments of a row side by side in ``2 * cols`` columns (PartialMatrix.updateRowsAdam).
+* ``BigMatrix.pushFtrl`` -- an extension: the same with one FTRL-proximal step, the second matrix holding
+  ``z`` and ``n`` of a row side by side; with ``l1 > 0`` most weights become exact zeros, which
+  ``pullSparse`` then leaves out (PartialMatrix.updateRowsFtrl).
 * ``BigMatrix.pullSum`` -- an extension: the sums of groups of rows, reduced on the shards
   (PartialMatrix.getRowsSum) and combined per group in partition-index order.
 * ``BigMatrix.pullDot`` -- an extension: the dot products of rows with caller vectors (or with
@@ -378,6 +381,40 @@ class BigMatrix(_InitMixin):
             idx = order[off[p]:off[p + 1]]
             if idx.size:
                 sh.updateRowsAdam(state.shards[p], rows[idx], grads[idx], lr, step, beta1, beta2, eps)
+        return True
+
+    def pushFtrl(self, state: "BigMatrix", rows, grads, alpha: float, beta: float = 1.0, l1: float = 0.0,
+                 l2: float = 0.0) -> bool:
+        """FTRL-proximal row push (an extension): this matrix holds the weights and ``state`` -- a
+        BigMatrix with the same partitioner, rows and dtype and ``2 * cols`` columns -- ``z`` in columns
+        ``[0, cols)`` and ``n`` in ``[cols, 2 * cols)`` of every row (zeros to start with, beside zeroed
+        weights). ``grads`` is (n, cols) or flat. Per distinct row: its gradient rows are summed in the
+        caller's order, then one FTRL-proximal step is taken on the shard that holds the row
+        (PartialMatrix.updateRowsFtrl); with ``l1 > 0`` a weight whose ``|z| <= l1`` becomes exactly +0, so
+        ``pullSparse`` of trained rows moves their non-zeros only. ``state``, the shapes and -- by the
+        partitioner -- every row are validated before any shard is called. Bucketed by partition as
+        ``pushRows``; one PartialMatrix.updateRowsFtrl per non-empty partition, with its rows and gradient
+        rows in the caller's order and that partition's state shard. A row lives in one partition, so the
+        bits are the shard's."""
+        if not isinstance(state, BigMatrix):
+            raise ValueError("state: expected a BigMatrix")
+        dtype = self.shards[0].np_dtype
+        if (state.rows, state.cols) != (self.rows, 2 * self.cols) or len(state.shards) != len(self.shards) \
+                or np.dtype(state.shards[0].np_dtype) != np.dtype(dtype) \
+                or not _same_partitioner(state.partitioner, self.partitioner):
+            raise ValueError("state: expected a matrix with this one's partitioner, rows and dtype and "
+                             "twice its cols")
+        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        grads = np.ascontiguousarray(grads, dtype=dtype)
+        if grads.size != rows.size * self.cols:
+            raise ValueError(f"grads: {grads.size} elements, expected {rows.size} rows x {self.cols} columns")
+        grads = grads.reshape(rows.size, self.cols)
+        owner = self.partitioner.partition_indices(rows)
+        order, off = bucket(owner, len(self.shards))
+        for p, sh in enumerate(self.shards):
+            idx = order[off[p]:off[p + 1]]
+            if idx.size:
+                sh.updateRowsFtrl(state.shards[p], rows[idx], grads[idx], alpha, beta, l1, l2)
         return True
 
     def pull(self, rows, cols=None) -> np.ndarray:

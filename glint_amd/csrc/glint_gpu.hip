@@ -1372,6 +1372,23 @@ inline int push_adagrad_rowwise_args(const glint_shard* w, const glint_shard* h,
   return GLINT_OK;
 }
 
+// argument checks of glint_mat_push_rows_ftrl / _dev: push_adam_args' about the two shards (the state packs
+// z and n in 2 * cols columns), n and the pointers; alpha > 0, beta, l1 and l2 >= 0 (a NaN fails each test)
+// and all four finite
+inline int push_ftrl_args(const glint_shard* w, const glint_shard* s, const void* rows, const void* grads, int64_t n,
+                          double alpha, double beta, double l1, double l2) {
+  if (!w || !s || w == s || w->part.cols == 0) return GLINT_EINVAL;
+  if (w->dtype != GLINT_F32 && w->dtype != GLINT_F64) return GLINT_EINVAL;
+  if (!same_rows(w, s) || s->part.cols != 2 * w->part.cols || s->part.pitch < s->part.cols) return GLINT_EINVAL;
+  const uintptr_t wa = (uintptr_t)w->data, sa = (uintptr_t)s->data;
+  if (wa < sa + (uintptr_t)s->elems * s->vsize && sa < wa + (uintptr_t)w->elems * w->vsize) return GLINT_EINVAL;
+  if (n < 0 || n >= ((i64)1 << 32) - kSortTile) return GLINT_EINVAL;
+  if (n > 0 && (!rows || !grads)) return GLINT_EINVAL;
+  if (!(alpha > 0) || !(beta >= 0) || !(l1 >= 0) || !(l2 >= 0)) return GLINT_EINVAL;
+  if (std::isinf(alpha) || std::isinf(beta) || std::isinf(l1) || std::isinf(l2)) return GLINT_EINVAL;
+  return GLINT_OK;
+}
+
 // argument checks of glint_mat_push_rows_grouped / _dev: glint_mat_push_rows's shard, flags and record count,
 // a 31-bit group count, the arrays present when they have elements (grp_ptr always: it has g + 1); coef may
 // be NULL
@@ -1615,7 +1632,7 @@ std::atomic<unsigned> g_env_gen{1};
 
 extern "C" {
 
-int glint_version(void) { return 1500; }  // 0.15.0: glint_mat_push_rows_adagrad_rowwise* (one accumulator per row)
+int glint_version(void) { return 1600; }  // 0.16.0: glint_mat_push_rows_ftrl / _dev (FTRL-proximal row push)
 
 int glint_wire_supported(int dtype, int wire) { return wire_supported(dtype, wire) ? 1 : 0; }
 
@@ -2087,6 +2104,17 @@ int glint_mat_push_rows_adagrad_rowwise_dev(glint_shard_t weights, glint_shard_t
     if (weights->dtype == GLINT_F64)
       return push_rows_adagrad_rowwise<double>(weights, state, (const i64*)rows, grads, n, lr, eps, st);
     return push_rows_adagrad_rowwise<float>(weights, state, (const i64*)rows, grads, n, lr, eps, st);
+  });
+}
+
+int glint_mat_push_rows_ftrl_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows, const void* grads,
+                                 int64_t n, double alpha, double beta, double l1, double l2, void* stream) {
+  const int args_rc = push_ftrl_args(weights, state, rows, grads, n, alpha, beta, l1, l2);
+  if (args_rc == GLINT_OK && n == 0) return GLINT_OK;
+  return dev_call2(weights, state, args_rc, stream, [&](hipStream_t st) -> int {
+    if (weights->dtype == GLINT_F64)
+      return push_rows_ftrl<double>(weights, state, (const i64*)rows, grads, n, alpha, beta, l1, l2, st);
+    return push_rows_ftrl<float>(weights, state, (const i64*)rows, grads, n, alpha, beta, l1, l2, st);
   });
 }
 
@@ -3225,6 +3253,24 @@ int glint_mat_push_rows_adagrad_rowwise(glint_shard_t weights, glint_shard_t sta
                      if (weights->dtype == GLINT_F64)
                        return push_rows_adagrad_rowwise<double>(weights, state, d_rows, st.p[1], n, lr, eps, stream);
                      return push_rows_adagrad_rowwise<float>(weights, state, d_rows, st.p[1], n, lr, eps, stream);
+                   });
+}
+
+// glint_mat_push_rows_ftrl: glint_mat_push_rows_adam's host side word for word -- every row checked against
+// the weights shard under both locks before anything is staged, rows and grads staged in one block, the
+// push on the weights shard's stream behind an event on the state shard's, the call ends synchronised.
+// Nothing comes back but the error state.
+int glint_mat_push_rows_ftrl(glint_shard_t weights, glint_shard_t state, const int64_t* rows, const void* grads,
+                             int64_t n, double alpha, double beta, double l1, double l2) {
+  if (int rc = push_ftrl_args(weights, state, rows, grads, n, alpha, beta, l1, l2)) return rc;
+  if (n == 0) return GLINT_OK;
+  return host_call(weights, state, {rows, nullptr, n}, false,
+                   {{rows, (size_t)n * 8}, {grads, (size_t)n * (size_t)weights->part.cols * weights->vsize}}, 0,
+                   [&](const Staged& st, hipStream_t stream, HostBack*) -> int {
+                     const i64* d_rows = (const i64*)st.p[0];
+                     if (weights->dtype == GLINT_F64)
+                       return push_rows_ftrl<double>(weights, state, d_rows, st.p[1], n, alpha, beta, l1, l2, stream);
+                     return push_rows_ftrl<float>(weights, state, d_rows, st.p[1], n, alpha, beta, l1, l2, stream);
                    });
 }
 

@@ -532,6 +532,15 @@ int push_rows_adam(glint_shard* weights, glint_shard* state, const i64* rows, co
 template <typename V>
 int push_rows_adagrad_rowwise(glint_shard* weights, glint_shard* state, const i64* rows, const void* grads, i64 n,
                               double lr, double eps, hipStream_t st);
+// FTRL-proximal row push (glint_rowftrl.hip), instantiated for float and double: per distinct row of the
+// push, G as above, then one FTRL-proximal step of the weights row and of the state row (`state` packs z in
+// columns [0, cols) and n in [cols, 2 * cols); it has `weights`' type and partition and its own pitch), in
+// the order include/glint_gpu.h fixes, alpha, beta, l1 and l2 each rounded once to V. Rows outside the
+// partition are skipped and recorded in err_of(weights). The front end's launches (weights' scratch) and one
+// fold launch on st, no host synchronisation; under both shards' locks.
+template <typename V>
+int push_rows_ftrl(glint_shard* weights, glint_shard* state, const i64* rows, const void* grads, i64 n, double alpha,
+                   double beta, double l1, double l2, hipStream_t st);
 // row-pair dot pull (glint_pairs.hip), instantiated for V in {int, long long, float, double}: out[i] = the
 // dot of row rows_a[i] of `a` with row rows_b[i] of `b` (device pointers), each row array translated with
 // its own shard's partition, in the row dot pull's order; `b` has a's type, device and cols and may be

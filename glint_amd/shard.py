@@ -744,6 +744,41 @@ class PartialMatrix(_Shard):
                                                 *scalars), self.handle)
         return True
 
+    def updateRowsFtrl(self, state: "PartialMatrix", rows, grads, alpha: float, beta: float = 1.0, l1: float = 0.0,
+                       l2: float = 0.0, sync: bool = True) -> bool:
+        """FTRL-proximal row push (an extension; glint_mat_push_rows_ftrl*): this shard holds the weights
+        and ``state`` -- a PartialMatrix of the same type, device and partition with ``2 * cols`` columns
+        -- ``z`` in columns ``[0, cols)`` and ``n`` in ``[cols, 2 * cols)``; zeroed weights beside a zeroed
+        state are the start. ``grads`` is (n, cols) or flat, dense row-major. Per distinct row of ``rows``:
+        ``G`` = its gradient rows added to +0 in push order, then ``n' = n + G * G``, ``z' = z + (G -
+        ((sqrt(n') - sqrt(n)) / alpha) * w)`` and ``w' = 0`` where ``|z'| <= l1``, else ``-(z' - sign(z')
+        * l1) / ((beta + sqrt(n')) / alpha + l2)``, every operation rounded on its own in the shard's type
+        (include/glint_gpu.h has the contract). The weights are a function of ``(z, n)``: a row's first
+        step overwrites whatever the weights shard held. Duplicates are coalesced, then one step is
+        taken; a row that is not named is not touched. There are no order flags: the call is
+        deterministic. Errors as ``updateRowsAdagrad``."""
+        if not isinstance(state, PartialMatrix):
+            raise TypeError("state: expected a PartialMatrix")
+        if np.dtype(self.np_dtype).kind != "f":
+            raise TypeError(f"updateRowsFtrl needs a Float or Double shard, not {np.dtype(self.np_dtype).name}")
+        if _is_torch_cuda(rows) != _is_torch_cuda(grads):
+            raise TypeError("rows and grads: mixing host arrays and device tensors")
+        scalars = (float(alpha), float(beta), float(l1), float(l2))
+        if _is_torch_cuda(rows):
+            n = rows.numel()
+            self._check_dev(n, rows, values=grads, value_elems=n * self.cols)
+            rc = self.lib.glint_mat_push_rows_ftrl_dev(self.handle, state.handle, rows.data_ptr(), grads.data_ptr(),
+                                                       n, *scalars, self._stream_of(rows))
+            self._dev_done(rc, rows, sync)
+            return True
+        r = _host(rows, np.int64).reshape(-1)
+        g = _host(grads, self.np_dtype).reshape(-1)
+        if g.size != r.size * self.cols:
+            raise ValueError(f"grads: {g.size} elements, expected {r.size} rows x {self.cols} columns")
+        check(self.lib.glint_mat_push_rows_ftrl(self.handle, state.handle, r.ctypes.data, g.ctypes.data, r.size,
+                                                *scalars), self.handle)
+        return True
+
     def _axpy_q(self, xshape, cshape, n: int) -> int:
         """q of updateRowsAxpy for vectors of shape ``xshape`` and coefficients of shape ``cshape``."""
         if xshape == (self.cols,):

@@ -435,6 +435,61 @@ int glint_mat_push_rows_adam(glint_shard_t weights, glint_shard_t state, const i
 int glint_mat_push_rows_adagrad_rowwise(glint_shard_t weights, glint_shard_t state, const int64_t* rows,
                                         const void* grads, int64_t n, double lr, double eps);
 
+/* FTRL-proximal row push (an extension: the reference has no such message): per-coordinate FTRL-proximal
+ * (McMahan et al., "Ad Click Prediction: a View from the Trenches", KDD 2013, algorithm 1) next to the
+ * rows, on the Adam row push's frame. Its L1 term writes exact +0 weights, so a table trained with l1 > 0
+ * is sparse to glint_mat_pull_rows_sparse. `weights` is a Float or Double matrix shard of type V; `state`
+ * is a matrix shard of the same dtype, device, size and partition with state.cols == 2 * weights.cols: row
+ * l holds z in columns [0, cols) and n (the accumulated squared gradients) in [cols, 2 * cols). A zeroed
+ * state with zeroed weights is the right start. w is a function of (z, n): the step reads w only to keep z
+ * consistent with it, and weights filled any other way are simply overwritten by a row's first step. One
+ * push crosses the link with n x cols gradients and nothing else.
+ *   grads  n x cols values of V, dense row-major, no pitch (glint_mat_push_rows's vals).
+ * alpha, beta, l1 and l2 arrive as double and are each rounded once to V: alpha, beta, l1, l2 below (the
+ * checks below are made on the doubles: a Float alpha that rounds to 0 or infinity is the caller's). For
+ * every distinct local row l the push names:
+ *   1. G[c] = (((+0 + g_i0[c]) + g_i1[c]) + ...) over the records i0 < i1 < ... with l(rows[i]) == l: the
+ *      sum runs in push order, in V, from +0 (the Adagrad push's step 1).
+ *   2. Per column, with z = state[l][c], n = state[l][cols + c] and w = weights[l][c], every operation in V
+ *      and rounded on its own (no fused multiply-add, no reassociation):
+ *        q  = G * G;       n' = n + q
+ *        r0 = sqrt(n);     r1 = sqrt(n')
+ *        ds = r1 - r0;     sg = ds / alpha
+ *        t  = sg * w;      u  = G - t;        z' = z + u
+ *        a  = |z'|
+ *        if a <= l1:  w' = +0
+ *        else:        s = copysign(l1, z');   y = z' - s
+ *                     b = beta + r1;  c = b / alpha;  d = c + l2
+ *                     e = y / d;      w' = -e
+ *      z' is stored to state[l][c] and n' to state[l][cols + c] on both branches, w' to weights[l][c].
+ *      ds / alpha and b / alpha are divisions, not products with a reciprocal; ds is the difference of the
+ *      two square roots, not q / (r1 + r0).
+ *   3. sqrt and / are IEEE correctly rounded; subnormal inputs and results are kept; infinities and NaN
+ *      follow IEEE (a NaN's payload and sign are unspecified). a <= l1 is false for a NaN z', which
+ *      therefore takes the second branch and reaches w' through y. An overflowing G * G makes n' and r1
+ *      infinite: sg is then infinite, t = sg * w is NaN where w == 0, and z' and w' with it. An n at the
+ *      type's maximum stays finite under a small q (r1 == r0, ds = 0). With beta = 0, l2 = 0, n' = 0 and
+ *      |z'| > l1, d = 0 and w' is infinite; with |z'| <= l1 the same row gives w' = +0 and d is never
+ *      looked at. A negative n (never written by this call from a zeroed state) gives sqrt = NaN.
+ * Duplicates are coalesced, then one step is taken -- not one step per record. A row the push does not name
+ * is neither read nor written in either shard; neither is the pitch padding of either shard. No run is ever
+ * split and no atomic is used: there are no flags, and the answer is a function of the inputs only, never
+ * of the alignment of grads, the slice path or the grid.
+ * Locks, ordering, errors and slabs are glint_mat_push_rows_adam's: both shards' locks are held, the call
+ * is ordered after both shards' earlier work and is synchronous for both; every row is checked against
+ * `weights` before anything is staged, and a row outside the partition returns GLINT_EOUTOFRANGE (the
+ * record's index in glint_shard_last_error(weights)) with both shards unchanged. A slab with views is
+ * refused for either shard.
+ * GLINT_EINVAL: a NULL, vector, Int or Long `weights`; a NULL `state`, the same handle as `weights`, one
+ * that overlaps it in memory, or one that differs from it in dtype, device, size or partition (kind, start,
+ * and index / parts for cyclic); state.cols != 2 * weights.cols; n < 0, n >= 2^32 - 2048; NULL rows or grads
+ * with n > 0; !(alpha > 0); !(beta >= 0); !(l1 >= 0); !(l2 >= 0) (a NaN fails each test); an infinite
+ * alpha, beta, l1 or l2. n == 0 launches nothing and returns GLINT_OK. Staged to the device: rows and grads
+ * in one block; nothing is copied back. Kernel timing: the one fold launch counts under GLINT_K_PUSH_ROWS
+ * on `weights`; nothing is recorded on `state`. */
+int glint_mat_push_rows_ftrl(glint_shard_t weights, glint_shard_t state, const int64_t* rows, const void* grads,
+                             int64_t n, double alpha, double beta, double l1, double l2);
+
 /* Row-pair dot pull (an extension: the reference has no such message): the read half of a two-table
  * scoring step -- skip-gram with negative sampling, matrix factorisation, any two-tower model -- where
  * the other operand is not a vector the caller sends but a row of a second shard on the same device.
@@ -713,6 +768,15 @@ int glint_mat_push_rows_adam_dev(glint_shard_t weights, glint_shard_t state, con
  * way. A slab that has views is GLINT_EINVAL for either shard. */
 int glint_mat_push_rows_adagrad_rowwise_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows,
                                             const void* grads, int64_t n, double lr, double eps, void* stream);
+
+/* glint_mat_push_rows_ftrl, device-resident: the same step with the same bits, stream-ordered on `stream`
+ * with no host synchronisation, after both shards' host-pointer work; both shards are marked for their
+ * next sync. A row outside the partition is skipped -- it contributes to no G -- and is reported by
+ * glint_shard_sync(weights, ...) as the lowest such record index; every other row is stepped. grads is
+ * read by 16 B when it is 16-B aligned (and cols allow), else element by element: the same bits either
+ * way. A slab that has views is GLINT_EINVAL for either shard. */
+int glint_mat_push_rows_ftrl_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows, const void* grads,
+                                 int64_t n, double alpha, double beta, double l1, double l2, void* stream);
 
 /* glint_mat_pull_pairs_dot, device-resident: the same dots with the same bits, one launch, stream-ordered
  * on `stream` with no host synchronisation, after both shards' host-pointer work; both shards are marked
@@ -1005,8 +1069,9 @@ enum glint_kernel_id {
   GLINT_K_PUSH_BINNED = 6,  /* the binned unordered-push pipeline (count, partition, apply) */
   GLINT_K_PUSH_ORDERED = 7, /* the order-preserving push of message-sized pushes (one launch) */
   /* the per-destination fold of a whole-row push (glint_mat_push_rows*), and the one fold launch of a
-   * non-empty Adagrad, row-wise Adagrad or Adam row push (glint_mat_push_rows_adagrad*,
-   * glint_mat_push_rows_adagrad_rowwise*, glint_mat_push_rows_adam*), recorded on its weights shard only. Also
+   * non-empty Adagrad, row-wise Adagrad, Adam or FTRL row push (glint_mat_push_rows_adagrad*,
+   * glint_mat_push_rows_adagrad_rowwise*, glint_mat_push_rows_adam*, glint_mat_push_rows_ftrl*), recorded on
+   * its weights shard only. Also
    * the one launch of a shard fill or uniform init (glint_shard_fill*, glint_shard_init_uniform*), and the
    * one fold launch of a non-empty grouped row push (glint_mat_push_rows_grouped*) or narrow-format row push
    * (glint_mat_push_rows_as*) */

@@ -6,7 +6,7 @@ the JNI shim sees. One JSON line per measurement on stdout.
     python tools/measure_paths.py [--quick] [--sparse] [--rowsum] [--dot] [--axpy [--out FILE]] [--topk [--out FILE]]
                                   [--adagrad [--out FILE]] [--pairs [--out FILE]] [--init [--out FILE]]
                                   [--groups [--out FILE]] [--adam [--out FILE]] [--sampler [--out FILE]]
-                                  [--rowwise [--out FILE]]
+                                  [--rowwise [--out FILE]] [--ftrl [--out FILE]]
 
 --sparse runs only the sparse-row-pull leg (dense getRows against getRowsSparse on a cfg5 shard).
 --rowsum runs only the grouped row-sum leg (getRowsSum against a dense row pull plus a reduction by the
@@ -37,6 +37,9 @@ and appends its lines to profiles/adam/adam_push.jsonl (or FILE).
 squares, pulls of weight rows and accumulators, the step and two pushes by the caller, on a cfg5 weights shard
 and an accumulator vector, with the Adagrad fold on the same rows beside it) and appends its lines to
 profiles/rowwise_adagrad/rowwise_push.jsonl (or FILE).
+--ftrl runs only the FTRL-proximal row push leg (updateRowsFtrl against coalescing, row pulls of weights and
+state, the step and two row pushes by the caller, on cfg5 shards, with the Adam fold on the same rows beside
+it) and appends its lines to profiles/ftrl/ftrl_push.jsonl (or FILE).
 --sampler runs only the row sampler leg (glint_sampler_draw_dev against torch.rand plus torch.searchsorted over a
 device cdf, at m = 2^20 Zipf counts and n = 2^24 draws, with and without exclusion; the creates and the host
 draw by wall clock) and appends its lines to profiles/sampler/sampler.jsonl (or FILE).
@@ -742,6 +745,180 @@ def adam_leg(rng, out_path):
         with open(out_path, "a") as f:
             f.write(json.dumps(line) + "\n")
     for sh in (wa, sa, wb, sb, wg, hg):
+        sh.destroy()
+
+
+# The two FTRL legs agree to rounding, not bit for bit: the baseline sums a row's gradients in another order
+# and adds deltas; w is continuous in z across the threshold, so agreement to rounding is meaningful. Largest
+# disagreement measured over both sizes (DESIGN.md "FTRL row push"), asserted at 100 x: absolute for the
+# weights and z, relative for n.
+FTRL_AGREE_MEASURED = {"w": 1.9e-14, "z": 1.7e-11, "n": 6.8e-11}
+FTRL_AGREE_BOUND = {k: 100 * v for k, v in FTRL_AGREE_MEASURED.items()}
+
+
+def ftrl_leg(rng, out_path):
+    """The Adam leg's method and shapes: 2^17 x 512 Double weights and a 2^17 x 1024 state shard (z, n) per
+    pair, 2^14 and 2^16 Zipf(1.0) rows of standard-normal gradients, alpha = 0.05, beta = 1, l1 = 1e-3, l2 =
+    1e-4. The leg under test steps one pair of shards, its baseline another pair, on alternating rounds of
+    one process; both pairs take the same steps.
+    Device: glint_mat_push_rows_ftrl_dev against what a caller does today -- torch.unique + index_add_ to
+    coalesce, glint_mat_pull_rows_dev of the weights and of the state, the step in torch, two
+    glint_mat_push_rows_dev of deltas -- a HIP event pair around each; the fold kernel alone by its prof
+    id, and its bytes (n x cols gradients plus a read and a write of distinct x 3 cols) over that time as a
+    fraction of the HBM peak; beside it the Adam fold on the same rows, on a third pair. Host:
+    glint_mat_push_rows_ftrl against the same done with numpy and the host calls, wall time. The baselines
+    never run the code under test; after each n the two pairs are compared to FTRL_AGREE_BOUND. One JSON
+    line per n, also appended to out_path."""
+    shard_rows, cols, rounds = 1 << 17, 512, 5
+    alpha, beta, l1, l2, hbm_peak_gbs = 0.05, 1.0, 1e-3, 1e-4, 8000.0
+    part = glint_amd.RangePartition(0, 0, shard_rows)
+    wa, wb, wg = (glint_amd.PartialMatrix(part, cols, "double", 0) for _ in range(3))
+    sa, sb, sg = (glint_amd.PartialMatrix(part, 2 * cols, "double", 0) for _ in range(3))
+    all_rows = torch.arange(shard_rows, dtype=torch.int64, device=dev)
+    steps = {"a": 0, "b": 0, "g": 0}
+
+    def ev_ms(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b)
+
+    def wall_ms(fn):
+        t0 = time.perf_counter()
+        fn()
+        return (time.perf_counter() - t0) * 1e3
+
+    def stats(ms):
+        return {"mean": float(np.mean(ms)), "min": float(np.min(ms)), "max": float(np.max(ms))}
+
+    def step(xp, w, zn, G):
+        """(w' - w, [z', n'] - [z, n]) of the pulled rows, in the caller's own arithmetic (xp: torch or numpy)."""
+        z, n = zn[:, :cols], zn[:, cols:]
+        n2 = n + G * G
+        r1 = xp.sqrt(n2)
+        z2 = z + G - (r1 - xp.sqrt(n)) / alpha * w
+        w2 = xp.where(xp.abs(z2) <= l1, xp.zeros_like(z2), -(z2 - xp.sign(z2) * l1) / ((beta + r1) / alpha + l2))
+        return w2 - w, z2 - z, n2 - n
+
+    Path(out_path).parent.mkdir(parents=True, exist_ok=True)
+    for n in (1 << 14, 1 << 16):
+        rows = zipf_keys(rng, shard_rows, n, 1.0)
+        g = rng.standard_normal((n, cols))
+        d_rows, d_g = torch.from_numpy(rows).to(dev), torch.from_numpy(g).to(dev)
+        distinct = int(np.unique(rows).size)
+
+        def dev_ftrl():
+            steps["a"] += 1
+            assert lib.glint_mat_push_rows_ftrl_dev(wa.handle, sa.handle, d_rows.data_ptr(), d_g.data_ptr(), n, alpha,
+                                                    beta, l1, l2, stream) == 0
+
+        def dev_base():
+            steps["b"] += 1
+            uniq, inv = torch.unique(d_rows, return_inverse=True)
+            u = uniq.numel()
+            G = torch.zeros((u, cols), dtype=torch.float64, device=dev).index_add_(0, inv, d_g)
+            w = torch.empty_like(G)
+            zn = torch.empty((u, 2 * cols), dtype=torch.float64, device=dev)
+            assert lib.glint_mat_pull_rows_dev(wb.handle, uniq.data_ptr(), w.data_ptr(), u, stream) == 0
+            assert lib.glint_mat_pull_rows_dev(sb.handle, uniq.data_ptr(), zn.data_ptr(), u, stream) == 0
+            dw, dz, dn = step(torch, w, zn, G)
+            ds = torch.cat([dz, dn], 1)
+            assert lib.glint_mat_push_rows_dev(sb.handle, uniq.data_ptr(), ds.data_ptr(), u, 0, stream) == 0
+            assert lib.glint_mat_push_rows_dev(wb.handle, uniq.data_ptr(), dw.data_ptr(), u, 0, stream) == 0
+            # (the temporaries are freed into torch's allocator, which reuses them on this stream only)
+
+        def host_ftrl():
+            steps["a"] += 1
+            assert lib.glint_mat_push_rows_ftrl(wa.handle, sa.handle, rows.ctypes.data, g.ctypes.data, n, alpha, beta,
+                                                l1, l2) == 0
+
+        def host_base():
+            steps["b"] += 1
+            uniq, inv = np.unique(rows, return_inverse=True)
+            G = np.zeros((uniq.size, cols))
+            np.add.at(G, inv, g)
+            w, zn = np.empty_like(G), np.empty((uniq.size, 2 * cols))
+            assert lib.glint_mat_pull_rows(wb.handle, uniq.ctypes.data, w.ctypes.data, uniq.size) == 0
+            assert lib.glint_mat_pull_rows(sb.handle, uniq.ctypes.data, zn.ctypes.data, uniq.size) == 0
+            dw, dz, dn = step(np, w, zn, G)
+            ds = np.concatenate([dz, dn], 1)
+            assert lib.glint_mat_push_rows(sb.handle, uniq.ctypes.data, ds.ctypes.data, uniq.size, 0) == 0
+            assert lib.glint_mat_push_rows(wb.handle, uniq.ctypes.data, dw.ctypes.data, uniq.size, 0) == 0
+
+        t = {k: [] for k in ("host_ftrl", "host_base", "dev_ftrl", "dev_base")}
+        for rnd in range(rounds + 1):  # round 0 warms up; the two legs alternate inside every round
+            got = {"host_base": wall_ms(host_base), "host_ftrl": wall_ms(host_ftrl)}
+            torch.cuda.synchronize()
+            got["dev_base"] = ev_ms(dev_base)
+            got["dev_ftrl"] = ev_ms(dev_ftrl)
+            if rnd:
+                for k, v in got.items():
+                    t[k].append(v)
+        assert steps["a"] == steps["b"]
+        lib.glint_prof_reset(wa.handle)  # the fold alone, mirrored on the baseline's shards
+        lib.glint_prof_enable(wa.handle, 1)
+        for _ in range(3):
+            dev_ftrl()
+            dev_base()
+        torch.cuda.synchronize()
+        fold_ms = kernel_ms(wa.handle, N.GLINT_K_PUSH_ROWS)
+        lib.glint_prof_enable(wa.handle, 0)
+        lib.glint_prof_reset(wg.handle)  # the Adam fold on the same rows, for scale
+        lib.glint_prof_enable(wg.handle, 1)
+        for _ in range(4):
+            steps["g"] += 1
+            assert lib.glint_mat_push_rows_adam_dev(wg.handle, sg.handle, d_rows.data_ptr(), d_g.data_ptr(), n, alpha,
+                                                    0.9, 0.999, 1e-8, steps["g"], stream) == 0
+        torch.cuda.synchronize()
+        adam_fold_ms = kernel_ms(wg.handle, N.GLINT_K_PUSH_ROWS)
+        lib.glint_prof_enable(wg.handle, 0)
+        for sh in (wa, sa, wb, sb, wg, sg):
+            sh.sync(stream)
+        wa_, wb_ = wa.getRows(all_rows), wb.getRows(all_rows)
+        dw = (wa_ - wb_).abs().max().item()
+        named = (sa.getRows(all_rows)[:, cols:] != 0).any(1)  # a row that was stepped has n != 0
+        touched = int(named.sum().item())
+        zeros = {"call": int((wa_[named] == 0).sum().item()), "baseline": int((wb_[named] == 0).sum().item())}
+        del wa_, wb_, named
+        sa_, sb_ = sa.getRows(all_rows), sb.getRows(all_rows)
+        dz = (sa_[:, :cols] - sb_[:, :cols]).abs().max().item()
+        dn = ((sa_[:, cols:] - sb_[:, cols:]).abs() / sb_[:, cols:].abs().clamp_min(1e-300)).max().item()
+        del sa_, sb_
+        agree = {"w": dw, "z": dz, "n": dn}
+        print(f"ftrl legs disagree by {agree}; bound {FTRL_AGREE_BOUND}", file=sys.stderr, flush=True)
+        assert all(agree[k] <= FTRL_AGREE_BOUND[k] for k in agree), (agree, FTRL_AGREE_BOUND)
+        m = {k: stats(v) for k, v in t.items()}
+        fold_bytes = (n + 6 * distinct) * cols * 8
+        line = dict(
+            op="mat_push_rows_ftrl", pattern="zipf1.0 rows", shape=[shard_rows, cols], rows=n,
+            distinct_rows=distinct, rounds=rounds, alpha=alpha, beta=beta, l1=l1, l2=l2, steps_taken=steps["a"],
+            host_ftrl_ms=m["host_ftrl"], host_baseline_ms=m["host_base"],
+            host_speedup=m["host_base"]["mean"] / m["host_ftrl"]["mean"],
+            host_ftrl_bytes_staged=n * 8 + n * cols * 8,
+            host_baseline_bytes_over_link=2 * distinct * 8 + 6 * distinct * cols * 8,
+            dev_ftrl_ms=m["dev_ftrl"], dev_baseline_ms=m["dev_base"],
+            dev_speedup=m["dev_base"]["mean"] / m["dev_ftrl"]["mean"],
+            fold_kernel_ms=fold_ms, fold_bytes=fold_bytes, fold_GBps=fold_bytes / (fold_ms * 1e-3) / 1e9,
+            fold_fraction_of_hbm_peak=fold_bytes / (fold_ms * 1e-3) / 1e9 / hbm_peak_gbs, hbm_peak_GBps=hbm_peak_gbs,
+            adam_fold_kernel_ms=adam_fold_ms, fold_over_adam_fold=fold_ms / adam_fold_ms,
+            max_abs_weight_difference=dw, max_abs_z_difference=dz, max_relative_n_difference=dn,
+            agreement_bound=FTRL_AGREE_BOUND, exact_zero_weights_in_touched_rows=zeros,
+            touched_rows=touched,
+            note="host_*: C calls on pageable numpy arrays, synchronous, wall ms; baseline = np.unique + np.add.at, "
+                 "glint_mat_pull_rows of weights and state, the step in numpy, two glint_mat_push_rows of deltas. "
+                 "dev_*: one HIP event pair per call; baseline = torch.unique + index_add_, two "
+                 "glint_mat_pull_rows_dev, the step in torch, two glint_mat_push_rows_dev. "
+                 "Legs alternate inside each of `rounds` rounds after one warm-up round. fold_kernel_ms: the fold "
+                 "alone (glint_prof, GLINT_K_PUSH_ROWS on the weights shard); fold_bytes = (rows + 6 * "
+                 "distinct_rows) * cols * 8. adam_fold_kernel_ms: the Adam push's fold on the same rows and "
+                 "gradients, on a pair of its own. exact_zero_weights_in_touched_rows counts w == 0 in the rows "
+                 "that were ever named (touched_rows: n != 0), of touched_rows * cols weights")
+        emit(**line)
+        with open(out_path, "a") as f:
+            f.write(json.dumps(line) + "\n")
+    for sh in (wa, sa, wb, sb, wg, sg):
         sh.destroy()
 
 
@@ -1610,6 +1787,11 @@ def main():
         out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
             str(Path(__file__).resolve().parent.parent / "profiles" / "adam" / "adam_push.jsonl")
         adam_leg(np.random.default_rng(42), out)
+        return
+    if "--ftrl" in sys.argv:
+        out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
+            str(Path(__file__).resolve().parent.parent / "profiles" / "ftrl" / "ftrl_push.jsonl")
+        ftrl_leg(np.random.default_rng(42), out)
         return
     if "--rowwise" in sys.argv:
         out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
