@@ -64,6 +64,10 @@ SIGNATURES = {
     "glint_mat_pull_rows_sparse_dev": (_I, [_P, _P, _I64, _P, _P, _P, _I64, _P]),
     "glint_mat_pull_rows_sum": (_I, [_P, _P, _I64, _P, _I64, _P]),
     "glint_mat_pull_rows_sum_dev": (_I, [_P, _P, _I64, _P, _I64, _P, _P]),
+    "glint_mat_pull_rows_wsum": (_I, [_P, _P, _I64, _P, _I64, _P, _P]),
+    "glint_mat_pull_rows_wsum_dev": (_I, [_P, _P, _I64, _P, _I64, _P, _P, _P]),
+    "glint_mat_pull_rows_gdot": (_I, [_P, _P, _I64, _P, _I64, _P, _P]),
+    "glint_mat_pull_rows_gdot_dev": (_I, [_P, _P, _I64, _P, _I64, _P, _P, _P]),
     "glint_mat_pull_rows_dot": (_I, [_P, _P, _I64, _P, _I64, _P]),
     "glint_mat_pull_rows_dot_dev": (_I, [_P, _P, _I64, _P, _I64, _P, _P]),
     "glint_mat_push_rows_axpy": (_I, [_P, _P, _I64, _P, _P, _I64, _I]),

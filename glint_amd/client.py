@@ -469,11 +469,14 @@ class BigMatrix(_InitMixin):
         take = np.repeat(src0 - indptr[:-1], counts) + np.arange(base, dtype=np.int64)
         return indptr, np.concatenate(part_cols)[take], np.concatenate(part_vals)[take]
 
-    def pullSum(self, rows, offsets) -> np.ndarray:
+    def pullSum(self, rows, offsets, weights=None) -> np.ndarray:
         """The sums of groups of rows (an extension): ``offsets`` has g + 1 entries, non-decreasing from
         0 to len(rows); row k of the (g, cols) answer is the sum of ``rows[offsets[k]:offsets[k+1]]``, an
         empty group zeros. Bucketed by partition as ``pull``; each non-empty partition answers one
-        PartialMatrix.getRowsSum over the sub-groups of its own rows, each in the caller's order.
+        PartialMatrix.getRowsSum over the sub-groups of its own rows, each in the caller's order. With
+        ``weights`` (n,) record i's term is ``weights[i] * row``, the product rounded before it is added:
+        the forward pass of a weighted bag, whose backward pass is ``pushGroups`` with the same weights;
+        each partition is sent the weights of its own records, ``n_p * itemsize`` bytes more.
 
         Order of the additions: inside a partition strictly the caller's, left to right from the first
         row's stored bits; then, per group, the partials of the partitions that hold at least one of its
@@ -485,6 +488,10 @@ class BigMatrix(_InitMixin):
         if offsets.size < 1 or offsets[0] != 0 or offsets[-1] != rows.size or (np.diff(offsets) < 0).any():
             raise ValueError("offsets must be non-decreasing from 0 to len(rows)")
         g = offsets.size - 1
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, dtype=self.shards[0].np_dtype).reshape(-1)
+            if weights.size != rows.size:
+                raise ValueError(f"weights: {weights.size} values, expected {rows.size}")
         owner = self.partitioner.partition_indices(rows)
         order, off = bucket(owner, len(self.shards))
         group = np.repeat(np.arange(g, dtype=np.int64), np.diff(offsets))  # the group of every record
@@ -495,7 +502,11 @@ class BigMatrix(_InitMixin):
             if idx.size:
                 sub = np.zeros(g + 1, dtype=np.int64)
                 np.cumsum(np.bincount(group[idx], minlength=g), out=sub[1:])
-                part = np.asarray(sh.getRowsSum(rows[idx], sub), dtype=out.dtype)
+                if weights is None:
+                    part = sh.getRowsSum(rows[idx], sub)
+                else:
+                    part = sh.getRowsSum(rows[idx], sub, weights=weights[idx])
+                part = np.asarray(part, dtype=out.dtype)
                 has = np.diff(sub) > 0
                 first, more = has & ~started, has & started
                 out[first] = part[first]
@@ -530,6 +541,45 @@ class BigMatrix(_InitMixin):
             idx = order[off[p]:off[p + 1]]
             if idx.size:
                 out[idx] = sh.getRowsDot(rows[idx], x)
+        return out
+
+    def pullGroupDot(self, rows, offsets, x) -> np.ndarray:
+        """The dot product of every row with the one vector of its group (an extension), reduced on the
+        shards: ``offsets`` is ``pullSum``'s, ``x`` is (g, cols) or flat, and the (n,) answer has
+        ``out[i] = dot(row rows[i], x[k])`` with k the group of record i -- the gradient of
+        ``pullSum(rows, offsets, weights)`` with respect to ``weights``. ``offsets``, the shapes and -- by
+        the partitioner -- every row are validated before any shard is called. Records are bucketed by
+        partition as ``pull``; each non-empty partition gets one PartialMatrix.getRowsGroupDot over the
+        sub-groups of its own records, in the caller's order: only the groups that have a record in that
+        partition are sent, their vectors compacted (``pushGroups``' construction), and the answers are
+        scattered back to the caller's positions. A row lives in one partition, so nothing is combined
+        here: the bits are the shard's under any partitioning.
+
+        Bytes sent to a partition with n_p of the records in g_p of the groups: ``8 n_p + 8 (g_p + 1) +
+        g_p * cols * itemsize``; bytes back: ``n_p * itemsize`` -- against ``n_p * cols * itemsize`` back
+        for ``pull`` of the rows."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        if offsets.size < 1 or offsets[0] != 0 or offsets[-1] != rows.size or (np.diff(offsets) < 0).any():
+            raise ValueError("offsets must be non-decreasing from 0 to len(rows)")
+        g = offsets.size - 1
+        dtype = self.shards[0].np_dtype
+        x = np.ascontiguousarray(x, dtype=dtype)
+        if x.shape != (g, self.cols) and x.shape != (g * self.cols,):
+            raise ValueError(f"x: shape {x.shape}, expected ({g}, {self.cols}) or ({g * self.cols},)")
+        x = x.reshape(g, self.cols)
+        owner = self.partitioner.partition_indices(rows)
+        order, off = bucket(owner, len(self.shards))
+        group = np.repeat(np.arange(g, dtype=np.int64), np.diff(offsets))  # the group of every record
+        out = np.zeros(rows.size, dtype=dtype)
+        for p, sh in enumerate(self.shards):
+            idx = order[off[p]:off[p + 1]]  # caller's order, so its groups are non-decreasing
+            if idx.size:
+                counts = np.bincount(group[idx], minlength=g)
+                has = np.flatnonzero(counts)  # the groups with a record here, ascending
+                sub = np.zeros(has.size + 1, dtype=np.int64)
+                np.cumsum(counts[has], out=sub[1:])
+                out[idx] = sh.getRowsGroupDot(rows[idx], sub, x[has])
         return out
 
     def _pair_buckets(self, other: "BigMatrix", name: str, rows, other_rows):

@@ -1518,6 +1518,33 @@ inline int pull_sum_args(const glint_shard* s, const void* rows, int64_t n, cons
   return GLINT_OK;
 }
 
+// argument checks of glint_mat_pull_rows_wsum / _dev: pull_sum_args, and the coefficients present when
+// there are records (an unweighted caller uses glint_mat_pull_rows_sum)
+inline int pull_wsum_args(const glint_shard* s, const void* rows, int64_t n, const void* grp_ptr, int64_t g,
+                          const void* coef, const void* out) {
+  if (int rc = pull_sum_args(s, rows, n, grp_ptr, g, out)) return rc;
+  return n > 0 && !coef ? GLINT_EINVAL : GLINT_OK;
+}
+
+// argument checks of glint_mat_pull_rows_gdot / _dev: a matrix shard, 31-bit row and group counts (no
+// GLINT_DOT_MAX_QUERIES cap: a record meets one vector), grp_ptr always (it has g + 1), the other arrays
+// present when there are records
+inline int pull_gdot_args(const glint_shard* s, const void* rows, int64_t n, const void* grp_ptr, int64_t g,
+                          const void* x, const void* out) {
+  if (!s || s->part.cols == 0) return GLINT_EINVAL;
+  if (n < 0 || g < 0 || n >= ((i64)1 << 31) || g >= ((i64)1 << 31)) return GLINT_EINVAL;
+  if (!grp_ptr || (n > 0 && (!rows || !x || !out))) return GLINT_EINVAL;
+  return GLINT_OK;
+}
+
+// the grp_ptr rule of the host-pointer group calls: g + 1 entries, non-decreasing from 0 to n
+inline bool grp_ptr_ok(const int64_t* grp_ptr, int64_t g, int64_t n) {
+  if (grp_ptr[0] != 0 || grp_ptr[g] != n) return false;
+  for (i64 k = 0; k < g; ++k)
+    if (grp_ptr[k + 1] < grp_ptr[k]) return false;
+  return true;
+}
+
 // argument checks of glint_mat_pull_rows_dot / _dev: a matrix shard, a 31-bit request count, 1 to
 // GLINT_DOT_MAX_QUERIES queries, x present unless it is the self-dot (q == 1), the arrays present when
 // they have elements
@@ -1632,7 +1659,8 @@ std::atomic<unsigned> g_env_gen{1};
 
 extern "C" {
 
-int glint_version(void) { return 1600; }  // 0.16.0: glint_mat_push_rows_ftrl / _dev (FTRL-proximal row push)
+// 0.17.0: glint_mat_pull_rows_wsum / _dev (weighted row-sum pull), glint_mat_pull_rows_gdot / _dev (grouped row dot)
+int glint_version(void) { return 1700; }
 
 int glint_wire_supported(int dtype, int wire) { return wire_supported(dtype, wire) ? 1 : 0; }
 
@@ -2019,7 +2047,26 @@ int glint_mat_pull_rows_sum_dev(glint_shard_t s, const int64_t* rows, int64_t n,
   const int args_rc = pull_sum_args(s, rows, n, grp_ptr, g, out);
   if (args_rc == GLINT_OK && g == 0) return GLINT_OK;
   return dev_call(s, args_rc, stream, [&](hipStream_t st) -> int {
-    GLINT_DISPATCH(s->dtype, pull_rows_sum, s, (const i64*)rows, n, (const i64*)grp_ptr, g, out, st);
+    GLINT_DISPATCH(s->dtype, pull_rows_sum, s, (const i64*)rows, n, (const i64*)grp_ptr, g, nullptr, out, st);
+  });
+}
+
+int glint_mat_pull_rows_wsum_dev(glint_shard_t s, const int64_t* rows, int64_t n, const int64_t* grp_ptr, int64_t g,
+                                 const void* coef, void* out, void* stream) {
+  const int args_rc = pull_wsum_args(s, rows, n, grp_ptr, g, coef, out);
+  if (args_rc == GLINT_OK && g == 0) return GLINT_OK;
+  return dev_call(s, args_rc, stream, [&](hipStream_t st) -> int {
+    GLINT_DISPATCH(s->dtype, pull_rows_sum, s, (const i64*)rows, n, (const i64*)grp_ptr, g, n > 0 ? coef : nullptr, out,
+                   st);
+  });
+}
+
+int glint_mat_pull_rows_gdot_dev(glint_shard_t s, const int64_t* rows, int64_t n, const int64_t* grp_ptr, int64_t g,
+                                 const void* x, void* out, void* stream) {
+  const int args_rc = pull_gdot_args(s, rows, n, grp_ptr, g, x, out);
+  if (args_rc == GLINT_OK && n == 0) return GLINT_OK;
+  return dev_call(s, args_rc, stream, [&](hipStream_t st) -> int {
+    GLINT_DISPATCH(s->dtype, pull_rows_gdot, s, (const i64*)rows, n, (const i64*)grp_ptr, g, x, out, st);
   });
 }
 
@@ -3080,16 +3127,56 @@ int glint_mat_pull_rows_sparse(glint_shard_t s, const int64_t* rows, int64_t n, 
 int glint_mat_pull_rows_sum(glint_shard_t s, const int64_t* rows, int64_t n, const int64_t* grp_ptr, int64_t g,
                             void* out) {
   if (int rc = pull_sum_args(s, rows, n, grp_ptr, g, out)) return rc;
-  if (grp_ptr[0] != 0 || grp_ptr[g] != n) return GLINT_EINVAL;
-  for (i64 k = 0; k < g; ++k)
-    if (grp_ptr[k + 1] < grp_ptr[k]) return GLINT_EINVAL;
+  if (!grp_ptr_ok(grp_ptr, g, n)) return GLINT_EINVAL;
   if (g == 0) return GLINT_OK;
   const size_t out_bytes = (size_t)g * (size_t)s->part.cols * s->vsize;
   return host_call(s, s, {rows, nullptr, n}, false, {{rows, (size_t)n * 8}, {grp_ptr, (size_t)(g + 1) * 8}}, 0,
                    [&](const Staged& st, hipStream_t stream, HostBack* back) -> int {
                      if (int rc = grow(&s->d_det, &s->det_bytes, out_bytes)) return rc;
                      back[0] = {out, s->d_det, out_bytes};
-                     GLINT_DISPATCH(s->dtype, pull_rows_sum, s, (const i64*)st.p[0], n, (const i64*)st.p[1], g, s->d_det, stream);
+                     GLINT_DISPATCH(s->dtype, pull_rows_sum, s, (const i64*)st.p[0], n, (const i64*)st.p[1], g, nullptr,
+                                    s->d_det, stream);
+                   });
+}
+
+// glint_mat_pull_rows_wsum: glint_mat_pull_rows_sum with the n coefficients staged in the same block behind
+// rows and grp_ptr -- n * 8 + (g + 1) * 8 bytes + n values go out and g * cols values come back, never
+// n * cols.
+int glint_mat_pull_rows_wsum(glint_shard_t s, const int64_t* rows, int64_t n, const int64_t* grp_ptr, int64_t g,
+                             const void* coef, void* out) {
+  if (int rc = pull_wsum_args(s, rows, n, grp_ptr, g, coef, out)) return rc;
+  if (!grp_ptr_ok(grp_ptr, g, n)) return GLINT_EINVAL;
+  if (g == 0) return GLINT_OK;
+  const size_t out_bytes = (size_t)g * (size_t)s->part.cols * s->vsize;
+  return host_call(s, s, {rows, nullptr, n}, false,
+                   {{rows, (size_t)n * 8}, {grp_ptr, (size_t)(g + 1) * 8}, {coef, (size_t)n * s->vsize}}, 0,
+                   [&](const Staged& st, hipStream_t stream, HostBack* back) -> int {
+                     if (int rc = grow(&s->d_det, &s->det_bytes, out_bytes)) return rc;
+                     back[0] = {out, s->d_det, out_bytes};
+                     GLINT_DISPATCH(s->dtype, pull_rows_sum, s, (const i64*)st.p[0], n, (const i64*)st.p[1], g,
+                                    n > 0 ? (const void*)st.p[2] : nullptr, s->d_det, stream);
+                   });
+}
+
+// glint_mat_pull_rows_gdot: grp_ptr and every row are checked before anything is staged (a rejected call
+// writes nothing), then rows, grp_ptr and x are staged in one block (every section starts 256-B aligned, so
+// x takes the 16-B path when cols allow), the one kernel writes its n dots into device scratch (the
+// shard's deterministic-path scratch) and those come back -- never n * cols or n * g values.
+int glint_mat_pull_rows_gdot(glint_shard_t s, const int64_t* rows, int64_t n, const int64_t* grp_ptr, int64_t g,
+                             const void* x, void* out) {
+  if (int rc = pull_gdot_args(s, rows, n, grp_ptr, g, x, out)) return rc;
+  if (!grp_ptr_ok(grp_ptr, g, n)) return GLINT_EINVAL;
+  if (n == 0) return GLINT_OK;
+  const size_t out_bytes = (size_t)n * s->vsize;
+  return host_call(s, s, {rows, nullptr, n}, false,
+                   {{rows, (size_t)n * 8},
+                    {grp_ptr, (size_t)(g + 1) * 8},
+                    {x, (size_t)g * (size_t)s->part.cols * s->vsize}},
+                   0, [&](const Staged& st, hipStream_t stream, HostBack* back) -> int {
+                     if (int rc = grow(&s->d_det, &s->det_bytes, out_bytes)) return rc;
+                     back[0] = {out, s->d_det, out_bytes};
+                     GLINT_DISPATCH(s->dtype, pull_rows_gdot, s, (const i64*)st.p[0], n, (const i64*)st.p[1], g,
+                                    (const void*)st.p[2], s->d_det, stream);
                    });
 }
 
@@ -3152,9 +3239,7 @@ int glint_mat_push_rows_axpy(glint_shard_t s, const int64_t* rows, int64_t n, co
 int glint_mat_push_rows_grouped(glint_shard_t s, const int64_t* rows, int64_t n, const int64_t* grp_ptr, int64_t g,
                                 const void* vals, const void* coef, int flags) {
   if (int rc = push_grouped_args(s, rows, n, grp_ptr, g, vals, flags)) return rc;
-  if (grp_ptr[0] != 0 || grp_ptr[g] != n) return GLINT_EINVAL;
-  for (i64 k = 0; k < g; ++k)
-    if (grp_ptr[k + 1] < grp_ptr[k]) return GLINT_EINVAL;
+  if (!grp_ptr_ok(grp_ptr, g, n)) return GLINT_EINVAL;
   if (n == 0) return GLINT_OK;
   return host_call(s, s, {rows, nullptr, n}, false,
                    {{rows, (size_t)n * 8},

@@ -601,9 +601,20 @@ int sparse_emit(glint_shard* s, const i64* rows, i64 n, const i64* row_ptr, int3
                 i64 cap, hipStream_t st);
 // grouped row-sum pull (glint_rowsum.hip), instantiated for the same V: out[k] (g x cols, dense) = the
 // left-to-right sum of rows[grp_ptr[k] .. grp_ptr[k+1]), device pointers; rows outside the partition
-// count as zeros and are recorded in err_of(s). One launch on st, no host synchronisation.
+// count as zeros and are recorded in err_of(s). With coef (n values, device pointer; nullptr: none) the
+// term of record i is coef[i] * its row, the product rounded before the add, and a row outside the
+// partition is the term zero whatever its coefficient. One launch on st, no host synchronisation.
 template <typename V>
-int pull_rows_sum(glint_shard* s, const i64* rows, i64 n, const i64* grp_ptr, i64 g, void* out, hipStream_t st);
+int pull_rows_sum(glint_shard* s, const i64* rows, i64 n, const i64* grp_ptr, i64 g, const void* coef, void* out,
+                  hipStream_t st);
+// grouped row-dot pull (glint_rowdot.hip), instantiated for the same V: out[i] (n values) = the dot of row
+// rows[i] with x[k] (g x cols, dense), k the group of record i under grp_ptr (g + 1 entries, each clamped to
+// [0, n] by the kernel; a record that no group covers answers zero), device pointers, in the order of
+// pull_rows_dot with q == 1; rows outside the partition answer zero and are recorded in err_of(s). One
+// launch on st, no scratch, no host synchronisation.
+template <typename V>
+int pull_rows_gdot(glint_shard* s, const i64* rows, i64 n, const i64* grp_ptr, i64 g, const void* x, void* out,
+                   hipStream_t st);
 // row dot-product pull (glint_rowdot.hip), instantiated for the same V: out[i*q + j] (n x q, dense) = the
 // dot of row rows[i] with x[j] (q x cols, dense; nullptr with q == 1: the row with itself), device
 // pointers, in the order include/glint_gpu.h fixes; rows outside the partition answer zeros and are

@@ -10,32 +10,13 @@
 //                     vals[group of record i] (COEF: coef[i] * that), strictly in list order -- the row
 //                     push of those rows, rounding for rounding (glint_axpy.h).
 // Only `cols` elements of a shard row are read or written, never the pitch padding; `vals` has no pitch.
-#include "glint_axpy.h"  // axpy_mul, axpy_add, lane_get: shared with the axpy pushes
+#include "glint_axpy.h"   // axpy_mul, axpy_add, lane_get: shared with the axpy pushes
+#include "glint_group.h"  // group_cut, group_find: shared with the grouped row-dot pull
 #include "glint_host.h"
 
 namespace glint {
 
 constexpr int kRowsDepth = 8;  // value-row slice loads in flight per wave (glint_rows.hip's kRowsDepth)
-
-// grp_ptr[k] clamped to [0, n]: what every read of a device caller's group pointer goes through
-__device__ __forceinline__ i64 group_cut(const i64* __restrict__ grp_ptr, i64 k, i64 n) {
-  const i64 v = grp_ptr[k];
-  return v < 0 ? 0 : (v > n ? n : v);
-}
-
-// The group of record i: the k in [0, g) with cut[k] <= i < cut[k+1], or -1 when no group covers it, by
-// an upper-bound search over cut[0 .. g] (the first position whose cut exceeds i; at most 32 dependent
-// 8-B loads, g < 2^31). Groups that are empty are stepped over: their cuts do not exceed i. Only
-// grp_ptr[0 .. g] is read and the answer lies in [-1, g), whatever the array holds.
-__device__ __forceinline__ int32_t group_find(const i64* __restrict__ grp_ptr, i64 g, i64 n, i64 i) {
-  i64 lo = 0, hi = g + 1;  // the answer lies in [lo, hi]
-  while (lo < hi) {
-    const i64 mid = lo + (hi - lo) / 2;
-    if (group_cut(grp_ptr, mid, n) > i) hi = mid;
-    else lo = mid + 1;
-  }
-  return lo >= 1 && lo <= g ? (int32_t)(lo - 1) : -1;
-}
 
 constexpr u32 kNoGroup = 0xFFFFFFFFu;  // rows_group_ids: no group covers the record (-1 as the fold reads it)
 

@@ -915,7 +915,7 @@ class PartialMatrix(_Shard):
             cols, vals = cols[:nnz.value].copy(), vals[:nnz.value].copy()
         return indptr, cols, vals
 
-    def getRowsSum(self, rows, offsets, out=None, sync: bool = True):
+    def getRowsSum(self, rows, offsets, out=None, sync: bool = True, *, weights=None):
         """The sums of groups of requested rows as one (g, cols) array (an extension;
         glint_mat_pull_rows_sum*): ``offsets`` has g + 1 int64 entries, non-decreasing from 0 to
         len(rows), and group k is ``rows[offsets[k]:offsets[k+1]]``. Row k of the answer is the
@@ -926,7 +926,13 @@ class PartialMatrix(_Shard):
         Host arrays: only the (g, cols) sums cross the link; a row outside the partition raises and
         nothing is written. Device tensors: one stream-ordered launch on the current stream; a row
         outside the partition counts as zeros and is raised by the sync (``sync=True``, or a later
-        ``sync()``); ``offsets`` values are clamped to [0, len(rows)] by the kernel."""
+        ``sync()``); ``offsets`` values are clamped to [0, len(rows)] by the kernel.
+
+        ``weights`` (keyword only; (n,) of the shard's dtype, a host array with host rows, a contiguous
+        CUDA tensor on rows' device with device rows) makes it the weighted sum (glint_mat_pull_rows_wsum*):
+        ``((weights[b] * r_b) + (weights[b+1] * r_b+1)) + ...``, every product rounded before it is added
+        (no fused multiply-add) and the first term the first product as computed. On the device a row
+        outside the partition is the term zero whatever its weight."""
         if _is_torch_cuda(rows):
             import torch
             n = rows.numel()
@@ -934,21 +940,97 @@ class PartialMatrix(_Shard):
                     or offsets.device != rows.device or offsets.numel() < 1:
                 raise TypeError("offsets: expected a contiguous int64 CUDA tensor of g + 1 entries on rows' device")
             g = offsets.numel() - 1
+            if weights is not None:
+                if not _is_torch_cuda(weights) or weights.dtype != self.torch_dtype or not weights.is_contiguous() \
+                        or weights.device != rows.device:
+                    raise TypeError(f"weights: expected a contiguous {self.torch_dtype} CUDA tensor on rows' device")
+                if weights.numel() != n:
+                    raise ValueError(f"weights: {weights.numel()} values, expected {n}")
             if out is None:
                 out = torch.empty((g, self.cols), dtype=self.torch_dtype, device=rows.device)
             self._check_dev(n, rows, out=out, out_elems=g * self.cols)
-            rc = self.lib.glint_mat_pull_rows_sum_dev(self.handle, rows.data_ptr(), n, offsets.data_ptr(), g,
-                                                      out.data_ptr(), self._stream_of(rows))
+            if weights is None:
+                rc = self.lib.glint_mat_pull_rows_sum_dev(self.handle, rows.data_ptr(), n, offsets.data_ptr(), g,
+                                                          out.data_ptr(), self._stream_of(rows))
+            else:
+                rc = self.lib.glint_mat_pull_rows_wsum_dev(self.handle, rows.data_ptr(), n, offsets.data_ptr(), g,
+                                                           weights.data_ptr() if n else None, out.data_ptr(),
+                                                           self._stream_of(rows))
             self._dev_done(rc, rows, sync)
             return out
+        if _is_torch_cuda(offsets) or _is_torch_cuda(weights):
+            raise TypeError("rows, offsets and weights: mixing host arrays and device tensors")
         r = _host(rows, np.int64).reshape(-1)
         o = _host(offsets, np.int64).reshape(-1)
         if o.size < 1:
             raise ValueError("offsets needs g + 1 entries")
+        w = None
+        if weights is not None:
+            if isinstance(weights, np.ndarray) and weights.dtype != np.dtype(self.np_dtype):
+                raise TypeError(f"weights: expected {np.dtype(self.np_dtype).name}, not {weights.dtype.name}")
+            w = _host(weights, self.np_dtype).reshape(-1)
+            if w.size != r.size:
+                raise ValueError(f"weights: {w.size} values, expected {r.size}")
         res = self._host_out(out, (o.size - 1, self.cols))
-        check(self.lib.glint_mat_pull_rows_sum(self.handle, r.ctypes.data, r.size, o.ctypes.data, o.size - 1,
-                                               res.ctypes.data), self.handle)
+        if w is None:
+            check(self.lib.glint_mat_pull_rows_sum(self.handle, r.ctypes.data, r.size, o.ctypes.data, o.size - 1,
+                                                   res.ctypes.data), self.handle)
+        else:
+            check(self.lib.glint_mat_pull_rows_wsum(self.handle, r.ctypes.data, r.size, o.ctypes.data, o.size - 1,
+                                                    w.ctypes.data if r.size else None, res.ctypes.data), self.handle)
         return res
+
+    def getRowsGroupDot(self, rows, offsets, x, out=None, sync: bool = True):
+        """The dot product of every requested row with the one vector of its group, as an (n,) array (an
+        extension; glint_mat_pull_rows_gdot*): ``offsets`` is ``getRowsSum``'s, ``x`` is (g, cols) or flat
+        with g * cols elements, and ``out[i] = dot(row rows[i], x[k])`` with k the group of record i -- the
+        gradient of ``getRowsSum(..., weights=w)`` with respect to ``w``, or each query's scores over its
+        own candidates. The arithmetic is ``getRowsDot``'s with one vector, bit for bit: ``out[i]`` is
+        ``getRowsDot(rows[i:i+1], x[k])``. Rows may repeat; answers keep the caller's order.
+
+        Host arrays: only the n dots cross the link; a row outside the partition raises and nothing is
+        written. Device tensors: one stream-ordered launch on the current stream; a row outside the
+        partition answers zero and is raised by the sync; ``offsets`` values are clamped to [0, len(rows)]
+        by the kernel and a record that no group covers answers zero."""
+        if _is_torch_cuda(rows):
+            import torch
+            n = rows.numel()
+            if not _is_torch_cuda(offsets) or offsets.dtype != torch.int64 or not offsets.is_contiguous() \
+                    or offsets.device != rows.device or offsets.numel() < 1:
+                raise TypeError("offsets: expected a contiguous int64 CUDA tensor of g + 1 entries on rows' device")
+            g = offsets.numel() - 1
+            if not _is_torch_cuda(x) or x.dtype != self.torch_dtype or not x.is_contiguous() \
+                    or x.device != rows.device:
+                raise TypeError(f"x: expected a contiguous {self.torch_dtype} CUDA tensor on rows' device")
+            self._gdot_shape(tuple(x.shape), g)
+            if out is None:
+                out = torch.empty((n,), dtype=self.torch_dtype, device=rows.device)
+            self._check_dev(n, rows, out=out, out_elems=n)
+            rc = self.lib.glint_mat_pull_rows_gdot_dev(self.handle, rows.data_ptr(), n, offsets.data_ptr(), g,
+                                                       x.data_ptr() if g else None, out.data_ptr(),
+                                                       self._stream_of(rows))
+            self._dev_done(rc, rows, sync)
+            return out
+        if _is_torch_cuda(offsets) or _is_torch_cuda(x):
+            raise TypeError("rows, offsets and x: mixing host arrays and device tensors")
+        r = _host(rows, np.int64).reshape(-1)
+        o = _host(offsets, np.int64).reshape(-1)
+        if o.size < 1:
+            raise ValueError("offsets needs g + 1 entries")
+        g = o.size - 1
+        if isinstance(x, np.ndarray) and x.dtype != np.dtype(self.np_dtype):
+            raise TypeError(f"x: expected {np.dtype(self.np_dtype).name}, not {x.dtype.name}")
+        xs = _host(x, self.np_dtype)
+        self._gdot_shape(xs.shape, g)
+        res = self._host_out(out, (r.size,))
+        check(self.lib.glint_mat_pull_rows_gdot(self.handle, r.ctypes.data, r.size, o.ctypes.data, g,
+                                                xs.ctypes.data if g else None, res.ctypes.data), self.handle)
+        return res
+
+    def _gdot_shape(self, shape, g: int) -> None:
+        """``x`` of a grouped row dot: (g, cols), or flat with g * cols elements."""
+        if tuple(shape) != (g, self.cols) and tuple(shape) != (g * self.cols,):
+            raise ValueError(f"x: shape {tuple(shape)}, expected ({g}, {self.cols}) or ({g * self.cols},)")
 
     def getRowsDot(self, rows, x=None, out=None, sync: bool = True):
         """The dot products of the requested rows with caller vectors (an extension;

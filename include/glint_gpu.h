@@ -582,6 +582,52 @@ int glint_mat_push_pairs_axpy(glint_shard_t dst, glint_shard_t src, const int64_
 int glint_mat_push_rows_grouped(glint_shard_t shard, const int64_t* rows, int64_t n, const int64_t* grp_ptr,
                                 int64_t g, const void* vals, const void* coef, int flags);
 
+/* Weighted row-sum pull (an extension: the reference has no such message): glint_mat_pull_rows_sum with a
+ * coefficient per record -- the forward pass of a weighted embedding bag, and the read-side counterpart of
+ * glint_mat_push_rows_grouped's coef -- so that g x cols values answer n rows and n weights.
+ *   grp_ptr   glint_mat_pull_rows_sum's: g + 1 int64, non-decreasing from 0 to n;
+ *   coef      n values of the shard's type, one per record;
+ *   out       g x cols values of the shard's type, dense row-major (NO pitch).
+ * out[k][c] = ((coef[b] * r_b[c]) + (coef[b+1] * r_b+1[c])) + ... over the group's records b, b + 1, ... in
+ * the caller's order, all in the shard's type. Every product is rounded before it is added (no fused
+ * multiply-add), and the first term is the first PRODUCT as computed, not 0 + product: a group of the one
+ * row -0.0 with coefficient 1 is -0.0. An empty group is all +0 / 0; Int and Long wrap. Subnormal products
+ * and sums are kept; infinities and NaN follow IEEE (inf * 0 is NaN; a NaN's payload and sign are
+ * unspecified: 1 * sNaN quiets). A row may occur several times in a group, and in several groups. Only
+ * `cols` elements of a row are read, never the pitch padding. The answer is deterministic: no atomics, and
+ * no group is split; there are no flags. With every coefficient 1 and a table without NaN the bits are
+ * glint_mat_pull_rows_sum's.
+ * GLINT_EINVAL: glint_mat_pull_rows_sum's cases (the grp_ptr rule in this host call only), and a NULL coef
+ * with n > 0 -- an unweighted caller uses glint_mat_pull_rows_sum. g == 0 writes nothing and returns
+ * GLINT_OK. Every row is checked first: a row outside the partition returns GLINT_EOUTOFRANGE (its index in
+ * `rows` in glint_shard_last_error) with nothing written to out. Staged to the device in one block: rows,
+ * grp_ptr and coef; copied back: g * cols values -- never n * cols. Kernel timing: one launch under
+ * GLINT_K_PULL_ROWS_SUM. */
+int glint_mat_pull_rows_wsum(glint_shard_t shard, const int64_t* rows, int64_t n, const int64_t* grp_ptr,
+                             int64_t g, const void* coef, void* out);
+
+/* Grouped row-dot pull (an extension: the reference has no such message): every record's row times the ONE
+ * vector of its group -- the gradient of a weighted bag with respect to its weights, a query's scores over
+ * its own candidate list, the scores of attention pooling -- so that n values answer n rows, where
+ * glint_mat_pull_rows_dot with a vector per group would answer n x g.
+ *   grp_ptr   glint_mat_pull_rows_sum's: g + 1 int64, non-decreasing from 0 to n;
+ *   x         g x cols values of the shard's type, dense row-major (NO pitch): one vector per group;
+ *   out       n values of the shard's type: out[i] = dot(row rows[i], x[k]), k the group of record i.
+ * Arithmetic: glint_mat_pull_rows_dot's with q == 1, bit for bit (E, lane L = (c / E) % 64, ascending
+ * columns, the product rounded before the add, the xor butterfly; Int/Long wrap): out[i] is what
+ * glint_mat_pull_rows_dot(shard, &rows[i], 1, x + k * cols, 1, ...) returns. It is a function of (type,
+ * cols) only -- never of the alignment of x, how records are batched over waves, or the grid. Answers keep
+ * the caller's order; a row requested twice is answered twice; an empty group reads nothing of x. g is
+ * limited to < 2^31 only (no GLINT_DOT_MAX_QUERIES cap). x must not overlap out.
+ * GLINT_EINVAL: a NULL or vector shard, n < 0, g < 0, n >= 2^31, g >= 2^31, a NULL grp_ptr, NULL rows, x or
+ * out with n > 0 and -- in this host call only, before anything is staged -- a grp_ptr that breaks the rule.
+ * n == 0 writes nothing and returns GLINT_OK. Every row is checked first: a row outside the partition
+ * returns GLINT_EOUTOFRANGE (its index in glint_shard_last_error) with nothing written to out. Staged to the
+ * device in one block: rows, grp_ptr and x (which starts 16-B aligned there); copied back: n values -- never
+ * n * cols or n * g. Kernel timing: one launch under GLINT_K_PULL_ROWS_DOT, no scratch for group ids. */
+int glint_mat_pull_rows_gdot(glint_shard_t shard, const int64_t* rows, int64_t n, const int64_t* grp_ptr,
+                             int64_t g, const void* x, void* out);
+
 /* Narrow-format row transport (an extension: the reference has no such message): whole rows cross the link
  * in a narrower floating type W than the shard's type V, while the shard keeps full precision -- a
  * full-precision master table whose rows and gradient rows travel as half or bfloat16. A pull rounds on the
@@ -713,6 +759,27 @@ int glint_mat_pull_rows_sparse_dev(glint_shard_t shard, const int64_t* rows, int
  * any element-aligned `out` gives the same bits. */
 int glint_mat_pull_rows_sum_dev(glint_shard_t shard, const int64_t* rows, int64_t n, const int64_t* grp_ptr,
                                 int64_t g, void* out, void* stream);
+
+/* glint_mat_pull_rows_wsum, device-resident: the same sums, stream-ordered on `stream` with no host
+ * synchronisation, one launch. grp_ptr is read as glint_mat_pull_rows_sum_dev reads it: every value
+ * clamped to [0, n], end < start an empty group. A row outside the partition contributes the term +0 / 0
+ * whatever its coefficient -- its row is not loaded and its coefficient is not used, so an infinite
+ * coefficient makes no NaN there -- and
+ * is reported by glint_shard_sync as the lowest such index in `rows`; every other record is summed. `out`
+ * 16-B aligned takes the 16-B path when cols allow; any element-aligned `out` gives the same bits. */
+int glint_mat_pull_rows_wsum_dev(glint_shard_t shard, const int64_t* rows, int64_t n, const int64_t* grp_ptr,
+                                 int64_t g, const void* coef, void* out, void* stream);
+
+/* glint_mat_pull_rows_gdot, device-resident: the same dots in the same order, stream-ordered on `stream`
+ * with no host synchronisation, one launch. grp_ptr is not checked on the host: every value the kernel
+ * reads is clamped to [0, n], and the group of record i is the k with cut[k] <= i < cut[k+1] found by an
+ * upper-bound search over the clamped values (glint_mat_push_rows_grouped_dev's rule, the same code). A
+ * record that no group covers answers +0 / 0 and is not an error, as that push skips it. A row outside the
+ * partition answers +0 / 0 without a load and is reported by glint_shard_sync as the lowest such request
+ * index; every other record is answered. x is read by 16 B when it is 16-B aligned (and cols allow), else
+ * element by element: the same bits either way. */
+int glint_mat_pull_rows_gdot_dev(glint_shard_t shard, const int64_t* rows, int64_t n, const int64_t* grp_ptr,
+                                 int64_t g, const void* x, void* out, void* stream);
 
 /* glint_mat_pull_rows_dot, device-resident: the same dots in the same order, stream-ordered on `stream`
  * with no host synchronisation, one launch. A row outside the partition answers q zeros without a load
@@ -1079,11 +1146,14 @@ enum glint_kernel_id {
   /* the sparse row pull (glint_mat_pull_rows_sparse*): its emit kernel, and under the same id its
    * count kernel and the launches of its scan, so the sum is the pull's whole device time */
   GLINT_K_PULL_ROWS_SPARSE = 9,
-  GLINT_K_PULL_ROWS_SUM = 10, /* the grouped row-sum pull (glint_mat_pull_rows_sum*): one launch per call */
+  /* the grouped row-sum pull (glint_mat_pull_rows_sum*) and the weighted one (glint_mat_pull_rows_wsum*): one
+   * launch per call */
+  GLINT_K_PULL_ROWS_SUM = 10,
   /* the row dot-product pull (glint_mat_pull_rows_dot*): one launch per call. Also every launch of a top-k
    * pull (glint_mat_pull_topk*), which is a dot pull over every row plus a selection: its scores launch
    * and one launch per selection level, so the sum is that pull's whole device time. Also the one launch
-   * of a row-pair dot pull (glint_mat_pull_pairs_dot*), recorded on its first shard only */
+   * of a row-pair dot pull (glint_mat_pull_pairs_dot*), recorded on its first shard only, and the one launch
+   * of a grouped row-dot pull (glint_mat_pull_rows_gdot*) */
   GLINT_K_PULL_ROWS_DOT = 11,
   /* the fold of a row axpy push (glint_mat_push_rows_axpy*): one launch per non-empty call. Also the fold
    * of a row-pair axpy push (glint_mat_push_pairs_axpy*), recorded on its destination shard only */

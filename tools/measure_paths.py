@@ -6,7 +6,7 @@ the JNI shim sees. One JSON line per measurement on stdout.
     python tools/measure_paths.py [--quick] [--sparse] [--rowsum] [--dot] [--axpy [--out FILE]] [--topk [--out FILE]]
                                   [--adagrad [--out FILE]] [--pairs [--out FILE]] [--init [--out FILE]]
                                   [--groups [--out FILE]] [--adam [--out FILE]] [--sampler [--out FILE]]
-                                  [--rowwise [--out FILE]] [--ftrl [--out FILE]]
+                                  [--rowwise [--out FILE]] [--ftrl [--out FILE]] [--wbag [--out FILE]]
 
 --sparse runs only the sparse-row-pull leg (dense getRows against getRowsSparse on a cfg5 shard).
 --rowsum runs only the grouped row-sum leg (getRowsSum against a dense row pull plus a reduction by the
@@ -40,6 +40,9 @@ profiles/rowwise_adagrad/rowwise_push.jsonl (or FILE).
 --ftrl runs only the FTRL-proximal row push leg (updateRowsFtrl against coalescing, row pulls of weights and
 state, the step and two row pushes by the caller, on cfg5 shards, with the Adam fold on the same rows beside
 it) and appends its lines to profiles/ftrl/ftrl_push.jsonl (or FILE).
+--wbag runs only the weighted-bag pull leg (the weighted row-sum pull and the grouped row-dot pull against a
+dense row pull plus the arithmetic by the caller, and against their unchanged neighbour kernels, on a cfg5
+shard) and appends its lines to profiles/wbag/wbag_pull.jsonl (or FILE).
 --sampler runs only the row sampler leg (glint_sampler_draw_dev against torch.rand plus torch.searchsorted over a
 device cdf, at m = 2^20 Zipf counts and n = 2^24 draws, with and without exclusion; the creates and the host
 draw by wall clock) and appends its lines to profiles/sampler/sampler.jsonl (or FILE).
@@ -1407,6 +1410,169 @@ def groups_leg(rng, out_path):
         torch.cuda.empty_cache()
 
 
+def wbag_leg(rng, out_path):
+    """Weighted row-sum pull and grouped row-dot pull on cfg5's per-GPU 2^17 x 512 Double shard: 2^14
+    Zipf(1.0) rows in groups of 1, 16 and 128 rows and as one group of all of them (the row-sum leg's request
+    shapes), weights uniform in [0, 1), one standard-normal vector per group. The baselines are what a
+    caller does today and never run the code under test: for the weighted sum a dense row pull into an
+    n x cols buffer, a multiply and a segment reduction (torch index_add_ on the device, np.add.reduceat on
+    the host); for the grouped dot a dense row pull and (rows * x[group]).sum(1). Beside them the unchanged
+    neighbour kernels on the same request in the same process: the unweighted row-sum pull, and the row dot
+    pull with one vector over the same rows. All legs alternate inside each of 5 rounds after a warm-up
+    round; host legs by wall clock, device legs by one HIP event pair per call; the four kernels alone by
+    their prof ids. One JSON line per group length, also appended to out_path."""
+    shard_rows, cols, n, rounds = 1 << 17, 512, 1 << 14, 5
+    msh = glint_amd.PartialMatrix(glint_amd.RangePartition(0, 0, shard_rows), cols, "double", 0)
+    h = msh.handle
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(7)
+    all_rows = torch.arange(shard_rows, dtype=torch.int64, device=dev)
+    for r0 in range(0, shard_rows, 1 << 14):  # fill in slices of whole rows
+        vv = torch.rand((1 << 14, cols), dtype=torch.float64, device=dev, generator=gen) - 0.5
+        msh.updateRows(all_rows[r0:r0 + (1 << 14)].contiguous(), vv)
+    del vv
+    rows = zipf_keys(rng, shard_rows, n, 1.0)
+    wts = rng.random(n)
+    d_rows, d_wts = torch.from_numpy(rows).to(dev), torch.from_numpy(wts).to(dev)
+    dense_out = np.empty((n, cols), np.float64)
+    d_dense = torch.empty((n, cols), dtype=torch.float64, device=dev)
+
+    def ev_ms(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b)
+
+    def wall_ms(fn):
+        t0 = time.perf_counter()
+        fn()
+        return (time.perf_counter() - t0) * 1e3
+
+    def stats(ms):
+        return {"mean": float(np.mean(ms)), "min": float(np.min(ms)), "max": float(np.max(ms))}
+
+    def prof_ms(kid, fn, reps=5):
+        """The kernel alone: mean over `reps` launches after a warm-up, by its prof id."""
+        fn()
+        torch.cuda.synchronize()
+        lib.glint_prof_reset(h)
+        lib.glint_prof_enable(h, 1)
+        for _ in range(reps):
+            fn()
+        torch.cuda.synchronize()
+        ms = kernel_ms(h, kid)
+        lib.glint_prof_enable(h, 0)
+        return ms
+
+    Path(out_path).parent.mkdir(parents=True, exist_ok=True)
+    for glen in (1, 16, 128, n):
+        g = n // glen
+        offsets = np.arange(g + 1, dtype=np.int64) * glen
+        group = np.repeat(np.arange(g, dtype=np.int64), glen)
+        x = rng.standard_normal((g, cols))
+        d_off, d_group, d_x = (torch.from_numpy(a).to(dev) for a in (offsets, group, x))
+        wsum_out, wsum_base = np.empty((g, cols)), np.empty((g, cols))
+        gdot_out, gdot_base = np.empty(n), np.empty(n)
+        d_wsum, d_wsum_base, d_sum = (torch.empty((g, cols), dtype=torch.float64, device=dev) for _ in range(3))
+        d_gdot, d_gdot_base, d_dot1 = (torch.empty(n, dtype=torch.float64, device=dev) for _ in range(3))
+
+        def host_wsum():
+            assert lib.glint_mat_pull_rows_wsum(h, rows.ctypes.data, n, offsets.ctypes.data, g, wts.ctypes.data,
+                                                wsum_out.ctypes.data) == 0
+
+        def host_wsum_base():
+            assert lib.glint_mat_pull_rows(h, rows.ctypes.data, dense_out.ctypes.data, n) == 0
+            np.add.reduceat(wts[:, None] * dense_out, offsets[:-1], axis=0, out=wsum_base)
+
+        def host_gdot():
+            assert lib.glint_mat_pull_rows_gdot(h, rows.ctypes.data, n, offsets.ctypes.data, g, x.ctypes.data,
+                                                gdot_out.ctypes.data) == 0
+
+        def host_gdot_base():
+            assert lib.glint_mat_pull_rows(h, rows.ctypes.data, dense_out.ctypes.data, n) == 0
+            np.sum(dense_out * x[group], axis=1, out=gdot_base)
+
+        def dev_wsum():
+            assert lib.glint_mat_pull_rows_wsum_dev(h, d_rows.data_ptr(), n, d_off.data_ptr(), g, d_wts.data_ptr(),
+                                                    d_wsum.data_ptr(), stream) == 0
+
+        def dev_wsum_base():
+            assert lib.glint_mat_pull_rows_dev(h, d_rows.data_ptr(), d_dense.data_ptr(), n, stream) == 0
+            d_wsum_base.zero_()
+            d_wsum_base.index_add_(0, d_group, d_wts[:, None] * d_dense)
+
+        def dev_sum():  # the unchanged neighbour of the weighted sum
+            assert lib.glint_mat_pull_rows_sum_dev(h, d_rows.data_ptr(), n, d_off.data_ptr(), g, d_sum.data_ptr(),
+                                                   stream) == 0
+
+        def dev_gdot():
+            assert lib.glint_mat_pull_rows_gdot_dev(h, d_rows.data_ptr(), n, d_off.data_ptr(), g, d_x.data_ptr(),
+                                                    d_gdot.data_ptr(), stream) == 0
+
+        def dev_gdot_base():
+            assert lib.glint_mat_pull_rows_dev(h, d_rows.data_ptr(), d_dense.data_ptr(), n, stream) == 0
+            torch.sum(d_dense * d_x.index_select(0, d_group), dim=1, out=d_gdot_base)
+
+        def dev_dot1():  # the unchanged neighbour of the grouped dot: one vector over the same rows
+            assert lib.glint_mat_pull_rows_dot_dev(h, d_rows.data_ptr(), n, d_x.data_ptr(), 1, d_dot1.data_ptr(),
+                                                   stream) == 0
+
+        legs = {"host_wsum_base": (wall_ms, host_wsum_base), "host_wsum": (wall_ms, host_wsum),
+                "host_gdot_base": (wall_ms, host_gdot_base), "host_gdot": (wall_ms, host_gdot),
+                "dev_wsum_base": (ev_ms, dev_wsum_base), "dev_wsum": (ev_ms, dev_wsum), "dev_sum": (ev_ms, dev_sum),
+                "dev_gdot_base": (ev_ms, dev_gdot_base), "dev_gdot": (ev_ms, dev_gdot), "dev_dot1": (ev_ms, dev_dot1)}
+        t = {k: [] for k in legs}
+        for rnd in range(rounds + 1):  # round 0 warms up; the legs alternate inside every round
+            for k, (timer, fn) in legs.items():
+                torch.cuda.synchronize()
+                v = timer(fn)
+                if rnd:
+                    t[k].append(v)
+        m = {k: stats(v) for k, v in t.items()}
+        k_wsum, k_sum = prof_ms(N.GLINT_K_PULL_ROWS_SUM, dev_wsum), prof_ms(N.GLINT_K_PULL_ROWS_SUM, dev_sum)
+        k_gdot, k_dot1 = prof_ms(N.GLINT_K_PULL_ROWS_DOT, dev_gdot), prof_ms(N.GLINT_K_PULL_ROWS_DOT, dev_dot1)
+        msh.sync(stream)
+        # the answers agree with the baselines up to the order of the additions and the fused products the
+        # baselines may use: 1e-9 of each element's sum of |terms|
+        ok_wsum = bool((np.abs(wsum_out - wsum_base) <=
+                        1e-9 * np.add.reduceat(wts[:, None] * np.abs(dense_out), offsets[:-1], axis=0)).all())
+        ok_gdot = bool((np.abs(gdot_out - gdot_base) <= 1e-9 * np.sum(np.abs(dense_out * x[group]), axis=1)).all())
+        assert ok_wsum and ok_gdot
+        same = bool(np.array_equal(d_wsum.cpu().numpy(), wsum_out) and np.array_equal(d_gdot.cpu().numpy(), gdot_out))
+        assert same
+        vs = 8
+        line = dict(
+            op="wbag_pull", pattern="zipf1.0 rows", shape=[shard_rows, cols], rows=n, group_len=glen, groups=g,
+            rounds=rounds,
+            host_wsum_ms=m["host_wsum"], host_wsum_baseline_ms=m["host_wsum_base"],
+            host_wsum_speedup=m["host_wsum_base"]["mean"] / m["host_wsum"]["mean"],
+            host_wsum_bytes_staged=n * 8 + (g + 1) * 8 + n * vs, host_wsum_bytes_back=g * cols * vs,
+            host_gdot_ms=m["host_gdot"], host_gdot_baseline_ms=m["host_gdot_base"],
+            host_gdot_speedup=m["host_gdot_base"]["mean"] / m["host_gdot"]["mean"],
+            host_gdot_bytes_staged=n * 8 + (g + 1) * 8 + g * cols * vs, host_gdot_bytes_back=n * vs,
+            host_baseline_bytes_staged=n * 8, host_baseline_bytes_back=n * cols * vs,
+            dev_wsum_ms=m["dev_wsum"], dev_wsum_baseline_ms=m["dev_wsum_base"],
+            dev_wsum_speedup=m["dev_wsum_base"]["mean"] / m["dev_wsum"]["mean"], dev_sum_ms=m["dev_sum"],
+            dev_gdot_ms=m["dev_gdot"], dev_gdot_baseline_ms=m["dev_gdot_base"],
+            dev_gdot_speedup=m["dev_gdot_base"]["mean"] / m["dev_gdot"]["mean"], dev_dot1_ms=m["dev_dot1"],
+            wsum_kernel_ms=k_wsum, sum_kernel_ms=k_sum, wsum_over_sum_kernel=k_wsum / k_sum,
+            gdot_kernel_ms=k_gdot, dot1_kernel_ms=k_dot1, gdot_over_dot1_kernel=k_gdot / k_dot1,
+            within_bound=True, host_and_device_answers_identical=same,
+            note="host_*: C calls on pageable numpy arrays into reused buffers, synchronous, wall ms; dev_*: one HIP "
+                 "event pair per call. Baselines: glint_mat_pull_rows[_dev] into an n x cols buffer, then weights * "
+                 "rows and np.add.reduceat (torch: zero_ + index_add_) for the weighted sum, (rows * "
+                 "x[group]).sum(1) for the grouped dot. dev_sum / dev_dot1: the unchanged neighbours on the same "
+                 "request -- glint_mat_pull_rows_sum_dev, and glint_mat_pull_rows_dot_dev with one vector. Legs "
+                 "alternate inside each of `rounds` rounds after one warm-up round. *_kernel_ms: the kernel alone "
+                 "(glint_prof), mean of 5 launches after a warm-up")
+        emit(**line)
+        with open(out_path, "a") as f:
+            f.write(json.dumps(line) + "\n")
+    msh.destroy()
+
+
 def init_leg(rng, out_path):
     """Shard fill and uniform init on cfg5's per-GPU shard (2^17 x 512 Double) and a word2vec-shaped one
     (2^17 x 128 Float): the whole shard, and a list of 2^14 distinct rows in random order. The calls under
@@ -1787,6 +1953,11 @@ def main():
         out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
             str(Path(__file__).resolve().parent.parent / "profiles" / "adam" / "adam_push.jsonl")
         adam_leg(np.random.default_rng(42), out)
+        return
+    if "--wbag" in sys.argv:
+        out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
+            str(Path(__file__).resolve().parent.parent / "profiles" / "wbag" / "wbag_pull.jsonl")
+        wbag_leg(np.random.default_rng(42), out)
         return
     if "--ftrl" in sys.argv:
         out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else \
