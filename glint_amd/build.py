@@ -35,7 +35,7 @@ HIP_SOURCES = [CSRC / "glint_gpu.hip", CSRC / "glint_sort.hip", CSRC / "glint_ro
 PLAN_HEADERS = [CSRC / "glint_push_plan.h", CSRC / "glint_bin_plan.h", CSRC / "glint_topk_plan.h",
                 CSRC / "glint_init_plan.h", CSRC / "glint_wire_plan.h", CSRC / "glint_sample_plan.h"]
 HIP_HEADERS = [CSRC / "glint_kernels.h", CSRC / "glint_device.h", CSRC / "glint_host.h", CSRC / "glint_dot.h",
-               CSRC / "glint_axpy.h", CSRC / "glint_group.h",
+               CSRC / "glint_axpy.h", CSRC / "glint_group.h", CSRC / "glint_rowstep.h",
                ROOT / "include" / "glint_gpu.h", *PLAN_HEADERS]
 HIP_DEPS = HIP_SOURCES + HIP_HEADERS
 OBJ_DIR = ROOT / "build" / "obj"

@@ -1322,68 +1322,58 @@ inline bool same_rows(const glint_shard* w, const glint_shard* h) {
          a.start == b.start && (a.kind == 0 || (a.cidx == b.cidx && a.cparts == b.cparts));
 }
 
-// argument checks of glint_mat_push_rows_adagrad / _dev: a Float or Double matrix shard, a second shard
-// of the same type, device and partition that shares no memory with it (the same handle, or two views of
-// one slab that overlap), glint_mat_push_rows's sizes, lr a number and eps >= 0 (a NaN eps fails the test)
-inline int push_adagrad_args(const glint_shard* w, const glint_shard* h, const void* rows, const void* grads,
-                             int64_t n, double lr, double eps) {
-  if (!w || !h || w == h || w->part.cols == 0) return GLINT_EINVAL;
-  if (w->dtype != GLINT_F32 && w->dtype != GLINT_F64) return GLINT_EINVAL;
-  if (!same_rows(w, h) || w->part.cols != h->part.cols || w->part.pitch != h->part.pitch) return GLINT_EINVAL;
-  const uintptr_t wa = (uintptr_t)w->data, ha = (uintptr_t)h->data;
-  const uintptr_t bytes = (uintptr_t)w->elems * w->vsize;  // (h's too: same size, pitch and type)
-  if (wa < ha + bytes && ha < wa + bytes) return GLINT_EINVAL;
-  if (n < 0 || n >= ((i64)1 << 32) - kSortTile) return GLINT_EINVAL;
-  if (n > 0 && (!rows || !grads)) return GLINT_EINVAL;
-  if (lr != lr || !(eps >= 0)) return GLINT_EINVAL;
-  return GLINT_OK;
-}
-
-// argument checks of glint_mat_push_rows_adam / _dev: push_adagrad_args' with a state shard of 2 * cols
-// columns (the packed moments; its pitch and byte size are its own), both betas in [0, 1) (a NaN fails
-// the test) and step >= 1
-inline int push_adam_args(const glint_shard* w, const glint_shard* s, const void* rows, const void* grads, int64_t n,
-                          double lr, double beta1, double beta2, double eps, int64_t step) {
+// What the argument checks of the four optimizer row pushes share: a Float or Double matrix shard `w`, a
+// second shard `s` of the same type, device and partition that shares no memory with it (the same handle,
+// or two views of one slab that overlap; each byte range has its own shard's size), glint_mat_push_rows's
+// sizes. The shape of `s` and the hyper-parameters are each call's own.
+inline int push_step_args(const glint_shard* w, const glint_shard* s, const void* rows, const void* grads, int64_t n) {
   if (!w || !s || w == s || w->part.cols == 0) return GLINT_EINVAL;
   if (w->dtype != GLINT_F32 && w->dtype != GLINT_F64) return GLINT_EINVAL;
-  if (!same_rows(w, s) || s->part.cols != 2 * w->part.cols || s->part.pitch < s->part.cols) return GLINT_EINVAL;
+  if (!same_rows(w, s)) return GLINT_EINVAL;
   const uintptr_t wa = (uintptr_t)w->data, sa = (uintptr_t)s->data;
   if (wa < sa + (uintptr_t)s->elems * s->vsize && sa < wa + (uintptr_t)w->elems * w->vsize) return GLINT_EINVAL;
   if (n < 0 || n >= ((i64)1 << 32) - kSortTile) return GLINT_EINVAL;
   if (n > 0 && (!rows || !grads)) return GLINT_EINVAL;
+  return GLINT_OK;
+}
+
+// argument checks of glint_mat_push_rows_adagrad / _dev: push_step_args', a state shard of the weights'
+// cols and pitch, lr a number and eps >= 0 (a NaN eps fails the test)
+inline int push_adagrad_args(const glint_shard* w, const glint_shard* h, const void* rows, const void* grads,
+                             int64_t n, double lr, double eps) {
+  if (int rc = push_step_args(w, h, rows, grads, n)) return rc;
+  if (w->part.cols != h->part.cols || w->part.pitch != h->part.pitch) return GLINT_EINVAL;
+  if (lr != lr || !(eps >= 0)) return GLINT_EINVAL;
+  return GLINT_OK;
+}
+
+// argument checks of glint_mat_push_rows_adam / _dev: push_step_args', a state shard of 2 * cols columns
+// (the packed moments), lr and eps as Adagrad's, both betas in [0, 1) (a NaN fails the test) and step >= 1
+inline int push_adam_args(const glint_shard* w, const glint_shard* s, const void* rows, const void* grads, int64_t n,
+                          double lr, double beta1, double beta2, double eps, int64_t step) {
+  if (int rc = push_step_args(w, s, rows, grads, n)) return rc;
+  if (s->part.cols != 2 * w->part.cols || s->part.pitch < s->part.cols) return GLINT_EINVAL;
   if (lr != lr || !(eps >= 0)) return GLINT_EINVAL;
   if (!(0 <= beta1 && beta1 < 1) || !(0 <= beta2 && beta2 < 1) || step < 1) return GLINT_EINVAL;
   return GLINT_OK;
 }
 
-// argument checks of glint_mat_push_rows_adagrad_rowwise / _dev: push_adagrad_args' with a state that is
-// a vector shard (one accumulator per row) of the weights' type, device, size and partition; the two byte
-// ranges, each of its own shard's size, may not overlap
+// argument checks of glint_mat_push_rows_adagrad_rowwise / _dev: push_step_args', a state that is a vector
+// shard (one accumulator per row), lr and eps as Adagrad's
 inline int push_adagrad_rowwise_args(const glint_shard* w, const glint_shard* h, const void* rows, const void* grads,
                                      int64_t n, double lr, double eps) {
-  if (!w || !h || w == h || w->part.cols == 0 || h->part.cols != 0) return GLINT_EINVAL;
-  if (w->dtype != GLINT_F32 && w->dtype != GLINT_F64) return GLINT_EINVAL;
-  if (!same_rows(w, h)) return GLINT_EINVAL;
-  const uintptr_t wa = (uintptr_t)w->data, ha = (uintptr_t)h->data;
-  if (wa < ha + (uintptr_t)h->elems * h->vsize && ha < wa + (uintptr_t)w->elems * w->vsize) return GLINT_EINVAL;
-  if (n < 0 || n >= ((i64)1 << 32) - kSortTile) return GLINT_EINVAL;
-  if (n > 0 && (!rows || !grads)) return GLINT_EINVAL;
+  if (int rc = push_step_args(w, h, rows, grads, n)) return rc;
+  if (h->part.cols != 0) return GLINT_EINVAL;
   if (lr != lr || !(eps >= 0)) return GLINT_EINVAL;
   return GLINT_OK;
 }
 
-// argument checks of glint_mat_push_rows_ftrl / _dev: push_adam_args' about the two shards (the state packs
-// z and n in 2 * cols columns), n and the pointers; alpha > 0, beta, l1 and l2 >= 0 (a NaN fails each test)
-// and all four finite
+// argument checks of glint_mat_push_rows_ftrl / _dev: push_step_args', a state shard of 2 * cols columns
+// (the packed z and n); alpha > 0, beta, l1 and l2 >= 0 (a NaN fails each test) and all four finite
 inline int push_ftrl_args(const glint_shard* w, const glint_shard* s, const void* rows, const void* grads, int64_t n,
                           double alpha, double beta, double l1, double l2) {
-  if (!w || !s || w == s || w->part.cols == 0) return GLINT_EINVAL;
-  if (w->dtype != GLINT_F32 && w->dtype != GLINT_F64) return GLINT_EINVAL;
-  if (!same_rows(w, s) || s->part.cols != 2 * w->part.cols || s->part.pitch < s->part.cols) return GLINT_EINVAL;
-  const uintptr_t wa = (uintptr_t)w->data, sa = (uintptr_t)s->data;
-  if (wa < sa + (uintptr_t)s->elems * s->vsize && sa < wa + (uintptr_t)w->elems * w->vsize) return GLINT_EINVAL;
-  if (n < 0 || n >= ((i64)1 << 32) - kSortTile) return GLINT_EINVAL;
-  if (n > 0 && (!rows || !grads)) return GLINT_EINVAL;
+  if (int rc = push_step_args(w, s, rows, grads, n)) return rc;
+  if (s->part.cols != 2 * w->part.cols || s->part.pitch < s->part.cols) return GLINT_EINVAL;
   if (!(alpha > 0) || !(beta >= 0) || !(l1 >= 0) || !(l2 >= 0)) return GLINT_EINVAL;
   if (std::isinf(alpha) || std::isinf(beta) || std::isinf(l1) || std::isinf(l2)) return GLINT_EINVAL;
   return GLINT_OK;
@@ -1598,6 +1588,22 @@ int dev_call2(glint_shard* a, glint_shard* b, int args_rc, void* stream, F body)
     (void)pick(both[i], stream);
   }
   return body((hipStream_t)stream);
+}
+
+// An optimizer row push: its push_rows_*<V> (glint_host.h), which all take the two shards, rows, grads, n,
+// the call's scalars S and the stream.
+template <typename... S>
+using StepPush = int (*)(glint_shard*, glint_shard*, const i64*, const void*, i64, S..., hipStream_t);
+
+// The device-resident entry of an optimizer row push whose argument check gave args_rc: pf for Float
+// weights, pd for Double, with the scalars k.
+template <typename... S>
+int step_push_dev(glint_shard* w, glint_shard* s, int args_rc, const int64_t* rows, const void* grads, int64_t n,
+                  void* stream, StepPush<S...> pf, StepPush<S...> pd, S... k) {
+  if (args_rc == GLINT_OK && n == 0) return GLINT_OK;
+  return dev_call2(w, s, args_rc, stream, [&](hipStream_t st) -> int {
+    return (w->dtype == GLINT_F64 ? pd : pf)(w, s, (const i64*)rows, grads, n, k..., st);
+  });
 }
 
 // What a host-pointer call does first, under the shard's lock: a slab with views is refused, the open
@@ -2122,47 +2128,28 @@ int glint_mat_push_rows_as_dev(glint_shard_t s, const int64_t* rows, const void*
 
 int glint_mat_push_rows_adagrad_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows, const void* grads,
                                     int64_t n, double lr, double eps, void* stream) {
-  const int args_rc = push_adagrad_args(weights, state, rows, grads, n, lr, eps);
-  if (args_rc == GLINT_OK && n == 0) return GLINT_OK;
-  return dev_call2(weights, state, args_rc, stream, [&](hipStream_t st) -> int {
-    if (weights->dtype == GLINT_F64)
-      return push_rows_adagrad<double>(weights, state, (const i64*)rows, grads, n, lr, eps, st);
-    return push_rows_adagrad<float>(weights, state, (const i64*)rows, grads, n, lr, eps, st);
-  });
+  return step_push_dev(weights, state, push_adagrad_args(weights, state, rows, grads, n, lr, eps), rows, grads, n,
+                       stream, push_rows_adagrad<float>, push_rows_adagrad<double>, lr, eps);
 }
 
 int glint_mat_push_rows_adam_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows, const void* grads,
                                  int64_t n, double lr, double beta1, double beta2, double eps, int64_t step,
                                  void* stream) {
-  const int args_rc = push_adam_args(weights, state, rows, grads, n, lr, beta1, beta2, eps, step);
-  if (args_rc == GLINT_OK && n == 0) return GLINT_OK;
-  return dev_call2(weights, state, args_rc, stream, [&](hipStream_t st) -> int {
-    if (weights->dtype == GLINT_F64)
-      return push_rows_adam<double>(weights, state, (const i64*)rows, grads, n, lr, beta1, beta2, eps, step, st);
-    return push_rows_adam<float>(weights, state, (const i64*)rows, grads, n, lr, beta1, beta2, eps, step, st);
-  });
+  return step_push_dev(weights, state, push_adam_args(weights, state, rows, grads, n, lr, beta1, beta2, eps, step),
+                       rows, grads, n, stream, push_rows_adam<float>, push_rows_adam<double>, lr, beta1, beta2, eps,
+                       (i64)step);
 }
 
 int glint_mat_push_rows_adagrad_rowwise_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows,
                                             const void* grads, int64_t n, double lr, double eps, void* stream) {
-  const int args_rc = push_adagrad_rowwise_args(weights, state, rows, grads, n, lr, eps);
-  if (args_rc == GLINT_OK && n == 0) return GLINT_OK;
-  return dev_call2(weights, state, args_rc, stream, [&](hipStream_t st) -> int {
-    if (weights->dtype == GLINT_F64)
-      return push_rows_adagrad_rowwise<double>(weights, state, (const i64*)rows, grads, n, lr, eps, st);
-    return push_rows_adagrad_rowwise<float>(weights, state, (const i64*)rows, grads, n, lr, eps, st);
-  });
+  return step_push_dev(weights, state, push_adagrad_rowwise_args(weights, state, rows, grads, n, lr, eps), rows, grads,
+                       n, stream, push_rows_adagrad_rowwise<float>, push_rows_adagrad_rowwise<double>, lr, eps);
 }
 
 int glint_mat_push_rows_ftrl_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows, const void* grads,
                                  int64_t n, double alpha, double beta, double l1, double l2, void* stream) {
-  const int args_rc = push_ftrl_args(weights, state, rows, grads, n, alpha, beta, l1, l2);
-  if (args_rc == GLINT_OK && n == 0) return GLINT_OK;
-  return dev_call2(weights, state, args_rc, stream, [&](hipStream_t st) -> int {
-    if (weights->dtype == GLINT_F64)
-      return push_rows_ftrl<double>(weights, state, (const i64*)rows, grads, n, alpha, beta, l1, l2, st);
-    return push_rows_ftrl<float>(weights, state, (const i64*)rows, grads, n, alpha, beta, l1, l2, st);
-  });
+  return step_push_dev(weights, state, push_ftrl_args(weights, state, rows, grads, n, alpha, beta, l1, l2), rows, grads,
+                       n, stream, push_rows_ftrl<float>, push_rows_ftrl<double>, alpha, beta, l1, l2);
 }
 
 int glint_mat_pull_pairs_dot_dev(glint_shard_t a, glint_shard_t b, const int64_t* rows_a, const int64_t* rows_b,
@@ -2940,6 +2927,25 @@ int host_call(glint_shard* a, glint_shard* b, HostRows rows, bool nothing, std::
   return host_staged(a, in, extra, body);
 }
 
+// The host-pointer entry of an optimizer row push (glint_mat_push_rows_adagrad, _adam, _adagrad_rowwise,
+// _ftrl) whose argument check gave args_rc: under both shards' locks every row is checked, against the
+// weights shard, before anything is staged (a rejected message changes neither shard), then rows and grads
+// are staged in one block -- n * 8 + n * cols values -- and the push runs on the weights shard's stream,
+// which first waits for the state shard's (its flushed ring entries and open batch included). The call ends
+// synchronised, so later calls on either shard see the step. Nothing comes back but the error state.
+// pf, pd and k as step_push_dev's.
+template <typename... S>
+int step_push_host(glint_shard* w, glint_shard* s, int args_rc, const int64_t* rows, const void* grads, int64_t n,
+                   StepPush<S...> pf, StepPush<S...> pd, S... k) {
+  if (args_rc) return args_rc;
+  if (n == 0) return GLINT_OK;
+  return host_call(w, s, {rows, nullptr, n}, false,
+                   {{rows, (size_t)n * 8}, {grads, (size_t)n * (size_t)w->part.cols * w->vsize}}, 0,
+                   [&](const Staged& st, hipStream_t stream, HostBack*) -> int {
+                     return (w->dtype == GLINT_F64 ? pd : pf)(w, s, (const i64*)st.p[0], st.p[1], n, k..., stream);
+                   });
+}
+
 int host_push(glint_shard* s, bool mat, const int64_t* keys, const int32_t* cols, const void* vals, int64_t n,
               int flags) {
   if (n < 0 || (n > 0 && (!keys || !vals || (mat && !cols)))) return GLINT_EINVAL;
@@ -3284,79 +3290,29 @@ int glint_mat_push_rows_as(glint_shard_t s, const int64_t* rows, const void* val
                    });
 }
 
-// glint_mat_push_rows_adagrad: under both shards' locks every row is checked, against the weights shard,
-// before anything is staged (a rejected message changes neither shard), then rows and grads are staged
-// in one block -- n * 8 + n * cols values -- and the push runs on the weights shard's stream, which first
-// waits for the state shard's. The call ends synchronised, so later calls on either shard see the step.
-// Nothing comes back but the error state.
 int glint_mat_push_rows_adagrad(glint_shard_t weights, glint_shard_t state, const int64_t* rows, const void* grads,
                                 int64_t n, double lr, double eps) {
-  if (int rc = push_adagrad_args(weights, state, rows, grads, n, lr, eps)) return rc;
-  if (n == 0) return GLINT_OK;
-  return host_call(weights, state, {rows, nullptr, n}, false,
-                   {{rows, (size_t)n * 8}, {grads, (size_t)n * (size_t)weights->part.cols * weights->vsize}}, 0,
-                   [&](const Staged& st, hipStream_t stream, HostBack*) -> int {
-                     const i64* d_rows = (const i64*)st.p[0];
-                     if (weights->dtype == GLINT_F64)
-                       return push_rows_adagrad<double>(weights, state, d_rows, st.p[1], n, lr, eps, stream);
-                     return push_rows_adagrad<float>(weights, state, d_rows, st.p[1], n, lr, eps, stream);
-                   });
+  return step_push_host(weights, state, push_adagrad_args(weights, state, rows, grads, n, lr, eps), rows, grads, n,
+                        push_rows_adagrad<float>, push_rows_adagrad<double>, lr, eps);
 }
 
-// glint_mat_push_rows_adam: glint_mat_push_rows_adagrad's host side word for word -- every row checked
-// against the weights shard under both locks before anything is staged, rows and grads staged in one
-// block, the push on the weights shard's stream behind an event on the state shard's, the call ends
-// synchronised. Nothing comes back but the error state.
 int glint_mat_push_rows_adam(glint_shard_t weights, glint_shard_t state, const int64_t* rows, const void* grads,
                              int64_t n, double lr, double beta1, double beta2, double eps, int64_t step) {
-  if (int rc = push_adam_args(weights, state, rows, grads, n, lr, beta1, beta2, eps, step)) return rc;
-  if (n == 0) return GLINT_OK;
-  return host_call(weights, state, {rows, nullptr, n}, false,
-                   {{rows, (size_t)n * 8}, {grads, (size_t)n * (size_t)weights->part.cols * weights->vsize}}, 0,
-                   [&](const Staged& st, hipStream_t stream, HostBack*) -> int {
-                     const i64* d_rows = (const i64*)st.p[0];
-                     if (weights->dtype == GLINT_F64)
-                       return push_rows_adam<double>(weights, state, d_rows, st.p[1], n, lr, beta1, beta2, eps, step,
-                                                     stream);
-                     return push_rows_adam<float>(weights, state, d_rows, st.p[1], n, lr, beta1, beta2, eps, step,
-                                                  stream);
-                   });
+  return step_push_host(weights, state, push_adam_args(weights, state, rows, grads, n, lr, beta1, beta2, eps, step),
+                        rows, grads, n, push_rows_adam<float>, push_rows_adam<double>, lr, beta1, beta2, eps,
+                        (i64)step);
 }
 
-// glint_mat_push_rows_adagrad_rowwise: glint_mat_push_rows_adagrad's host side word for word -- every row
-// checked against the weights shard under both locks before anything is staged, rows and grads staged in
-// one block, the push on the weights shard's stream behind the state vector's (its flushed ring entries
-// and open batch included), the call ends synchronised. Nothing comes back but the error state.
 int glint_mat_push_rows_adagrad_rowwise(glint_shard_t weights, glint_shard_t state, const int64_t* rows,
                                         const void* grads, int64_t n, double lr, double eps) {
-  if (int rc = push_adagrad_rowwise_args(weights, state, rows, grads, n, lr, eps)) return rc;
-  if (n == 0) return GLINT_OK;
-  return host_call(weights, state, {rows, nullptr, n}, false,
-                   {{rows, (size_t)n * 8}, {grads, (size_t)n * (size_t)weights->part.cols * weights->vsize}}, 0,
-                   [&](const Staged& st, hipStream_t stream, HostBack*) -> int {
-                     const i64* d_rows = (const i64*)st.p[0];
-                     if (weights->dtype == GLINT_F64)
-                       return push_rows_adagrad_rowwise<double>(weights, state, d_rows, st.p[1], n, lr, eps, stream);
-                     return push_rows_adagrad_rowwise<float>(weights, state, d_rows, st.p[1], n, lr, eps, stream);
-                   });
+  return step_push_host(weights, state, push_adagrad_rowwise_args(weights, state, rows, grads, n, lr, eps), rows, grads,
+                        n, push_rows_adagrad_rowwise<float>, push_rows_adagrad_rowwise<double>, lr, eps);
 }
 
-// glint_mat_push_rows_ftrl: glint_mat_push_rows_adam's host side word for word -- every row checked against
-// the weights shard under both locks before anything is staged, rows and grads staged in one block, the
-// push on the weights shard's stream behind an event on the state shard's, the call ends synchronised.
-// Nothing comes back but the error state.
 int glint_mat_push_rows_ftrl(glint_shard_t weights, glint_shard_t state, const int64_t* rows, const void* grads,
                              int64_t n, double alpha, double beta, double l1, double l2) {
-  if (int rc = push_ftrl_args(weights, state, rows, grads, n, alpha, beta, l1, l2)) return rc;
-  if (n == 0) return GLINT_OK;
-  return host_call(weights, state, {rows, nullptr, n}, false,
-                   {{rows, (size_t)n * 8}, {grads, (size_t)n * (size_t)weights->part.cols * weights->vsize}}, 0,
-                   [&](const Staged& st, hipStream_t stream, HostBack*) -> int {
-                     const i64* d_rows = (const i64*)st.p[0];
-                     if (weights->dtype == GLINT_F64)
-                       return push_rows_ftrl<double>(weights, state, d_rows, st.p[1], n, alpha, beta, l1, l2, stream);
-                     return push_rows_ftrl<float>(weights, state, d_rows, st.p[1], n, alpha, beta, l1, l2, stream);
-                   });
+  return step_push_host(weights, state, push_ftrl_args(weights, state, rows, grads, n, alpha, beta, l1, l2), rows,
+                        grads, n, push_rows_ftrl<float>, push_rows_ftrl<double>, alpha, beta, l1, l2);
 }
 
 // glint_mat_pull_pairs_dot: every pair is checked, then the two row arrays are staged in one block, the

@@ -435,6 +435,15 @@ inline unsigned grid_for(i64 units, i64 per_block, i64 cap) {
   return (unsigned)g;
 }
 
+// Column slices of a row of `cols` values of V for the row folds' one wave per (item, slice): a slice is
+// 64 lanes x 16 B when v16 (the caller's test: cols * sizeof(V) a multiple of 16, its operand aligned),
+// else 64 lanes x one element.
+template <typename V>
+inline i64 row_slices(i64 cols, bool v16) {
+  const i64 slice = v16 ? 1024 : 64 * (i64)sizeof(V);  // bytes
+  return (cols * (i64)sizeof(V) + slice - 1) / slice;
+}
+
 // resident blocks per CU for a kernel (occupancy query, once per kernel), capped at the measured best
 template <auto Kernel>
 inline int blocks_per_cu(int cap) {

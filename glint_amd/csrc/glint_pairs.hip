@@ -255,8 +255,7 @@ int push_pairs_axpy(glint_shard* dst, glint_shard* src, const i64* rows_dst, con
   int rc = rows_front(dst, rows_dst, n, flags, st, &f);
   if (rc) return rc;
   const bool v16 = ((i64)dst->part.cols * (i64)sizeof(V)) % 16 == 0;
-  const i64 slices = ((i64)dst->part.cols * (i64)sizeof(V) + (v16 ? 1023 : 64 * (i64)sizeof(V) - 1)) /
-                     (v16 ? 1024 : 64 * (i64)sizeof(V));
+  const i64 slices = row_slices<V>(dst->part.cols, v16);
   const unsigned gf = grid_for(n * slices, kTPB / 64, (i64)dst->cus * 8);
   void (*fold)(const u32*, const u32*, const uint2*, const u32*, const i64*, const V*, const V*, PartDesc, V*,
                PartDesc, ErrState*) =

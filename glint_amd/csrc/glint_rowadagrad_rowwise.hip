@@ -16,28 +16,24 @@
 // operation is rounded on its own in the shard's type (include/glint_gpu.h has the contract); nothing of it
 // depends on the alignment of grads or the grid. No atomics, no LDS.
 #include "glint_dot.h"  // dot_step, x_load: the row dot pull's arithmetic, word for word
-#include "glint_host.h"
+#include "glint_rowstep.h"
 
 namespace glint {
 
-constexpr int kRowwiseDepth = 16;  // gradient loads in flight per wave (the Adagrad fold's depth)
 #ifndef GLINT_ROWWISE_KEEP_BUILD  // (a variant build for measurement sets 0: every row sums its run twice)
 #define GLINT_ROWWISE_KEEP_BUILD GLINT_ROWWISE_KEEP_STRIPS
 #endif
 constexpr int kRowwiseKeep = GLINT_ROWWISE_KEEP_BUILD;  // strips kept in registers between the two passes
 
-__device__ __forceinline__ double rowwise_sqrt(double x) { return __builtin_sqrt(x); }
-__device__ __forceinline__ float rowwise_sqrt(float x) { return __builtin_sqrtf(x); }
-
 // The five row scalars of the contract, each rounded on its own; returns k and leaves h' in h. ss / C is
 // a division, not a product with a reciprocal, and k = lr / d is one division per row. sqrt and / are the
-// compiler's IEEE ones (adagrad_step's note, glint_rowadagrad.hip).
+// compiler's IEEE ones (step_sqrt's note, glint_rowstep.h).
 template <typename V>
 __device__ __forceinline__ V rowwise_scalars(V& h, V ss, V C, V lr, V eps) {
 #pragma clang fp contract(off)
   const V s = ss / C;
   const V h2 = h + s;
-  const V r = rowwise_sqrt(h2);
+  const V r = step_sqrt(h2);
   const V d = r + eps;
   const V k = lr / d;
   h = h2;
@@ -50,49 +46,6 @@ __device__ __forceinline__ V rowwise_update(V w, V k, V G) {
 #pragma clang fp contract(off)
   const V p = k * G;
   return w - p;
-}
-
-// G = a lane's E columns [c, c + E) of records [start, start + len) of the sorted list, added to +0 in
-// list order: rows_adagrad_item's loop (64 record ids per wave handed round by readlane, kRowwiseDepth
-// loads in flight). GW: the E columns by one 16-B load, else one by one; columns at or past cols are zeros.
-template <typename V, int E, bool GW>
-__device__ __forceinline__ void rowwise_strip_sum(V (&G)[E], const u32* __restrict__ idx, u32 start, u32 len,
-                                                  const V* __restrict__ grads, i64 c, i64 cols, int lane) {
-#pragma unroll
-  for (int k = 0; k < E; ++k) G[k] = V(0);
-  for (u32 b = 0; b < len; b += 64) {
-    const u32 m = len - b < 64u ? len - b : 64u;
-    const u32 mine = (u32)lane < m ? idx[(i64)start + b + lane] : 0u;  // 64 record indices, one per lane
-    for (u32 j = 0; j < m; j += kRowwiseDepth) {
-      V t[kRowwiseDepth][E];
-      if (m - j >= (u32)kRowwiseDepth) {
-#pragma unroll
-        for (int d = 0; d < kRowwiseDepth; ++d) {
-          const u32 id = (u32)__builtin_amdgcn_readlane((int)mine, (int)(j + d));
-          x_load<V, E, GW>(t[d], grads + (i64)id * cols, c, cols);
-        }
-#pragma unroll
-        for (int d = 0; d < kRowwiseDepth; ++d)
-#pragma unroll
-          for (int k = 0; k < E; ++k) G[k] = vadd(G[k], t[d][k]);
-      } else {  // the run's last few records (wave-uniform tests)
-#pragma unroll
-        for (int d = 0; d < kRowwiseDepth; ++d) {
-          if (j + d < m) {
-            const u32 id = (u32)__builtin_amdgcn_readlane((int)mine, (int)(j + d));
-            x_load<V, E, GW>(t[d], grads + (i64)id * cols, c, cols);
-          }
-        }
-#pragma unroll
-        for (int d = 0; d < kRowwiseDepth; ++d) {
-          if (j + d < m) {
-#pragma unroll
-            for (int k = 0; k < E; ++k) G[k] = vadd(G[k], t[d][k]);
-          }
-        }
-      }
-    }
-  }
 }
 
 // Persistent grid; one wave per item. A strip is 64 lanes x E columns, lane L owning columns
@@ -127,14 +80,18 @@ __global__ __launch_bounds__(kTPB) void rows_adagrad_rowwise_fold_kernel(
 #pragma unroll
       for (int s = 0; s < KEEP; ++s) {
         if ((u32)s < nstrips) {
-          rowwise_strip_sum<V, E, GW>(G[s], idx, e.x, e.y, grads, ((i64)s * 64 + lane) * E, cols, lane);
+#pragma unroll
+          for (int k = 0; k < E; ++k) G[s][k] = V(0);
+          run_sum<V, E, x_load<V, E, GW>>(G[s], idx, e.x, e.y, grads, ((i64)s * 64 + lane) * E, cols, lane);
 #pragma unroll
           for (int k = 0; k < E; ++k) acc = dot_step(acc, G[s][k], G[s][k]);
         }
       }
     } else {
       for (u32 s = 0; s < nstrips; ++s) {
-        rowwise_strip_sum<V, E, GW>(G[0], idx, e.x, e.y, grads, ((i64)s * 64 + lane) * E, cols, lane);
+#pragma unroll
+        for (int k = 0; k < E; ++k) G[0][k] = V(0);
+        run_sum<V, E, x_load<V, E, GW>>(G[0], idx, e.x, e.y, grads, ((i64)s * 64 + lane) * E, cols, lane);
 #pragma unroll
         for (int k = 0; k < E; ++k) acc = dot_step(acc, G[0][k], G[0][k]);
       }
@@ -163,7 +120,9 @@ __global__ __launch_bounds__(kTPB) void rows_adagrad_rowwise_fold_kernel(
         const i64 c = ((i64)s * 64 + lane) * E;
         V w[E];
         slice_load<V, E, VEC16>(w, wrow, c, cols);
-        rowwise_strip_sum<V, E, GW>(G[0], idx, e.x, e.y, grads, c, cols, lane);
+#pragma unroll
+        for (int j = 0; j < E; ++j) G[0][j] = V(0);
+        run_sum<V, E, x_load<V, E, GW>>(G[0], idx, e.x, e.y, grads, c, cols, lane);
 #pragma unroll
         for (int j = 0; j < E; ++j) w[j] = rowwise_update<V>(w[j], k, G[0][j]);
         slice_store<V, E, VEC16>(w, wrow, c, cols);

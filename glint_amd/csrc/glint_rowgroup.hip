@@ -177,8 +177,7 @@ int push_rows_grouped(glint_shard* s, const i64* rows, i64 n, const i64* grp_ptr
   rows_group_ids_kernel<<<grid_for(n, kTPB, (i64)s->cus * 8), kTPB, 0, st>>>(grp_ptr, g, n, gids);
   HIPCHK(hipGetLastError());
   const bool v16 = ((i64)s->part.cols * (i64)sizeof(V)) % 16 == 0 && aligned(vals, 16);
-  const i64 slices = ((i64)s->part.cols * (i64)sizeof(V) + (v16 ? 1023 : 64 * (i64)sizeof(V) - 1)) /
-                     (v16 ? 1024 : 64 * (i64)sizeof(V));
+  const i64 slices = row_slices<V>(s->part.cols, v16);
   const unsigned gf = grid_for(n * slices, kTPB / 64, (i64)s->cus * 8);
   if (v16)
     return f.strict ? launch_group_fold<V, true, false>(s, f, gids, vals, coef, gf, st)

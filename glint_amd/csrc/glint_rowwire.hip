@@ -228,8 +228,7 @@ int push_rows_as(glint_shard* s, const i64* rows, const void* vals, i64 n, int f
   int rc = rows_front(s, rows, n, flags, st, &f);
   if (rc) return rc;
   const bool v16 = ((i64)s->part.cols * (i64)sizeof(V)) % 16 == 0 && aligned(vals, 8);
-  const i64 slices = ((i64)s->part.cols * (i64)sizeof(V) + (v16 ? 1023 : 64 * (i64)sizeof(V) - 1)) /
-                     (v16 ? 1024 : 64 * (i64)sizeof(V));
+  const i64 slices = row_slices<V>(s->part.cols, v16);
   const unsigned gf = grid_for(n * slices, kTPB / 64, (i64)s->cus * 8);
   void (*fold)(const u32*, const u32*, const uint2*, const u32*, const T*, V*, PartDesc) =
       v16 ? (f.strict ? rows_fold_as_kernel<WIRE, true, false> : rows_fold_as_kernel<WIRE, true, true>)
