@@ -65,9 +65,20 @@ def bucket(owner: np.ndarray, nparts: int):
     return order, offsets
 
 
+def _buckets(model, keys) -> list:
+    """The fan-out every call of both models makes: ``[(p, shard, idx)]`` for the non-empty partitions of
+    ``keys`` (global keys) in ascending p, ``idx`` the positions of partition p's keys in the caller's order.
+    The partitioner validates every key first, so a key outside the model raises before any shard is called."""
+    order, off = bucket(model.partitioner.partition_indices(keys), len(model.shards))
+    return [(p, sh, order[off[p]:off[p + 1]]) for p, sh in enumerate(model.shards) if off[p + 1] > off[p]]
+
+
 def _same_partitioner(a, b) -> bool:
     """Whether two partitioners lay the same key space out the same way: one kind, the same partitions."""
     return type(a) is type(b) and [repr(p) for p in a.all()] == [repr(p) for p in b.all()]
+
+
+_TWICE_COLS = "state: expected a matrix with this one's partitioner, rows and dtype and twice its cols"
 
 
 def _init_fanout(model, rows, call) -> bool:
@@ -79,11 +90,8 @@ def _init_fanout(model, rows, call) -> bool:
             call(sh, None)
         return True
     rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
-    order, off = bucket(model.partitioner.partition_indices(rows), len(model.shards))
-    for p, sh in enumerate(model.shards):
-        idx = order[off[p]:off[p + 1]]
-        if idx.size:
-            call(sh, rows[idx])
+    for _, sh, idx in _buckets(model, rows):
+        call(sh, rows[idx])
     return True
 
 
@@ -118,23 +126,15 @@ class BigVector(_InitMixin):
     def push(self, keys, values, deterministic: bool = False) -> bool:
         keys = np.ascontiguousarray(keys, dtype=np.int64)
         values = np.ascontiguousarray(values, dtype=self.shards[0].np_dtype)
-        owner = self.partitioner.partition_indices(keys)
-        order, off = bucket(owner, len(self.shards))
-        for p, sh in enumerate(self.shards):
-            idx = order[off[p]:off[p + 1]]
-            if idx.size:
-                sh.update(keys[idx], values[idx], deterministic=deterministic)
+        for _, sh, idx in _buckets(self, keys):
+            sh.update(keys[idx], values[idx], deterministic=deterministic)
         return True
 
     def pull(self, keys) -> np.ndarray:
         keys = np.ascontiguousarray(keys, dtype=np.int64)
-        owner = self.partitioner.partition_indices(keys)
-        order, off = bucket(owner, len(self.shards))
         out = np.zeros(keys.shape, dtype=self.shards[0].np_dtype)
-        for p, sh in enumerate(self.shards):
-            idx = order[off[p]:off[p + 1]]
-            if idx.size:
-                out[idx] = sh.get(keys[idx])
+        for _, sh, idx in _buckets(self, keys):
+            out[idx] = sh.get(keys[idx])
         return out
 
     def destroy(self) -> bool:
@@ -160,29 +160,39 @@ class BigMatrix(_InitMixin):
         rows = np.ascontiguousarray(rows, dtype=np.int64)
         cols = np.ascontiguousarray(cols, dtype=np.int32)
         values = np.ascontiguousarray(values, dtype=self.shards[0].np_dtype)
-        owner = self.partitioner.partition_indices(rows)
-        order, off = bucket(owner, len(self.shards))
-        for p, sh in enumerate(self.shards):
-            idx = order[off[p]:off[p + 1]]
-            if idx.size:
-                sh.update(rows[idx], cols[idx], values[idx], deterministic=deterministic)
+        for _, sh, idx in _buckets(self, rows):
+            sh.update(rows[idx], cols[idx], values[idx], deterministic=deterministic)
         return True
+
+    # what the row calls below validate before any shard is called ----------------------------------------
+    def _rows_values(self, rows, values, dtype, name: str = "values") -> tuple:
+        """Flat int64 rows and their value rows ((n, cols) or flat, called ``name``) as an (n, cols) array."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        values = np.ascontiguousarray(values, dtype=dtype)
+        if values.size != rows.size * self.cols:
+            raise ValueError(f"{name}: {values.size} elements, expected {rows.size} rows x {self.cols} columns")
+        return rows, values.reshape(rows.size, self.cols)
+
+    @staticmethod
+    def _offsets(rows: np.ndarray, offsets) -> tuple:
+        """The offsets of a grouped call over flat ``rows`` as (flat int64 array, g)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        if offsets.size < 1 or offsets[0] != 0 or offsets[-1] != rows.size or (np.diff(offsets) < 0).any():
+            raise ValueError("offsets must be non-decreasing from 0 to len(rows)")
+        return offsets, offsets.size - 1
+
+    def _check_queries(self, x: np.ndarray) -> None:
+        """Caller vectors: (cols,), or (q, cols) with q >= 1."""
+        if x.shape != (self.cols,) and not (x.ndim == 2 and x.shape[1] == self.cols and x.shape[0] >= 1):
+            raise ValueError(f"x: shape {x.shape}, expected ({self.cols},) or (q, {self.cols})")
 
     def pushRows(self, rows, values, deterministic: bool = False) -> bool:
         """Whole rows: row rows[i] += values[i] (an (n, cols) array, or flat), in the caller's order
         -- ``push`` of the triplets (rows[i], c, values[i][c]) without expanding them. Bucketed by
         partition as ``push``; one PartialMatrix.updateRows per non-empty partition."""
-        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
-        values = np.ascontiguousarray(values, dtype=self.shards[0].np_dtype)
-        if values.size != rows.size * self.cols:
-            raise ValueError(f"values: {values.size} elements, expected {rows.size} rows x {self.cols} columns")
-        values = values.reshape(rows.size, self.cols)
-        owner = self.partitioner.partition_indices(rows)
-        order, off = bucket(owner, len(self.shards))
-        for p, sh in enumerate(self.shards):
-            idx = order[off[p]:off[p + 1]]
-            if idx.size:
-                sh.updateRows(rows[idx], values[idx], deterministic=deterministic)
+        rows, values = self._rows_values(rows, values, self.shards[0].np_dtype)
+        for _, sh, idx in _buckets(self, rows):
+            sh.updateRows(rows[idx], values[idx], deterministic=deterministic)
         return True
 
     def pushRowsAs(self, rows, values, wire: str, deterministic: bool = False) -> bool:
@@ -197,15 +207,9 @@ class BigMatrix(_InitMixin):
         values = np.asarray(values)
         if values.dtype != np_wire:
             raise ValueError(f"values: dtype {values.dtype}, expected {np.dtype(np_wire).name} for wire type {wire!r}")
-        if values.size != rows.size * self.cols:
-            raise ValueError(f"values: {values.size} elements, expected {rows.size} rows x {self.cols} columns")
-        values = np.ascontiguousarray(values).reshape(rows.size, self.cols)
-        owner = self.partitioner.partition_indices(rows)
-        order, off = bucket(owner, len(self.shards))
-        for p, sh in enumerate(self.shards):
-            idx = order[off[p]:off[p + 1]]
-            if idx.size:
-                sh.updateRowsAs(rows[idx], values[idx], wire, deterministic=deterministic)
+        rows, values = self._rows_values(rows, values, np_wire)
+        for _, sh, idx in _buckets(self, rows):
+            sh.updateRowsAs(rows[idx], values[idx], wire, deterministic=deterministic)
         return True
 
     def pullRowsAs(self, rows, wire: str) -> np.ndarray:
@@ -215,13 +219,9 @@ class BigMatrix(_InitMixin):
         by partition as ``pull``; one PartialMatrix.getRowsAs per non-empty partition."""
         np_wire = resolve_wire(wire)[1]
         rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
-        owner = self.partitioner.partition_indices(rows)
-        order, off = bucket(owner, len(self.shards))
         out = np.zeros((rows.size, self.cols), dtype=np_wire)
-        for p, sh in enumerate(self.shards):
-            idx = order[off[p]:off[p + 1]]
-            if idx.size:
-                out[idx] = sh.getRowsAs(rows[idx], wire)
+        for _, sh, idx in _buckets(self, rows):
+            out[idx] = sh.getRowsAs(rows[idx], wire)
         return out
 
     def pushAxpy(self, rows, coef, x, deterministic: bool = False) -> bool:
@@ -234,17 +234,12 @@ class BigMatrix(_InitMixin):
         dtype = self.shards[0].np_dtype
         x = np.ascontiguousarray(x, dtype=dtype)
         coef = np.ascontiguousarray(coef, dtype=dtype)
-        if x.shape != (self.cols,) and not (x.ndim == 2 and x.shape[1] == self.cols and x.shape[0] >= 1):
-            raise ValueError(f"x: shape {x.shape}, expected ({self.cols},) or (q, {self.cols})")
+        self._check_queries(x)
         q = 1 if x.ndim == 1 else x.shape[0]
         if coef.shape != (rows.size, q) and not (q == 1 and coef.shape == (rows.size,)):
             raise ValueError(f"coef: shape {coef.shape}, expected ({rows.size}, {q})")
-        owner = self.partitioner.partition_indices(rows)
-        order, off = bucket(owner, len(self.shards))
-        for p, sh in enumerate(self.shards):
-            idx = order[off[p]:off[p + 1]]
-            if idx.size:
-                sh.updateRowsAxpy(rows[idx], coef[idx], x, deterministic=deterministic)
+        for _, sh, idx in _buckets(self, rows):
+            sh.updateRowsAxpy(rows[idx], coef[idx], x, deterministic=deterministic)
         return True
 
     def pushGroups(self, rows, offsets, values, weights=None, deterministic: bool = False) -> bool:
@@ -263,10 +258,7 @@ class BigMatrix(_InitMixin):
         g_p * cols * itemsize``, plus ``n_p * itemsize`` with ``weights`` -- against ``8 n_p + n_p * cols *
         itemsize`` for ``pushRows`` of the expanded rows."""
         rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
-        if offsets.size < 1 or offsets[0] != 0 or offsets[-1] != rows.size or (np.diff(offsets) < 0).any():
-            raise ValueError("offsets must be non-decreasing from 0 to len(rows)")
-        g = offsets.size - 1
+        offsets, g = self._offsets(rows, offsets)
         dtype = self.shards[0].np_dtype
         values = np.ascontiguousarray(values, dtype=dtype)
         if values.size != g * self.cols:
@@ -276,18 +268,14 @@ class BigMatrix(_InitMixin):
             weights = np.ascontiguousarray(weights, dtype=dtype).reshape(-1)
             if weights.size != rows.size:
                 raise ValueError(f"weights: {weights.size} values, expected {rows.size}")
-        owner = self.partitioner.partition_indices(rows)
-        order, off = bucket(owner, len(self.shards))
         group = np.repeat(np.arange(g, dtype=np.int64), np.diff(offsets))  # the group of every record
-        for p, sh in enumerate(self.shards):
-            idx = order[off[p]:off[p + 1]]  # caller's order, so its groups are non-decreasing
-            if idx.size:
-                counts = np.bincount(group[idx], minlength=g)
-                has = np.flatnonzero(counts)  # the groups with a record here, ascending
-                sub = np.zeros(has.size + 1, dtype=np.int64)
-                np.cumsum(counts[has], out=sub[1:])
-                sh.updateRowsGrouped(rows[idx], sub, values[has], None if weights is None else weights[idx],
-                                     deterministic=deterministic)
+        for _, sh, idx in _buckets(self, rows):  # idx in the caller's order, so its groups are non-decreasing
+            counts = np.bincount(group[idx], minlength=g)
+            has = np.flatnonzero(counts)  # the groups with a record here, ascending
+            sub = np.zeros(has.size + 1, dtype=np.int64)
+            np.cumsum(counts[has], out=sub[1:])
+            sh.updateRowsGrouped(rows[idx], sub, values[has], None if weights is None else weights[idx],
+                                 deterministic=deterministic)
         return True
 
     def pushAdagrad(self, state: "BigMatrix", rows, grads, lr: float, eps: float = 1e-10) -> bool:
@@ -299,24 +287,29 @@ class BigMatrix(_InitMixin):
         PartialMatrix.updateRowsAdagrad per non-empty partition, with its rows and gradient rows in the
         caller's order and that partition's state shard. A row lives in one partition, so the bits are the
         shard's."""
-        if not isinstance(state, BigMatrix):
-            raise ValueError("state: expected a BigMatrix")
+        return self._push_step(state, BigMatrix, 1, "state: expected a matrix with this one's partitioner, rows, "
+                               "cols and dtype", rows, grads,
+                               lambda sh, st, r, g: sh.updateRowsAdagrad(st, r, g, lr, eps))
+
+    def _push_step(self, state, kind, state_cols_factor: int, message: str, rows, grads, call) -> bool:
+        """What the optimizer row pushes share: ``state`` is a model of class ``kind`` laid out as this one --
+        a BigVector of ``rows`` keys, or a BigMatrix of ``rows`` rows and ``state_cols_factor * cols`` columns,
+        else ValueError(``message``) -- and each non-empty partition gets one ``call(shard, its state shard,
+        its rows, their gradient rows)``, in the caller's order."""
+        if not isinstance(state, kind):
+            raise ValueError(f"state: expected a {kind.__name__}")
         dtype = self.shards[0].np_dtype
-        if (state.rows, state.cols) != (self.rows, self.cols) or len(state.shards) != len(self.shards) \
+        if kind is BigVector:
+            fits = state.size == self.rows
+        else:
+            fits = (state.rows, state.cols) == (self.rows, state_cols_factor * self.cols)
+        if not fits or len(state.shards) != len(self.shards) \
                 or np.dtype(state.shards[0].np_dtype) != np.dtype(dtype) \
                 or not _same_partitioner(state.partitioner, self.partitioner):
-            raise ValueError("state: expected a matrix with this one's partitioner, rows, cols and dtype")
-        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
-        grads = np.ascontiguousarray(grads, dtype=dtype)
-        if grads.size != rows.size * self.cols:
-            raise ValueError(f"grads: {grads.size} elements, expected {rows.size} rows x {self.cols} columns")
-        grads = grads.reshape(rows.size, self.cols)
-        owner = self.partitioner.partition_indices(rows)
-        order, off = bucket(owner, len(self.shards))
-        for p, sh in enumerate(self.shards):
-            idx = order[off[p]:off[p + 1]]
-            if idx.size:
-                sh.updateRowsAdagrad(state.shards[p], rows[idx], grads[idx], lr, eps)
+            raise ValueError(message)
+        rows, grads = self._rows_values(rows, grads, dtype, "grads")
+        for p, sh, idx in _buckets(self, rows):
+            call(sh, state.shards[p], rows[idx], grads[idx])
         return True
 
     def pushAdagradRowwise(self, state: "BigVector", rows, grads, lr: float, eps: float = 1e-10) -> bool:
@@ -330,25 +323,9 @@ class BigMatrix(_InitMixin):
         PartialMatrix.updateRowsAdagradRowwise per non-empty partition, with its rows and gradient rows in
         the caller's order and that partition's state shard. A row lives in one partition, so the bits are
         the shard's."""
-        if not isinstance(state, BigVector):
-            raise ValueError("state: expected a BigVector")
-        dtype = self.shards[0].np_dtype
-        if state.size != self.rows or len(state.shards) != len(self.shards) \
-                or np.dtype(state.shards[0].np_dtype) != np.dtype(dtype) \
-                or not _same_partitioner(state.partitioner, self.partitioner):
-            raise ValueError("state: expected a vector with this matrix's partitioner, rows and dtype")
-        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
-        grads = np.ascontiguousarray(grads, dtype=dtype)
-        if grads.size != rows.size * self.cols:
-            raise ValueError(f"grads: {grads.size} elements, expected {rows.size} rows x {self.cols} columns")
-        grads = grads.reshape(rows.size, self.cols)
-        owner = self.partitioner.partition_indices(rows)
-        order, off = bucket(owner, len(self.shards))
-        for p, sh in enumerate(self.shards):
-            idx = order[off[p]:off[p + 1]]
-            if idx.size:
-                sh.updateRowsAdagradRowwise(state.shards[p], rows[idx], grads[idx], lr, eps)
-        return True
+        return self._push_step(state, BigVector, 0, "state: expected a vector with this matrix's partitioner, rows "
+                               "and dtype", rows, grads,
+                               lambda sh, st, r, g: sh.updateRowsAdagradRowwise(st, r, g, lr, eps))
 
     def pushAdam(self, state: "BigMatrix", rows, grads, lr: float, step: int, beta1: float = 0.9,
                  beta2: float = 0.999, eps: float = 1e-8) -> bool:
@@ -362,26 +339,8 @@ class BigMatrix(_InitMixin):
         partition as ``pushRows``; one PartialMatrix.updateRowsAdam per non-empty partition, with its rows
         and gradient rows in the caller's order and that partition's state shard. A row lives in one
         partition, so the bits are the shard's."""
-        if not isinstance(state, BigMatrix):
-            raise ValueError("state: expected a BigMatrix")
-        dtype = self.shards[0].np_dtype
-        if (state.rows, state.cols) != (self.rows, 2 * self.cols) or len(state.shards) != len(self.shards) \
-                or np.dtype(state.shards[0].np_dtype) != np.dtype(dtype) \
-                or not _same_partitioner(state.partitioner, self.partitioner):
-            raise ValueError("state: expected a matrix with this one's partitioner, rows and dtype and "
-                             "twice its cols")
-        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
-        grads = np.ascontiguousarray(grads, dtype=dtype)
-        if grads.size != rows.size * self.cols:
-            raise ValueError(f"grads: {grads.size} elements, expected {rows.size} rows x {self.cols} columns")
-        grads = grads.reshape(rows.size, self.cols)
-        owner = self.partitioner.partition_indices(rows)
-        order, off = bucket(owner, len(self.shards))
-        for p, sh in enumerate(self.shards):
-            idx = order[off[p]:off[p + 1]]
-            if idx.size:
-                sh.updateRowsAdam(state.shards[p], rows[idx], grads[idx], lr, step, beta1, beta2, eps)
-        return True
+        return self._push_step(state, BigMatrix, 2, _TWICE_COLS, rows, grads,
+                               lambda sh, st, r, g: sh.updateRowsAdam(st, r, g, lr, step, beta1, beta2, eps))
 
     def pushFtrl(self, state: "BigMatrix", rows, grads, alpha: float, beta: float = 1.0, l1: float = 0.0,
                  l2: float = 0.0) -> bool:
@@ -396,46 +355,23 @@ class BigMatrix(_InitMixin):
         ``pushRows``; one PartialMatrix.updateRowsFtrl per non-empty partition, with its rows and gradient
         rows in the caller's order and that partition's state shard. A row lives in one partition, so the
         bits are the shard's."""
-        if not isinstance(state, BigMatrix):
-            raise ValueError("state: expected a BigMatrix")
-        dtype = self.shards[0].np_dtype
-        if (state.rows, state.cols) != (self.rows, 2 * self.cols) or len(state.shards) != len(self.shards) \
-                or np.dtype(state.shards[0].np_dtype) != np.dtype(dtype) \
-                or not _same_partitioner(state.partitioner, self.partitioner):
-            raise ValueError("state: expected a matrix with this one's partitioner, rows and dtype and "
-                             "twice its cols")
-        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
-        grads = np.ascontiguousarray(grads, dtype=dtype)
-        if grads.size != rows.size * self.cols:
-            raise ValueError(f"grads: {grads.size} elements, expected {rows.size} rows x {self.cols} columns")
-        grads = grads.reshape(rows.size, self.cols)
-        owner = self.partitioner.partition_indices(rows)
-        order, off = bucket(owner, len(self.shards))
-        for p, sh in enumerate(self.shards):
-            idx = order[off[p]:off[p + 1]]
-            if idx.size:
-                sh.updateRowsFtrl(state.shards[p], rows[idx], grads[idx], alpha, beta, l1, l2)
-        return True
+        return self._push_step(state, BigMatrix, 2, _TWICE_COLS, rows, grads,
+                               lambda sh, st, r, g: sh.updateRowsFtrl(st, r, g, alpha, beta, l1, l2))
 
     def pull(self, rows, cols=None) -> np.ndarray:
         """pull(rows, cols): elements (AsyncBigMatrix.scala:96-130); pull(rows): whole rows as an
         (n, cols) array (AsyncBigMatrix.scala:53-86)."""
         rows = np.ascontiguousarray(rows, dtype=np.int64)
-        owner = self.partitioner.partition_indices(rows)
-        order, off = bucket(owner, len(self.shards))
+        buckets = _buckets(self, rows)
         if cols is None:
             out = np.zeros((rows.size, self.cols), dtype=self.shards[0].np_dtype)
-            for p, sh in enumerate(self.shards):
-                idx = order[off[p]:off[p + 1]]
-                if idx.size:
-                    out[idx] = sh.getRows(rows[idx])
+            for _, sh, idx in buckets:
+                out[idx] = sh.getRows(rows[idx])
             return out
         cols = np.ascontiguousarray(cols, dtype=np.int32)
         out = np.zeros(rows.shape, dtype=self.shards[0].np_dtype)
-        for p, sh in enumerate(self.shards):
-            idx = order[off[p]:off[p + 1]]
-            if idx.size:
-                out[idx] = sh.get(rows[idx], cols[idx])
+        for _, sh, idx in buckets:
+            out[idx] = sh.get(rows[idx], cols[idx])
         return out
 
     def pullSparse(self, rows):
@@ -445,22 +381,18 @@ class BigMatrix(_InitMixin):
         partition as ``pull``; one PartialMatrix.getRowsSparse per non-empty partition, and the partial
         triples merged without a Python loop over rows."""
         rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
-        owner = self.partitioner.partition_indices(rows)
-        order, off = bucket(owner, len(self.shards))
         n = rows.size
         counts = np.zeros(n, dtype=np.int64)  # entries per request, caller's order
         src0 = np.zeros(n, dtype=np.int64)    # where a request's entries start in the concatenated partials
         part_cols, part_vals, base = [], [], 0
-        for p, sh in enumerate(self.shards):
-            idx = order[off[p]:off[p + 1]]
-            if idx.size:
-                ip, c, v = sh.getRowsSparse(rows[idx])
-                ip = np.asarray(ip, dtype=np.int64)
-                counts[idx] = np.diff(ip)
-                src0[idx] = base + ip[:-1]
-                part_cols.append(np.asarray(c, dtype=np.int32))
-                part_vals.append(np.asarray(v, dtype=self.shards[0].np_dtype))
-                base += int(ip[-1])
+        for _, sh, idx in _buckets(self, rows):
+            ip, c, v = sh.getRowsSparse(rows[idx])
+            ip = np.asarray(ip, dtype=np.int64)
+            counts[idx] = np.diff(ip)
+            src0[idx] = base + ip[:-1]
+            part_cols.append(np.asarray(c, dtype=np.int32))
+            part_vals.append(np.asarray(v, dtype=self.shards[0].np_dtype))
+            base += int(ip[-1])
         indptr = np.zeros(n + 1, dtype=np.int64)
         np.cumsum(counts, out=indptr[1:])
         if not base:
@@ -484,34 +416,27 @@ class BigMatrix(_InitMixin):
         With one partition that is the strict caller order; with several it is partition-major, caller's
         order inside a partition. Deterministic either way; Int/Long wrap."""
         rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
-        if offsets.size < 1 or offsets[0] != 0 or offsets[-1] != rows.size or (np.diff(offsets) < 0).any():
-            raise ValueError("offsets must be non-decreasing from 0 to len(rows)")
-        g = offsets.size - 1
+        offsets, g = self._offsets(rows, offsets)
         if weights is not None:
             weights = np.ascontiguousarray(weights, dtype=self.shards[0].np_dtype).reshape(-1)
             if weights.size != rows.size:
                 raise ValueError(f"weights: {weights.size} values, expected {rows.size}")
-        owner = self.partitioner.partition_indices(rows)
-        order, off = bucket(owner, len(self.shards))
         group = np.repeat(np.arange(g, dtype=np.int64), np.diff(offsets))  # the group of every record
         out = np.zeros((g, self.cols), dtype=self.shards[0].np_dtype)
         started = np.zeros(g, dtype=bool)  # groups that already hold a partition's partial
-        for p, sh in enumerate(self.shards):
-            idx = order[off[p]:off[p + 1]]  # caller's order, so its groups are non-decreasing
-            if idx.size:
-                sub = np.zeros(g + 1, dtype=np.int64)
-                np.cumsum(np.bincount(group[idx], minlength=g), out=sub[1:])
-                if weights is None:
-                    part = sh.getRowsSum(rows[idx], sub)
-                else:
-                    part = sh.getRowsSum(rows[idx], sub, weights=weights[idx])
-                part = np.asarray(part, dtype=out.dtype)
-                has = np.diff(sub) > 0
-                first, more = has & ~started, has & started
-                out[first] = part[first]
-                out[more] = out[more] + part[more]
-                started |= has
+        for _, sh, idx in _buckets(self, rows):  # idx in the caller's order, so its groups are non-decreasing
+            sub = np.zeros(g + 1, dtype=np.int64)
+            np.cumsum(np.bincount(group[idx], minlength=g), out=sub[1:])
+            if weights is None:
+                part = sh.getRowsSum(rows[idx], sub)
+            else:
+                part = sh.getRowsSum(rows[idx], sub, weights=weights[idx])
+            part = np.asarray(part, dtype=out.dtype)
+            has = np.diff(sub) > 0
+            first, more = has & ~started, has & started
+            out[first] = part[first]
+            out[more] = out[more] + part[more]
+            started |= has
         return out
 
     def pullAverage(self, rows, offsets) -> np.ndarray:
@@ -530,17 +455,12 @@ class BigMatrix(_InitMixin):
         shape = (rows.size,)
         if x is not None:
             x = np.ascontiguousarray(x, dtype=dtype)
-            if x.shape != (self.cols,) and not (x.ndim == 2 and x.shape[1] == self.cols and x.shape[0] >= 1):
-                raise ValueError(f"x: shape {x.shape}, expected ({self.cols},) or (q, {self.cols})")
+            self._check_queries(x)
             if x.ndim == 2:
                 shape = (rows.size, x.shape[0])
-        owner = self.partitioner.partition_indices(rows)
-        order, off = bucket(owner, len(self.shards))
         out = np.zeros(shape, dtype=dtype)
-        for p, sh in enumerate(self.shards):
-            idx = order[off[p]:off[p + 1]]
-            if idx.size:
-                out[idx] = sh.getRowsDot(rows[idx], x)
+        for _, sh, idx in _buckets(self, rows):
+            out[idx] = sh.getRowsDot(rows[idx], x)
         return out
 
     def pullGroupDot(self, rows, offsets, x) -> np.ndarray:
@@ -559,27 +479,20 @@ class BigMatrix(_InitMixin):
         g_p * cols * itemsize``; bytes back: ``n_p * itemsize`` -- against ``n_p * cols * itemsize`` back
         for ``pull`` of the rows."""
         rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
-        if offsets.size < 1 or offsets[0] != 0 or offsets[-1] != rows.size or (np.diff(offsets) < 0).any():
-            raise ValueError("offsets must be non-decreasing from 0 to len(rows)")
-        g = offsets.size - 1
+        offsets, g = self._offsets(rows, offsets)
         dtype = self.shards[0].np_dtype
         x = np.ascontiguousarray(x, dtype=dtype)
         if x.shape != (g, self.cols) and x.shape != (g * self.cols,):
             raise ValueError(f"x: shape {x.shape}, expected ({g}, {self.cols}) or ({g * self.cols},)")
         x = x.reshape(g, self.cols)
-        owner = self.partitioner.partition_indices(rows)
-        order, off = bucket(owner, len(self.shards))
         group = np.repeat(np.arange(g, dtype=np.int64), np.diff(offsets))  # the group of every record
         out = np.zeros(rows.size, dtype=dtype)
-        for p, sh in enumerate(self.shards):
-            idx = order[off[p]:off[p + 1]]  # caller's order, so its groups are non-decreasing
-            if idx.size:
-                counts = np.bincount(group[idx], minlength=g)
-                has = np.flatnonzero(counts)  # the groups with a record here, ascending
-                sub = np.zeros(has.size + 1, dtype=np.int64)
-                np.cumsum(counts[has], out=sub[1:])
-                out[idx] = sh.getRowsGroupDot(rows[idx], sub, x[has])
+        for _, sh, idx in _buckets(self, rows):  # idx in the caller's order, so its groups are non-decreasing
+            counts = np.bincount(group[idx], minlength=g)
+            has = np.flatnonzero(counts)  # the groups with a record here, ascending
+            sub = np.zeros(has.size + 1, dtype=np.int64)
+            np.cumsum(counts[has], out=sub[1:])
+            out[idx] = sh.getRowsGroupDot(rows[idx], sub, x[has])
         return out
 
     def _pair_buckets(self, other: "BigMatrix", name: str, rows, other_rows):
@@ -664,8 +577,7 @@ class BigMatrix(_InitMixin):
         (rank, row), so the answer does not depend on how the matrix is partitioned."""
         dtype = self.shards[0].np_dtype
         x = np.ascontiguousarray(x, dtype=dtype)
-        if x.shape != (self.cols,) and not (x.ndim == 2 and x.shape[1] == self.cols and x.shape[0] >= 1):
-            raise ValueError(f"x: shape {x.shape}, expected ({self.cols},) or (q, {self.cols})")
+        self._check_queries(x)
         k = int(k)
         if k < 1:
             raise ValueError(f"k: {k}, expected k >= 1")

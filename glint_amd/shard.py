@@ -42,15 +42,15 @@ def resolve_dtype(dtype) -> tuple:
     return _DTYPES[key]
 
 
-def check(rc: int, handle=None) -> None:
+def check(rc: int, handle=None, rec: Optional[int] = None) -> None:
     """Translate a C ABI status into the reference's exception types."""
     if rc == N.GLINT_OK:
         return
     if rc == N.GLINT_EOUTOFRANGE:
-        rec = -1
-        if handle is not None:
+        if rec is None:  # (wait and sync get the record with the status)
             v = C.c_int64(-1)
-            N.load().glint_shard_last_error(handle, C.byref(v))
+            if handle is not None:
+                N.load().glint_shard_last_error(handle, C.byref(v))
             rec = v.value
         raise ArrayIndexOutOfBoundsException(f"record {rec} is outside the partition", rec)
     if rc == N.GLINT_EDEVICE:
@@ -75,6 +75,33 @@ def _is_torch_cuda(x) -> bool:
 
 def _host(x, dtype) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(x, dtype=dtype))
+
+
+def _host_offsets(offsets) -> tuple:
+    """Host ``offsets`` of a grouped call as (flat int64 array, g)."""
+    o = _host(offsets, np.int64).reshape(-1)
+    if o.size < 1:
+        raise ValueError("offsets needs g + 1 entries")
+    return o, o.size - 1
+
+
+def _check_like(name: str, t, dtype, rows, elems: Optional[int] = None) -> None:
+    """A further device argument of a row call: a contiguous ``dtype`` CUDA tensor on the device of ``rows``
+    (which _check_dev ties to the shard's), of ``elems`` elements where the call fixes its size -- the kernels
+    take raw pointers."""
+    if not _is_torch_cuda(t) or t.dtype != dtype or not t.is_contiguous() or t.device != rows.device:
+        raise TypeError(f"{name}: expected a contiguous {dtype} CUDA tensor on rows' device")
+    if elems is not None and t.numel() != elems:
+        raise ValueError(f"{name}: {t.numel()} elements, expected {elems}")
+
+
+def _check_offsets_dev(offsets, rows) -> int:
+    """Device ``offsets`` of a grouped call, as _check_like with at least one entry; returns g."""
+    import torch
+    if not _is_torch_cuda(offsets) or offsets.dtype != torch.int64 or not offsets.is_contiguous() \
+            or offsets.device != rows.device or offsets.numel() < 1:
+        raise TypeError("offsets: expected a contiguous int64 CUDA tensor of g + 1 entries on rows' device")
+    return offsets.numel() - 1
 
 
 # wire types of the narrow-format row transport (glint_mat_pull_rows_as / glint_mat_push_rows_as):
@@ -164,10 +191,12 @@ class _Shard:
         else:
             raise TypeError(f"unsupported partition type {type(partition).__name__}")
         check(rc)
+        self._read_info()
+
+    def _read_info(self) -> None:
         sz, cl = C.c_int32(), C.c_int32()
         check(self.lib.glint_shard_info(self._h, C.byref(sz), C.byref(cl), None, None), self._h)
-        self.size = sz.value
-        self.cols = cl.value
+        self.size, self.cols = sz.value, cl.value
 
     @classmethod
     def view(cls, slab: "_Shard", partition: RangePartition, offset: int):
@@ -181,10 +210,8 @@ class _Shard:
         self.code, self.np_dtype = slab.code, slab.np_dtype
         self._h = C.c_void_p()
         check(self.lib.glint_shard_create_in(slab.handle, int(offset), partition.start, partition.end, C.byref(self._h)))
-        sz, cl = C.c_int32(), C.c_int32()
-        check(self.lib.glint_shard_info(self._h, C.byref(sz), C.byref(cl), None, None), self._h)
-        self.size, self.cols = sz.value, cl.value
-        if cl.value:
+        self._read_info()
+        if self.cols:
             self.rows = self.size
         self.slab = slab
         return self
@@ -326,18 +353,12 @@ class _Shard:
         """Until the push with this ticket (and every earlier one) is applied; raises GlintDeviceError if
         one of them failed to launch (rejected records raise at the enqueueing call instead)."""
         bad = C.c_int64(-1)
-        rc = self.lib.glint_shard_wait(self.handle, ticket, C.byref(bad))
-        if rc == N.GLINT_EOUTOFRANGE:
-            raise ArrayIndexOutOfBoundsException(f"record {bad.value} is outside the partition", bad.value)
-        check(rc, self.handle)
+        check(self.lib.glint_shard_wait(self.handle, ticket, C.byref(bad)), self.handle, bad.value)
 
     def sync(self, stream: Optional[int] = None) -> None:
         """Wait for device-resident calls and raise if any of them rejected a record."""
         bad = C.c_int64(-1)
-        rc = self.lib.glint_shard_sync(self.handle, stream, C.byref(bad))
-        if rc == N.GLINT_EOUTOFRANGE:
-            raise ArrayIndexOutOfBoundsException(f"record {bad.value} is outside the partition", bad.value)
-        check(rc, self.handle)
+        check(self.lib.glint_shard_sync(self.handle, stream, C.byref(bad)), self.handle, bad.value)
 
     def _dev_done(self, rc: int, t, sync: bool) -> None:
         """Ends a device-resident call enqueued on tensor ``t``'s stream: raise on ``rc``, then wait if ``sync``."""
@@ -382,16 +403,36 @@ class _Shard:
             if t.numel() != want:
                 raise ValueError(f"{name}: {t.numel()} elements, expected {want}")
 
-    def _host_out(self, out, shape) -> np.ndarray:
+    def _host_out(self, out, shape, dtype=None) -> np.ndarray:
         """A caller-provided host result buffer must be a writable C-contiguous array of the shard's
-        type and exact shape (the library writes n x sizeof(V) bytes into it)."""
+        type (or ``dtype``, a wire type's) and exact shape (the library writes n x sizeof(V) bytes into it)."""
+        dtype = self.np_dtype if dtype is None else dtype
         if out is None:
-            return np.empty(shape, dtype=self.np_dtype)
-        if not isinstance(out, np.ndarray) or out.dtype != self.np_dtype or out.shape != tuple(shape) \
+            return np.empty(shape, dtype=dtype)
+        if not isinstance(out, np.ndarray) or out.dtype != dtype or out.shape != tuple(shape) \
                 or not out.flags.c_contiguous or not out.flags.writeable:
-            raise ValueError(f"out must be a writable C-contiguous {np.dtype(self.np_dtype).name} array of shape "
+            raise ValueError(f"out must be a writable C-contiguous {np.dtype(dtype).name} array of shape "
                              f"{tuple(shape)}")
         return out
+
+    def _keys(self) -> np.ndarray:
+        """The global keys of the partition's elements (rows), in local order."""
+        p = self.partition
+        if isinstance(p, RangePartition):
+            return np.arange(p.start, p.start + self.size, dtype=np.int64)
+        return np.arange(self.size, dtype=np.int64) * p.numberOfPartitions + p.index
+
+    def push_wire(self, payload: bytes, deterministic: bool = False) -> int:
+        """Apply a RequestSerializer Push*Vector* byte image; returns its message id."""
+        buf = (C.c_uint8 * len(payload)).from_buffer_copy(payload)
+        mid = C.c_int32()
+        flags = N.GLINT_PUSH_DETERMINISTIC if deterministic else N.GLINT_PUSH_DEFAULT
+        check(self.lib.glint_push_wire(self.handle, buf, len(payload), C.byref(mid), flags), self.handle)
+        return mid.value
+
+    def pull_wire(self, payload: bytes) -> bytes:
+        """Answer a RequestSerializer PullVector byte image with the ResponseSerializer image."""
+        return _pull_wire(self, payload)
 
 
 class PartialVector(_Shard):
@@ -442,26 +483,9 @@ class PartialVector(_Shard):
         check(self.lib.glint_vec_pull(self.handle, k.ctypes.data, res.ctypes.data, k.size), self.handle)
         return res
 
-    def push_wire(self, payload: bytes, deterministic: bool = False) -> int:
-        """Apply a RequestSerializer Push*Vector* byte image; returns its message id."""
-        buf = (C.c_uint8 * len(payload)).from_buffer_copy(payload)
-        mid = C.c_int32()
-        flags = N.GLINT_PUSH_DETERMINISTIC if deterministic else N.GLINT_PUSH_DEFAULT
-        check(self.lib.glint_push_wire(self.handle, buf, len(payload), C.byref(mid), flags), self.handle)
-        return mid.value
-
-    def pull_wire(self, payload: bytes) -> bytes:
-        """Answer a RequestSerializer PullVector byte image with the ResponseSerializer image."""
-        return _pull_wire(self, payload)
-
     def to_numpy(self) -> np.ndarray:
         """Whole shard to host (a pull of every local key through the product path)."""
-        p = self.partition
-        if isinstance(p, RangePartition):
-            keys = np.arange(p.start, p.start + self.size, dtype=np.int64)
-        else:
-            keys = np.arange(self.size, dtype=np.int64) * p.numberOfPartitions + p.index
-        return self.get(keys)
+        return self.get(self._keys())
 
 
 class PartialMatrix(_Shard):
@@ -513,12 +537,18 @@ class PartialMatrix(_Shard):
                                                   self._stream_of(rows))
             self._dev_done(rc, rows, sync)
             return True
-        r = _host(rows, np.int64).reshape(-1)
-        v = _host(values, self.np_dtype).reshape(-1)
-        if v.size != r.size * self.cols:
-            raise ValueError(f"values: {v.size} elements, expected {r.size} rows x {self.cols} columns")
+        r, v = self._host_rows(rows, values, self.np_dtype)
         check(self.lib.glint_mat_push_rows(self.handle, r.ctypes.data, v.ctypes.data, r.size, flags), self.handle)
         return True
+
+    def _host_rows(self, rows, values, dtype, name: str = "values") -> tuple:
+        """Host rows and their dense value rows ((n, cols) or flat, called ``name``) as flat contiguous arrays
+        of int64 and ``dtype``."""
+        r = _host(rows, np.int64).reshape(-1)
+        v = _host(values, dtype).reshape(-1)
+        if v.size != r.size * self.cols:
+            raise ValueError(f"{name}: {v.size} elements, expected {r.size} rows x {self.cols} columns")
+        return r, v
 
     def updateRowsAs(self, rows, values, wire: str, deterministic: bool = False, sync: bool = True,
                      unordered: bool = False) -> bool:
@@ -546,9 +576,7 @@ class PartialMatrix(_Shard):
         v = np.asarray(values)
         if v.dtype != np_wire:
             raise ValueError(f"values: dtype {v.dtype}, expected {np.dtype(np_wire).name} for wire type {wire!r}")
-        v = np.ascontiguousarray(v).reshape(-1)
-        if v.size != r.size * self.cols:
-            raise ValueError(f"values: {v.size} elements, expected {r.size} rows x {self.cols} columns")
+        r, v = self._host_rows(r, v, np_wire)
         check(self.lib.glint_mat_push_rows_as(self.handle, r.ctypes.data, v.ctypes.data, r.size, code, flags),
               self.handle)
         return True
@@ -566,10 +594,8 @@ class PartialMatrix(_Shard):
         flags = _flags(deterministic, unordered)
         if _is_torch_cuda(rows):
             n = rows.numel()
-            for name, t in (("coef", coef), ("x", x)):
-                if not _is_torch_cuda(t) or t.dtype != self.torch_dtype or not t.is_contiguous() \
-                        or t.device != rows.device:
-                    raise TypeError(f"{name}: expected a contiguous {self.torch_dtype} CUDA tensor on rows' device")
+            _check_like("coef", coef, self.torch_dtype, rows)
+            _check_like("x", x, self.torch_dtype, rows)
             q = self._axpy_q(tuple(x.shape), tuple(coef.shape), n)
             self._check_dev(n, rows)
             rc = self.lib.glint_mat_push_rows_axpy_dev(self.handle, rows.data_ptr(), n, coef.data_ptr(),
@@ -605,19 +631,11 @@ class PartialMatrix(_Shard):
             if _is_torch_cuda(t) != dev:
                 raise TypeError(f"rows and {name}: mixing host arrays and device tensors")
         if dev:
-            import torch
             n = rows.numel()
-            if offsets.dtype != torch.int64 or not offsets.is_contiguous() or offsets.device != rows.device \
-                    or offsets.numel() < 1:
-                raise TypeError("offsets: expected a contiguous int64 CUDA tensor of g + 1 entries on rows' device")
-            g = offsets.numel() - 1
-            for name, t, want in (("values", values, g * self.cols), ("weights", weights, n)):
-                if t is None:
-                    continue
-                if t.dtype != self.torch_dtype or not t.is_contiguous() or t.device != rows.device:
-                    raise TypeError(f"{name}: expected a contiguous {self.torch_dtype} CUDA tensor on rows' device")
-                if t.numel() != want:
-                    raise ValueError(f"{name}: {t.numel()} elements, expected {want}")
+            g = _check_offsets_dev(offsets, rows)
+            _check_like("values", values, self.torch_dtype, rows, g * self.cols)
+            if weights is not None:
+                _check_like("weights", weights, self.torch_dtype, rows, n)
             self._check_dev(n, rows)
             rc = self.lib.glint_mat_push_rows_grouped_dev(
                 self.handle, rows.data_ptr(), n, offsets.data_ptr(), g, values.data_ptr() if g else None,
@@ -625,10 +643,7 @@ class PartialMatrix(_Shard):
             self._dev_done(rc, rows, sync)
             return True
         r = _host(rows, np.int64).reshape(-1)
-        o = _host(offsets, np.int64).reshape(-1)
-        if o.size < 1:
-            raise ValueError("offsets needs g + 1 entries")
-        g = o.size - 1
+        o, g = _host_offsets(offsets)
         v = _host(values, self.np_dtype).reshape(-1)
         if v.size != g * self.cols:
             raise ValueError(f"values: {v.size} elements, expected {g} groups x {self.cols} columns")
@@ -653,26 +668,29 @@ class PartialMatrix(_Shard):
         are no order flags: the call is deterministic. Errors as ``updateRows``: host arrays reject a
         message with a row outside the partition before either shard changes; device tensors skip such a
         row and raise at the weights shard's sync."""
-        if not isinstance(state, PartialMatrix):
-            raise TypeError("state: expected a PartialMatrix")
+        return self._step_push("updateRowsAdagrad", "glint_mat_push_rows_adagrad", state, PartialMatrix, rows, grads,
+                               (float(lr), float(eps)), sync)
+
+    def _step_push(self, name: str, symbol: str, state, state_cls, rows, grads, scalars: tuple, sync: bool) -> bool:
+        """What the optimizer row pushes share (as step_push_host / step_push_dev do below the C ABI): method
+        ``name`` calls ``symbol`` -- ``symbol + "_dev"`` for device tensors -- with the weights shard, a
+        ``state`` shard of class ``state_cls``, the rows, their gradient rows and the step's ``scalars``."""
+        if not isinstance(state, state_cls):
+            raise TypeError(f"state: expected a {state_cls.__name__}")
         if np.dtype(self.np_dtype).kind != "f":
-            raise TypeError(f"updateRowsAdagrad needs a Float or Double shard, not {np.dtype(self.np_dtype).name}")
+            raise TypeError(f"{name} needs a Float or Double shard, not {np.dtype(self.np_dtype).name}")
         if _is_torch_cuda(rows) != _is_torch_cuda(grads):
             raise TypeError("rows and grads: mixing host arrays and device tensors")
         if _is_torch_cuda(rows):
             n = rows.numel()
             self._check_dev(n, rows, values=grads, value_elems=n * self.cols)
-            rc = self.lib.glint_mat_push_rows_adagrad_dev(self.handle, state.handle, rows.data_ptr(),
-                                                          grads.data_ptr(), n, float(lr), float(eps),
-                                                          self._stream_of(rows))
+            rc = getattr(self.lib, symbol + "_dev")(self.handle, state.handle, rows.data_ptr(), grads.data_ptr(), n,
+                                                    *scalars, self._stream_of(rows))
             self._dev_done(rc, rows, sync)
             return True
-        r = _host(rows, np.int64).reshape(-1)
-        g = _host(grads, self.np_dtype).reshape(-1)
-        if g.size != r.size * self.cols:
-            raise ValueError(f"grads: {g.size} elements, expected {r.size} rows x {self.cols} columns")
-        check(self.lib.glint_mat_push_rows_adagrad(self.handle, state.handle, r.ctypes.data, g.ctypes.data, r.size,
-                                                   float(lr), float(eps)), self.handle)
+        r, g = self._host_rows(rows, grads, self.np_dtype, "grads")
+        check(getattr(self.lib, symbol)(self.handle, state.handle, r.ctypes.data, g.ctypes.data, r.size, *scalars),
+              self.handle)
         return True
 
     def updateRowsAdagradRowwise(self, state: "PartialVector", rows, grads, lr: float, eps: float = 1e-10,
@@ -686,28 +704,8 @@ class PartialMatrix(_Shard):
         operation rounded on its own in the shard's type (include/glint_gpu.h has the contract):
         duplicates are coalesced, then one step is taken. There are no order flags: the call is
         deterministic. Errors as ``updateRowsAdagrad``."""
-        if not isinstance(state, PartialVector):
-            raise TypeError("state: expected a PartialVector")
-        if np.dtype(self.np_dtype).kind != "f":
-            raise TypeError("updateRowsAdagradRowwise needs a Float or Double shard, not "
-                            f"{np.dtype(self.np_dtype).name}")
-        if _is_torch_cuda(rows) != _is_torch_cuda(grads):
-            raise TypeError("rows and grads: mixing host arrays and device tensors")
-        if _is_torch_cuda(rows):
-            n = rows.numel()
-            self._check_dev(n, rows, values=grads, value_elems=n * self.cols)
-            rc = self.lib.glint_mat_push_rows_adagrad_rowwise_dev(self.handle, state.handle, rows.data_ptr(),
-                                                                  grads.data_ptr(), n, float(lr), float(eps),
-                                                                  self._stream_of(rows))
-            self._dev_done(rc, rows, sync)
-            return True
-        r = _host(rows, np.int64).reshape(-1)
-        g = _host(grads, self.np_dtype).reshape(-1)
-        if g.size != r.size * self.cols:
-            raise ValueError(f"grads: {g.size} elements, expected {r.size} rows x {self.cols} columns")
-        check(self.lib.glint_mat_push_rows_adagrad_rowwise(self.handle, state.handle, r.ctypes.data, g.ctypes.data,
-                                                           r.size, float(lr), float(eps)), self.handle)
-        return True
+        return self._step_push("updateRowsAdagradRowwise", "glint_mat_push_rows_adagrad_rowwise", state, PartialVector,
+                               rows, grads, (float(lr), float(eps)), sync)
 
     def updateRowsAdam(self, state: "PartialMatrix", rows, grads, lr: float, step: int, beta1: float = 0.9,
                        beta2: float = 0.999, eps: float = 1e-8, sync: bool = True) -> bool:
@@ -722,27 +720,9 @@ class PartialMatrix(_Shard):
         duplicates are coalesced, then one step is taken; ``step`` is the caller's global count from 1,
         and a row that is not named keeps its moments. There are no order flags: the call is
         deterministic. Errors as ``updateRowsAdagrad``."""
-        if not isinstance(state, PartialMatrix):
-            raise TypeError("state: expected a PartialMatrix")
-        if np.dtype(self.np_dtype).kind != "f":
-            raise TypeError(f"updateRowsAdam needs a Float or Double shard, not {np.dtype(self.np_dtype).name}")
-        if _is_torch_cuda(rows) != _is_torch_cuda(grads):
-            raise TypeError("rows and grads: mixing host arrays and device tensors")
         scalars = (float(lr), float(beta1), float(beta2), float(eps), int(step))
-        if _is_torch_cuda(rows):
-            n = rows.numel()
-            self._check_dev(n, rows, values=grads, value_elems=n * self.cols)
-            rc = self.lib.glint_mat_push_rows_adam_dev(self.handle, state.handle, rows.data_ptr(), grads.data_ptr(),
-                                                       n, *scalars, self._stream_of(rows))
-            self._dev_done(rc, rows, sync)
-            return True
-        r = _host(rows, np.int64).reshape(-1)
-        g = _host(grads, self.np_dtype).reshape(-1)
-        if g.size != r.size * self.cols:
-            raise ValueError(f"grads: {g.size} elements, expected {r.size} rows x {self.cols} columns")
-        check(self.lib.glint_mat_push_rows_adam(self.handle, state.handle, r.ctypes.data, g.ctypes.data, r.size,
-                                                *scalars), self.handle)
-        return True
+        return self._step_push("updateRowsAdam", "glint_mat_push_rows_adam", state, PartialMatrix, rows, grads,
+                               scalars, sync)
 
     def updateRowsFtrl(self, state: "PartialMatrix", rows, grads, alpha: float, beta: float = 1.0, l1: float = 0.0,
                        l2: float = 0.0, sync: bool = True) -> bool:
@@ -757,27 +737,9 @@ class PartialMatrix(_Shard):
         step overwrites whatever the weights shard held. Duplicates are coalesced, then one step is
         taken; a row that is not named is not touched. There are no order flags: the call is
         deterministic. Errors as ``updateRowsAdagrad``."""
-        if not isinstance(state, PartialMatrix):
-            raise TypeError("state: expected a PartialMatrix")
-        if np.dtype(self.np_dtype).kind != "f":
-            raise TypeError(f"updateRowsFtrl needs a Float or Double shard, not {np.dtype(self.np_dtype).name}")
-        if _is_torch_cuda(rows) != _is_torch_cuda(grads):
-            raise TypeError("rows and grads: mixing host arrays and device tensors")
         scalars = (float(alpha), float(beta), float(l1), float(l2))
-        if _is_torch_cuda(rows):
-            n = rows.numel()
-            self._check_dev(n, rows, values=grads, value_elems=n * self.cols)
-            rc = self.lib.glint_mat_push_rows_ftrl_dev(self.handle, state.handle, rows.data_ptr(), grads.data_ptr(),
-                                                       n, *scalars, self._stream_of(rows))
-            self._dev_done(rc, rows, sync)
-            return True
-        r = _host(rows, np.int64).reshape(-1)
-        g = _host(grads, self.np_dtype).reshape(-1)
-        if g.size != r.size * self.cols:
-            raise ValueError(f"grads: {g.size} elements, expected {r.size} rows x {self.cols} columns")
-        check(self.lib.glint_mat_push_rows_ftrl(self.handle, state.handle, r.ctypes.data, g.ctypes.data, r.size,
-                                                *scalars), self.handle)
-        return True
+        return self._step_push("updateRowsFtrl", "glint_mat_push_rows_ftrl", state, PartialMatrix, rows, grads,
+                               scalars, sync)
 
     def _axpy_q(self, xshape, cshape, n: int) -> int:
         """q of updateRowsAxpy for vectors of shape ``xshape`` and coefficients of shape ``cshape``."""
@@ -849,12 +811,7 @@ class PartialMatrix(_Shard):
             self._dev_done(rc, rows, sync)
             return out
         r = _host(rows, np.int64).reshape(-1)
-        shape = (r.size, self.cols)
-        if out is None:
-            out = np.empty(shape, dtype=np_wire)
-        elif not isinstance(out, np.ndarray) or out.dtype != np_wire or out.shape != shape \
-                or not out.flags.c_contiguous or not out.flags.writeable:
-            raise ValueError(f"out must be a writable C-contiguous {np.dtype(np_wire).name} array of shape {shape}")
+        out = self._host_out(out, (r.size, self.cols), np_wire)
         check(self.lib.glint_mat_pull_rows_as(self.handle, r.ctypes.data, out.ctypes.data, r.size, code), self.handle)
         return out
 
@@ -936,14 +893,9 @@ class PartialMatrix(_Shard):
         if _is_torch_cuda(rows):
             import torch
             n = rows.numel()
-            if not _is_torch_cuda(offsets) or offsets.dtype != torch.int64 or not offsets.is_contiguous() \
-                    or offsets.device != rows.device or offsets.numel() < 1:
-                raise TypeError("offsets: expected a contiguous int64 CUDA tensor of g + 1 entries on rows' device")
-            g = offsets.numel() - 1
+            g = _check_offsets_dev(offsets, rows)
             if weights is not None:
-                if not _is_torch_cuda(weights) or weights.dtype != self.torch_dtype or not weights.is_contiguous() \
-                        or weights.device != rows.device:
-                    raise TypeError(f"weights: expected a contiguous {self.torch_dtype} CUDA tensor on rows' device")
+                _check_like("weights", weights, self.torch_dtype, rows)
                 if weights.numel() != n:
                     raise ValueError(f"weights: {weights.numel()} values, expected {n}")
             if out is None:
@@ -961,9 +913,7 @@ class PartialMatrix(_Shard):
         if _is_torch_cuda(offsets) or _is_torch_cuda(weights):
             raise TypeError("rows, offsets and weights: mixing host arrays and device tensors")
         r = _host(rows, np.int64).reshape(-1)
-        o = _host(offsets, np.int64).reshape(-1)
-        if o.size < 1:
-            raise ValueError("offsets needs g + 1 entries")
+        o, g = _host_offsets(offsets)
         w = None
         if weights is not None:
             if isinstance(weights, np.ndarray) and weights.dtype != np.dtype(self.np_dtype):
@@ -971,12 +921,12 @@ class PartialMatrix(_Shard):
             w = _host(weights, self.np_dtype).reshape(-1)
             if w.size != r.size:
                 raise ValueError(f"weights: {w.size} values, expected {r.size}")
-        res = self._host_out(out, (o.size - 1, self.cols))
+        res = self._host_out(out, (g, self.cols))
         if w is None:
-            check(self.lib.glint_mat_pull_rows_sum(self.handle, r.ctypes.data, r.size, o.ctypes.data, o.size - 1,
+            check(self.lib.glint_mat_pull_rows_sum(self.handle, r.ctypes.data, r.size, o.ctypes.data, g,
                                                    res.ctypes.data), self.handle)
         else:
-            check(self.lib.glint_mat_pull_rows_wsum(self.handle, r.ctypes.data, r.size, o.ctypes.data, o.size - 1,
+            check(self.lib.glint_mat_pull_rows_wsum(self.handle, r.ctypes.data, r.size, o.ctypes.data, g,
                                                     w.ctypes.data if r.size else None, res.ctypes.data), self.handle)
         return res
 
@@ -995,13 +945,8 @@ class PartialMatrix(_Shard):
         if _is_torch_cuda(rows):
             import torch
             n = rows.numel()
-            if not _is_torch_cuda(offsets) or offsets.dtype != torch.int64 or not offsets.is_contiguous() \
-                    or offsets.device != rows.device or offsets.numel() < 1:
-                raise TypeError("offsets: expected a contiguous int64 CUDA tensor of g + 1 entries on rows' device")
-            g = offsets.numel() - 1
-            if not _is_torch_cuda(x) or x.dtype != self.torch_dtype or not x.is_contiguous() \
-                    or x.device != rows.device:
-                raise TypeError(f"x: expected a contiguous {self.torch_dtype} CUDA tensor on rows' device")
+            g = _check_offsets_dev(offsets, rows)
+            _check_like("x", x, self.torch_dtype, rows)
             self._gdot_shape(tuple(x.shape), g)
             if out is None:
                 out = torch.empty((n,), dtype=self.torch_dtype, device=rows.device)
@@ -1014,10 +959,7 @@ class PartialMatrix(_Shard):
         if _is_torch_cuda(offsets) or _is_torch_cuda(x):
             raise TypeError("rows, offsets and x: mixing host arrays and device tensors")
         r = _host(rows, np.int64).reshape(-1)
-        o = _host(offsets, np.int64).reshape(-1)
-        if o.size < 1:
-            raise ValueError("offsets needs g + 1 entries")
-        g = o.size - 1
+        o, g = _host_offsets(offsets)
         if isinstance(x, np.ndarray) and x.dtype != np.dtype(self.np_dtype):
             raise TypeError(f"x: expected {np.dtype(self.np_dtype).name}, not {x.dtype.name}")
         xs = _host(x, self.np_dtype)
@@ -1050,9 +992,7 @@ class PartialMatrix(_Shard):
             n = rows.numel()
             q, shape = 1, (n,)
             if x is not None:
-                if not _is_torch_cuda(x) or x.dtype != self.torch_dtype or not x.is_contiguous() \
-                        or x.device != rows.device:
-                    raise TypeError(f"x: expected a contiguous {self.torch_dtype} CUDA tensor on rows' device")
+                _check_like("x", x, self.torch_dtype, rows)
                 q, shape = self._dot_shape(tuple(x.shape), n)
             if out is None:
                 out = torch.empty(shape, dtype=self.torch_dtype, device=rows.device)
@@ -1213,23 +1153,8 @@ class PartialMatrix(_Shard):
         raise ValueError(f"x: shape {tuple(xshape)}, expected ({self.cols},) or (q, {self.cols}) with "
                          f"1 <= q <= {N.GLINT_TOPK_MAX_QUERIES}")
 
-    def push_wire(self, payload: bytes, deterministic: bool = False) -> int:
-        buf = (C.c_uint8 * len(payload)).from_buffer_copy(payload)
-        mid = C.c_int32()
-        flags = N.GLINT_PUSH_DETERMINISTIC if deterministic else N.GLINT_PUSH_DEFAULT
-        check(self.lib.glint_push_wire(self.handle, buf, len(payload), C.byref(mid), flags), self.handle)
-        return mid.value
-
-    def pull_wire(self, payload: bytes) -> bytes:
-        return _pull_wire(self, payload)
-
     def to_numpy(self) -> np.ndarray:
-        p = self.partition
-        if isinstance(p, RangePartition):
-            rows = np.arange(p.start, p.start + self.size, dtype=np.int64)
-        else:
-            rows = np.arange(self.size, dtype=np.int64) * p.numberOfPartitions + p.index
-        return self.getRows(rows)
+        return self.getRows(self._keys())
 
 
 def _pull_wire(shard: _Shard, payload: bytes) -> bytes:
