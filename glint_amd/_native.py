@@ -127,6 +127,16 @@ SIGNATURES = {
     "glint_sampler_info": (_I, [_P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I)]),
     "glint_sampler_draw": (_I, [_P, C.c_uint64, C.c_uint64, _I64, _P, _I64, _P]),
     "glint_sampler_draw_dev": (_I, [_P, C.c_uint64, C.c_uint64, _I64, _P, _I64, _P, _P]),
+    "glint_keymap_create": (_I, [_I, _I64, _I64, _I64, C.POINTER(_P)]),
+    "glint_keymap_destroy": (_I, [_P]),
+    "glint_keymap_info": (_I, [_P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I)]),
+    "glint_keymap_insert": (_I, [_P, _P, _I64, _P, C.POINTER(_I64), C.POINTER(_I64)]),
+    "glint_keymap_insert_dev": (_I, [_P, _P, _I64, _P, _P]),
+    "glint_keymap_lookup": (_I, [_P, _P, _I64, _I64, _P, C.POINTER(_I64)]),
+    "glint_keymap_lookup_dev": (_I, [_P, _P, _I64, _I64, _P, _P]),
+    "glint_keymap_keys_of": (_I, [_P, _P, _I64, _P, C.POINTER(_I64)]),
+    "glint_keymap_keys_of_dev": (_I, [_P, _P, _I64, _P, _P]),
+    "glint_keymap_sync": (_I, [_P, _P, C.POINTER(_I64), C.POINTER(_I64)]),
     "glint_prof_enable": (_I, [_P, _I]),
     "glint_prof_read": (_I, [_P, _I, C.POINTER(C.c_double), C.POINTER(_I64)]),
     "glint_prof_read_launches": (_I, [_P, _I, C.POINTER(C.c_double), _I64, C.POINTER(_I64)]),

@@ -660,5 +660,16 @@ class Client:
             device = self.devices[0]
         return Sampler(weights, firstKey, device)
 
+    def keymap(self, capacity: int, firstRow: int = 0, device: Optional[int] = None, slots: Optional[int] = None):
+        """A device key map (glint_amd.keymap.KeyMap; an extension) from 64-bit feature ids to the rows
+        ``firstRow .. firstRow + capacity - 1`` of a matrix of any partitioning, on ``device`` or the client's
+        first device."""
+        from .keymap import KeyMap
+        if device is None:
+            if not self.devices:
+                raise ModelCreationException("Cannot create a key map without active parameter servers")
+            device = self.devices[0]
+        return KeyMap(capacity, firstRow, device, slots)
+
 
 __all__ = ["Client", "BigVector", "BigMatrix", "bucket", "RangePartitioner", "CyclicPartitioner"]

@@ -1666,7 +1666,7 @@ std::atomic<unsigned> g_env_gen{1};
 extern "C" {
 
 // 0.17.0: glint_mat_pull_rows_wsum / _dev (weighted row-sum pull), glint_mat_pull_rows_gdot / _dev (grouped row dot)
-int glint_version(void) { return 1700; }
+int glint_version(void) { return 1800; }
 
 int glint_wire_supported(int dtype, int wire) { return wire_supported(dtype, wire) ? 1 : 0; }
 

@@ -19,6 +19,16 @@ class ArrayIndexOutOfBoundsException(IndexOutOfBoundsException):
         self.record = record
 
 
+class KeyMapFullException(ArrayIndexOutOfBoundsException):
+    """An insert into a ``KeyMap`` named more new keys than the map has free rows (an extension). The map is
+    as it was before the call; ``free`` is the free row count, and no single record is to blame (``record``
+    stays -1)."""
+
+    def __init__(self, msg: str = "", free: int = -1):
+        super().__init__(msg, -1)
+        self.free = free
+
+
 class GlintDeviceError(RuntimeError):
     """HIP runtime failure (GLINT_EDEVICE), including 'no GPU present'."""
 

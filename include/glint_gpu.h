@@ -1122,6 +1122,70 @@ int glint_sampler_draw(glint_sampler_t sampler, uint64_t seed, uint64_t first, i
 int glint_sampler_draw_dev(glint_sampler_t sampler, uint64_t seed, uint64_t first, int64_t n,
                            const int64_t* exclude, int64_t per, int64_t* out, void* stream);
 
+/* ---- key map (device) ---------------------------------------------------------------------- *
+ * 64-bit feature ids to table rows on the device (an extension: the reference's keys are dense by
+ * construction): what an embedding-bag, two-tower, open-vocabulary skip-gram or hashed-feature FTRL step
+ * needs in front of the row calls, so that no id crosses the link and no host dictionary sits between "which
+ * rows?" and the row call. A key map is an insert-only open-addressing table on one device; it is not a
+ * shard, and one map serves a matrix of any partitioning (its rows are ordinary global row ids).
+ * Create: capacity >= 1 keys map to rows first_row .. first_row + capacity - 1, first_row >= 0 and first_row
+ * + capacity <= 2^62. `slots` is a power of two, capacity < slots <= 2^30, so an empty slot always ends a
+ * miss; slots == 0 asks for the default, the least power of two >= 2 * capacity. Anything else is
+ * GLINT_EINVAL (before the device is touched) and no handle is produced (*out = NULL). The map starts empty
+ * and the create ends synchronised. Memory: 16 slots + 8 capacity bytes, and the scratch below.
+ * Insert: out[i] = the row of keys[i]. A key already in the map answers its row. The distinct new keys of
+ * the call are numbered by the position of their first occurrence in `keys`: the j-th of them (from 0) gets
+ * row first_row + size + j, size being the number of keys in the map before the call; later occurrences in
+ * the call answer the same row, and afterwards size has grown by the number of distinct new keys. Rows are
+ * therefore a function of the sequence of insert calls and their keys only: never of `slots`, the hash, the
+ * launch shape, the host or device form, or of how one call's keys are split over consecutive calls.
+ * Lookup: out[i] = the row of keys[i], or `missing` for a key not in the map; the map is only read.
+ * Keys-of: out[i] = the key that owns rows[i], for rows in [first_row, first_row + size); any other row is
+ * refused (its out[i] is INT64_MIN).
+ * The reserved key: INT64_MIN marks an empty slot and is no key. An insert or lookup that names it is refused
+ * with the lowest index at which it appears; a refused insert leaves the map exactly as it was, its out[i]
+ * the row of a key already present and -1 for every other record; a refused lookup answers `missing` there.
+ * Overflow: an insert whose distinct new keys exceed the free rows capacity - size is refused in the same
+ * way -- the map, its probe chains included, exactly as before the call (every slot the call claimed was
+ * empty before and is emptied again), out[i] the row of a key already present and -1 elsewhere -- and
+ * reports the free row count, not a record.
+ * Host forms (glint_keymap_insert, _lookup, _keys_of: host pointers) stage 8 n bytes, run on a stream of the
+ * map's own after the work enqueued on the last device-form call's stream, copy 8 n bytes back and end
+ * synchronised. A refused call returns GLINT_EOUTOFRANGE with *bad = the refused index, or *bad = -1 and
+ * *free_rows = the free row count for an overflow (either pointer may be NULL; -1 is stored otherwise).
+ * Device forms (_insert_dev, _lookup_dev, _keys_of_dev: device pointers of the map's device) only launch on
+ * `stream`: nothing on the host waits, size lives in device memory and the commit-or-roll-back decision is
+ * taken on the device. A refusal is latched in device memory and reported by the next glint_keymap_sync,
+ * which waits for `stream`, returns GLINT_EOUTOFRANGE with *bad = the lowest refused index among the calls
+ * since the last report, or *bad = -1 and *free_rows = the least free row count of an overflowed insert, and
+ * clears the latch -- as an unsynced push reports at glint_shard_sync.
+ * Ordering: the calls on one map are ordered by the caller -- one stream, or events between streams.
+ * Lookups and keys-of calls may overlap each other; nothing may overlap an insert.
+ * Every call: GLINT_EINVAL for a NULL map, n < 0, n >= 2^31, or a NULL array with n > 0. n == 0 returns
+ * GLINT_OK and touches nothing.
+ * Scratch: an insert uses 8 n bytes plus 4 bytes per 1024 records, from a grow-only buffer of the map's. The
+ * buffer grows -- one free and one allocation, which wait for the device -- only in a call longer than every
+ * call before it; a create allocates for calls of up to 2^17 records, so a caller who wants no such wait
+ * behind an unsynchronised chain issues its longest insert first. Host forms keep 16 n bytes of staging
+ * by the same rule.
+ * glint_keymap_info: any pointer may be NULL; a non-NULL `size` waits for the device's enqueued work.
+ * Kernel timing: a key map is not a shard and has no kernel id; time it with events on `stream`. */
+typedef struct glint_keymap* glint_keymap_t;
+int glint_keymap_create(int device, int64_t capacity, int64_t first_row, int64_t slots, glint_keymap_t* out);
+int glint_keymap_destroy(glint_keymap_t map);
+int glint_keymap_info(glint_keymap_t map, int64_t* capacity, int64_t* first_row, int64_t* slots, int64_t* size,
+                      int* device);
+int glint_keymap_insert(glint_keymap_t map, const int64_t* keys, int64_t n, int64_t* out, int64_t* bad,
+                        int64_t* free_rows);
+int glint_keymap_insert_dev(glint_keymap_t map, const int64_t* keys, int64_t n, int64_t* out, void* stream);
+int glint_keymap_lookup(glint_keymap_t map, const int64_t* keys, int64_t n, int64_t missing, int64_t* out,
+                        int64_t* bad);
+int glint_keymap_lookup_dev(glint_keymap_t map, const int64_t* keys, int64_t n, int64_t missing, int64_t* out,
+                            void* stream);
+int glint_keymap_keys_of(glint_keymap_t map, const int64_t* rows, int64_t n, int64_t* out, int64_t* bad);
+int glint_keymap_keys_of_dev(glint_keymap_t map, const int64_t* rows, int64_t n, int64_t* out, void* stream);
+int glint_keymap_sync(glint_keymap_t map, void* stream, int64_t* bad, int64_t* free_rows);
+
 /* ---- kernel timing ------------------------------------------------------------------------- *
  * With profiling on, every kernel launch of the shard is bracketed by HIP events recorded on the
  * stream it is launched on; glint_prof_read waits for them and returns the summed device time and
