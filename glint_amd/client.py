@@ -257,28 +257,39 @@ class BigMatrix(_InitMixin):
         Bytes sent to a partition with n_p of the records in g_p of the groups: ``8 n_p + 8 (g_p + 1) +
         g_p * cols * itemsize``, plus ``n_p * itemsize`` with ``weights`` -- against ``8 n_p + n_p * cols *
         itemsize`` for ``pushRows`` of the expanded rows."""
+        for _, sh, r, sub, v, w in self._sub_groups(rows, offsets, values, weights):
+            sh.updateRowsGrouped(r, sub, v, w, deterministic=deterministic)
+        return True
+
+    def _sub_groups(self, rows, offsets, values, weights, name: str = "values") -> list:
+        """What the grouped pushes send: ``offsets``, the shapes of the (g, cols) or flat value rows (called
+        ``name``) and of ``weights`` ((n,) or None) and -- by the partitioner -- every row are validated, the
+        records bucketed by partition as ``pushRows``, and each non-empty partition p gets ``(p, shard, its
+        rows, the offsets of its sub-groups, their value rows, its weights or None)`` in the caller's order:
+        only the groups that have a record in that partition, their value rows compacted."""
         rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
         offsets, g = self._offsets(rows, offsets)
         dtype = self.shards[0].np_dtype
         values = np.ascontiguousarray(values, dtype=dtype)
         if values.size != g * self.cols:
-            raise ValueError(f"values: {values.size} elements, expected {g} groups x {self.cols} columns")
+            raise ValueError(f"{name}: {values.size} elements, expected {g} groups x {self.cols} columns")
         values = values.reshape(g, self.cols)
         if weights is not None:
             weights = np.ascontiguousarray(weights, dtype=dtype).reshape(-1)
             if weights.size != rows.size:
                 raise ValueError(f"weights: {weights.size} values, expected {rows.size}")
         group = np.repeat(np.arange(g, dtype=np.int64), np.diff(offsets))  # the group of every record
-        for _, sh, idx in _buckets(self, rows):  # idx in the caller's order, so its groups are non-decreasing
+        out = []
+        for p, sh, idx in _buckets(self, rows):  # idx in the caller's order, so its groups are non-decreasing
             counts = np.bincount(group[idx], minlength=g)
             has = np.flatnonzero(counts)  # the groups with a record here, ascending
             sub = np.zeros(has.size + 1, dtype=np.int64)
             np.cumsum(counts[has], out=sub[1:])
-            sh.updateRowsGrouped(rows[idx], sub, values[has], None if weights is None else weights[idx],
-                                 deterministic=deterministic)
-        return True
+            out.append((p, sh, rows[idx], sub, values[has], None if weights is None else weights[idx]))
+        return out
 
-    def pushAdagrad(self, state: "BigMatrix", rows, grads, lr: float, eps: float = 1e-10) -> bool:
+    def pushAdagrad(self, state: "BigMatrix", rows, grads, lr: float, eps: float = 1e-10, *, offsets=None,
+                    weights=None) -> bool:
         """Adagrad row push (an extension): this matrix holds the weights and ``state`` -- a BigMatrix
         with the same partitioner, rows, cols and dtype -- the accumulated squared gradients. ``grads`` is
         (n, cols) or flat. Per distinct row: its gradient rows are summed in the caller's order, then
@@ -286,16 +297,28 @@ class BigMatrix(_InitMixin):
         row (PartialMatrix.updateRowsAdagrad). Bucketed by partition as ``pushRows``; one
         PartialMatrix.updateRowsAdagrad per non-empty partition, with its rows and gradient rows in the
         caller's order and that partition's state shard. A row lives in one partition, so the bits are the
-        shard's."""
+        shard's.
+
+        With ``offsets`` (keyword only; g + 1 entries as ``pushGroups`` takes them) this is the bag backward
+        fused with the step: ``grads`` is (g, cols) or flat, one value row per group, and record i's gradient
+        row is ``grads[group of i]`` -- times ``weights[i]`` when ``weights`` (n,) is given -- without those n
+        rows being built or sent: each non-empty partition gets the sub-groups of its own rows, as
+        ``pushGroups`` sends them, and the bits are those of the push of the expanded rows. ``weights``
+        without ``offsets`` raises ValueError."""
         return self._push_step(state, BigMatrix, 1, "state: expected a matrix with this one's partitioner, rows, "
                                "cols and dtype", rows, grads,
-                               lambda sh, st, r, g: sh.updateRowsAdagrad(st, r, g, lr, eps))
+                               lambda sh, st, r, g, **kw: sh.updateRowsAdagrad(st, r, g, lr, eps, **kw),
+                               offsets, weights)
 
-    def _push_step(self, state, kind, state_cols_factor: int, message: str, rows, grads, call) -> bool:
+    def _push_step(self, state, kind, state_cols_factor: int, message: str, rows, grads, call, offsets=None,
+                   weights=None) -> bool:
         """What the optimizer row pushes share: ``state`` is a model of class ``kind`` laid out as this one --
         a BigVector of ``rows`` keys, or a BigMatrix of ``rows`` rows and ``state_cols_factor * cols`` columns,
         else ValueError(``message``) -- and each non-empty partition gets one ``call(shard, its state shard,
-        its rows, their gradient rows)``, in the caller's order."""
+        its rows, their gradient rows)``, in the caller's order. With ``offsets`` it is the grouped form:
+        ``grads`` holds one value row per group, and each non-empty partition gets its sub-groups as
+        ``pushGroups`` builds them, ``call(shard, its state shard, its rows, their value rows, offsets=its
+        sub-groups' offsets, weights=its weights)``. ``weights`` without ``offsets`` raises ValueError."""
         if not isinstance(state, kind):
             raise ValueError(f"state: expected a {kind.__name__}")
         dtype = self.shards[0].np_dtype
@@ -307,12 +330,19 @@ class BigMatrix(_InitMixin):
                 or np.dtype(state.shards[0].np_dtype) != np.dtype(dtype) \
                 or not _same_partitioner(state.partitioner, self.partitioner):
             raise ValueError(message)
+        if offsets is not None:
+            for p, sh, r, sub, v, w in self._sub_groups(rows, offsets, grads, weights, "grads"):
+                call(sh, state.shards[p], r, v, offsets=sub, weights=w)
+            return True
+        if weights is not None:
+            raise ValueError("weights: given without offsets (only the grouped form takes weights)")
         rows, grads = self._rows_values(rows, grads, dtype, "grads")
         for p, sh, idx in _buckets(self, rows):
             call(sh, state.shards[p], rows[idx], grads[idx])
         return True
 
-    def pushAdagradRowwise(self, state: "BigVector", rows, grads, lr: float, eps: float = 1e-10) -> bool:
+    def pushAdagradRowwise(self, state: "BigVector", rows, grads, lr: float, eps: float = 1e-10, *, offsets=None,
+                           weights=None) -> bool:
         """Row-wise Adagrad row push (an extension): this matrix holds the weights and ``state`` -- a
         BigVector with the same partitioner, ``size == rows`` and dtype -- one accumulator per row (zeros
         to start with), so the optimizer state is ``1 / cols`` of the table. ``grads`` is (n, cols) or
@@ -322,13 +352,15 @@ class BigMatrix(_InitMixin):
         row are validated before any shard is called. Bucketed by partition as ``pushRows``; one
         PartialMatrix.updateRowsAdagradRowwise per non-empty partition, with its rows and gradient rows in
         the caller's order and that partition's state shard. A row lives in one partition, so the bits are
-        the shard's."""
+        the shard's. ``offsets`` and ``weights`` (keyword only) make it the grouped form, as ``pushAdagrad``
+        describes it."""
         return self._push_step(state, BigVector, 0, "state: expected a vector with this matrix's partitioner, rows "
                                "and dtype", rows, grads,
-                               lambda sh, st, r, g: sh.updateRowsAdagradRowwise(st, r, g, lr, eps))
+                               lambda sh, st, r, g, **kw: sh.updateRowsAdagradRowwise(st, r, g, lr, eps, **kw),
+                               offsets, weights)
 
     def pushAdam(self, state: "BigMatrix", rows, grads, lr: float, step: int, beta1: float = 0.9,
-                 beta2: float = 0.999, eps: float = 1e-8) -> bool:
+                 beta2: float = 0.999, eps: float = 1e-8, *, offsets=None, weights=None) -> bool:
         """Adam row push (an extension): this matrix holds the weights and ``state`` -- a BigMatrix with
         the same partitioner, rows and dtype and ``2 * cols`` columns -- both moments of every row, ``m``
         in columns ``[0, cols)`` and ``v`` in ``[cols, 2 * cols)`` (zeros to start with). ``grads`` is
@@ -338,12 +370,14 @@ class BigMatrix(_InitMixin):
         and -- by the partitioner -- every row are validated before any shard is called. Bucketed by
         partition as ``pushRows``; one PartialMatrix.updateRowsAdam per non-empty partition, with its rows
         and gradient rows in the caller's order and that partition's state shard. A row lives in one
-        partition, so the bits are the shard's."""
+        partition, so the bits are the shard's. ``offsets`` and ``weights`` (keyword only) make it the grouped
+        form, as ``pushAdagrad`` describes it."""
         return self._push_step(state, BigMatrix, 2, _TWICE_COLS, rows, grads,
-                               lambda sh, st, r, g: sh.updateRowsAdam(st, r, g, lr, step, beta1, beta2, eps))
+                               lambda sh, st, r, g, **kw: sh.updateRowsAdam(st, r, g, lr, step, beta1, beta2, eps,
+                                                                            **kw), offsets, weights)
 
     def pushFtrl(self, state: "BigMatrix", rows, grads, alpha: float, beta: float = 1.0, l1: float = 0.0,
-                 l2: float = 0.0) -> bool:
+                 l2: float = 0.0, *, offsets=None, weights=None) -> bool:
         """FTRL-proximal row push (an extension): this matrix holds the weights and ``state`` -- a
         BigMatrix with the same partitioner, rows and dtype and ``2 * cols`` columns -- ``z`` in columns
         ``[0, cols)`` and ``n`` in ``[cols, 2 * cols)`` of every row (zeros to start with, beside zeroed
@@ -354,9 +388,11 @@ class BigMatrix(_InitMixin):
         partitioner -- every row are validated before any shard is called. Bucketed by partition as
         ``pushRows``; one PartialMatrix.updateRowsFtrl per non-empty partition, with its rows and gradient
         rows in the caller's order and that partition's state shard. A row lives in one partition, so the
-        bits are the shard's."""
+        bits are the shard's. ``offsets`` and ``weights`` (keyword only) make it the grouped form, as ``pushAdagrad``
+        describes it."""
         return self._push_step(state, BigMatrix, 2, _TWICE_COLS, rows, grads,
-                               lambda sh, st, r, g: sh.updateRowsFtrl(st, r, g, alpha, beta, l1, l2))
+                               lambda sh, st, r, g, **kw: sh.updateRowsFtrl(st, r, g, alpha, beta, l1, l2, **kw),
+                               offsets, weights)
 
     def pull(self, rows, cols=None) -> np.ndarray:
         """pull(rows, cols): elements (AsyncBigMatrix.scala:96-130); pull(rows): whole rows as an

@@ -1391,6 +1391,16 @@ inline int push_grouped_args(const glint_shard* s, const void* rows, int64_t n, 
   return GLINT_OK;
 }
 
+// What the grouped optimizer row pushes add to their optimizer's own argument check, whose result is step_rc:
+// that check is made with step_grads(vals, grp_ptr, g) where grads stood -- vals, required only when there
+// are groups -- and then push_grouped_args' 31-bit group count and grp_ptr, which always has g + 1 entries.
+inline const void* step_grads(const void* vals, const void* grp_ptr, int64_t g) { return g > 0 ? vals : grp_ptr; }
+inline int push_step_grouped_args(int step_rc, const void* grp_ptr, int64_t g) {
+  if (step_rc) return step_rc;
+  if (!grp_ptr || g < 0 || g >= ((i64)1 << 31)) return GLINT_EINVAL;
+  return GLINT_OK;
+}
+
 // The locks of a call on shards a and b, which may be one: the one lock once, else both in lock_order
 // (glint_vec_push_dev_shards' rule). The lock taken first is a ShardLock, so a call on one shard is
 // accounted as under a ShardLock.
@@ -1606,6 +1616,24 @@ int step_push_dev(glint_shard* w, glint_shard* s, int args_rc, const int64_t* ro
   });
 }
 
+// A grouped optimizer row push: its push_rows_*_grouped<V> (glint_host.h), which all take the two shards,
+// rows, n, grp_ptr, g, vals, coef, the call's scalars S and the stream.
+template <typename... S>
+using GroupStepPush = int (*)(glint_shard*, glint_shard*, const i64*, i64, const i64*, i64, const void*, const void*,
+                              S..., hipStream_t);
+
+// The device-resident entry of a grouped optimizer row push whose argument check gave args_rc (step_push_dev's
+// frame): pf for Float weights, pd for Double, with the scalars k. grp_ptr is clamped by the kernel.
+template <typename... S>
+int group_step_push_dev(glint_shard* w, glint_shard* s, int args_rc, const int64_t* rows, int64_t n,
+                        const int64_t* grp_ptr, int64_t g, const void* vals, const void* coef, void* stream,
+                        GroupStepPush<S...> pf, GroupStepPush<S...> pd, S... k) {
+  if (args_rc == GLINT_OK && n == 0) return GLINT_OK;
+  return dev_call2(w, s, args_rc, stream, [&](hipStream_t st) -> int {
+    return (w->dtype == GLINT_F64 ? pd : pf)(w, s, (const i64*)rows, n, (const i64*)grp_ptr, g, vals, coef, k..., st);
+  });
+}
+
 // What a host-pointer call does first, under the shard's lock: a slab with views is refused, the open
 // ring batch is launched and the shard's stream is ordered after the last device-resident call's.
 enum class HostEntry { Order, FlushOrder, OrderFlush };  // (Order: the call may append to the open batch)
@@ -1666,7 +1694,7 @@ std::atomic<unsigned> g_env_gen{1};
 extern "C" {
 
 // 0.17.0: glint_mat_pull_rows_wsum / _dev (weighted row-sum pull), glint_mat_pull_rows_gdot / _dev (grouped row dot)
-int glint_version(void) { return 1800; }
+int glint_version(void) { return 1900; }
 
 int glint_wire_supported(int dtype, int wire) { return wire_supported(dtype, wire) ? 1 : 0; }
 
@@ -2150,6 +2178,44 @@ int glint_mat_push_rows_ftrl_dev(glint_shard_t weights, glint_shard_t state, con
                                  int64_t n, double alpha, double beta, double l1, double l2, void* stream) {
   return step_push_dev(weights, state, push_ftrl_args(weights, state, rows, grads, n, alpha, beta, l1, l2), rows, grads,
                        n, stream, push_rows_ftrl<float>, push_rows_ftrl<double>, alpha, beta, l1, l2);
+}
+
+int glint_mat_push_rows_adagrad_grouped_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows, int64_t n,
+                                            const int64_t* grp_ptr, int64_t g, const void* vals, const void* coef,
+                                            double lr, double eps, void* stream) {
+  const int step_rc = push_adagrad_args(weights, state, rows, step_grads(vals, grp_ptr, g), n, lr, eps);
+  return group_step_push_dev(weights, state, push_step_grouped_args(step_rc, grp_ptr, g), rows, n, grp_ptr, g, vals,
+                             coef, stream, push_rows_adagrad_grouped<float>, push_rows_adagrad_grouped<double>, lr,
+                             eps);
+}
+
+int glint_mat_push_rows_adagrad_rowwise_grouped_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows,
+                                                    int64_t n, const int64_t* grp_ptr, int64_t g, const void* vals,
+                                                    const void* coef, double lr, double eps, void* stream) {
+  const int step_rc = push_adagrad_rowwise_args(weights, state, rows, step_grads(vals, grp_ptr, g), n, lr, eps);
+  return group_step_push_dev(weights, state, push_step_grouped_args(step_rc, grp_ptr, g), rows, n, grp_ptr, g, vals,
+                             coef, stream, push_rows_adagrad_rowwise_grouped<float>,
+                             push_rows_adagrad_rowwise_grouped<double>, lr, eps);
+}
+
+int glint_mat_push_rows_adam_grouped_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows, int64_t n,
+                                         const int64_t* grp_ptr, int64_t g, const void* vals, const void* coef,
+                                         double lr, double beta1, double beta2, double eps, int64_t step,
+                                         void* stream) {
+  const int step_rc =
+      push_adam_args(weights, state, rows, step_grads(vals, grp_ptr, g), n, lr, beta1, beta2, eps, step);
+  return group_step_push_dev(weights, state, push_step_grouped_args(step_rc, grp_ptr, g), rows, n, grp_ptr, g, vals,
+                             coef, stream, push_rows_adam_grouped<float>, push_rows_adam_grouped<double>, lr, beta1,
+                             beta2, eps, (i64)step);
+}
+
+int glint_mat_push_rows_ftrl_grouped_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows, int64_t n,
+                                         const int64_t* grp_ptr, int64_t g, const void* vals, const void* coef,
+                                         double alpha, double beta, double l1, double l2, void* stream) {
+  const int step_rc = push_ftrl_args(weights, state, rows, step_grads(vals, grp_ptr, g), n, alpha, beta, l1, l2);
+  return group_step_push_dev(weights, state, push_step_grouped_args(step_rc, grp_ptr, g), rows, n, grp_ptr, g, vals,
+                             coef, stream, push_rows_ftrl_grouped<float>, push_rows_ftrl_grouped<double>, alpha, beta,
+                             l1, l2);
 }
 
 int glint_mat_pull_pairs_dot_dev(glint_shard_t a, glint_shard_t b, const int64_t* rows_a, const int64_t* rows_b,
@@ -2946,6 +3012,32 @@ int step_push_host(glint_shard* w, glint_shard* s, int args_rc, const int64_t* r
                    });
 }
 
+// The host-pointer entry of a grouped optimizer row push (glint_mat_push_rows_adagrad_grouped, _adam_grouped,
+// _adagrad_rowwise_grouped, _ftrl_grouped) whose argument check gave args_rc: grp_ptr is checked, then, under
+// both shards' locks, every row against the weights shard before anything is staged (a rejected message
+// changes neither shard); rows, grp_ptr, coef (when given) and vals are staged in one block -- n * 8 +
+// (g + 1) * 8 + n + g * cols values, never n * cols; every section starts 256-B aligned, so vals takes the
+// 16-B path when cols allow -- and the push runs on the weights shard's stream as step_push_host's does. The
+// call ends synchronised. pf, pd and k as group_step_push_dev's.
+template <typename... S>
+int group_step_push_host(glint_shard* w, glint_shard* s, int args_rc, const int64_t* rows, int64_t n,
+                         const int64_t* grp_ptr, int64_t g, const void* vals, const void* coef,
+                         GroupStepPush<S...> pf, GroupStepPush<S...> pd, S... k) {
+  if (args_rc) return args_rc;
+  if (!grp_ptr_ok(grp_ptr, g, n)) return GLINT_EINVAL;
+  if (n == 0) return GLINT_OK;
+  return host_call(w, s, {rows, nullptr, n}, false,
+                   {{rows, (size_t)n * 8},
+                    {grp_ptr, (size_t)(g + 1) * 8},
+                    {coef, coef ? (size_t)n * w->vsize : 0},
+                    {vals, (size_t)g * (size_t)w->part.cols * w->vsize}},
+                   0, [&](const Staged& st, hipStream_t stream, HostBack*) -> int {
+                     return (w->dtype == GLINT_F64 ? pd : pf)(w, s, (const i64*)st.p[0], n, (const i64*)st.p[1], g,
+                                                              (const void*)st.p[3],
+                                                              coef ? (const void*)st.p[2] : nullptr, k..., stream);
+                   });
+}
+
 int host_push(glint_shard* s, bool mat, const int64_t* keys, const int32_t* cols, const void* vals, int64_t n,
               int flags) {
   if (n < 0 || (n > 0 && (!keys || !vals || (mat && !cols)))) return GLINT_EINVAL;
@@ -3313,6 +3405,42 @@ int glint_mat_push_rows_ftrl(glint_shard_t weights, glint_shard_t state, const i
                              int64_t n, double alpha, double beta, double l1, double l2) {
   return step_push_host(weights, state, push_ftrl_args(weights, state, rows, grads, n, alpha, beta, l1, l2), rows,
                         grads, n, push_rows_ftrl<float>, push_rows_ftrl<double>, alpha, beta, l1, l2);
+}
+
+int glint_mat_push_rows_adagrad_grouped(glint_shard_t weights, glint_shard_t state, const int64_t* rows, int64_t n,
+                                        const int64_t* grp_ptr, int64_t g, const void* vals, const void* coef,
+                                        double lr, double eps) {
+  const int step_rc = push_adagrad_args(weights, state, rows, step_grads(vals, grp_ptr, g), n, lr, eps);
+  return group_step_push_host(weights, state, push_step_grouped_args(step_rc, grp_ptr, g), rows, n, grp_ptr, g, vals,
+                              coef, push_rows_adagrad_grouped<float>, push_rows_adagrad_grouped<double>, lr, eps);
+}
+
+int glint_mat_push_rows_adagrad_rowwise_grouped(glint_shard_t weights, glint_shard_t state, const int64_t* rows,
+                                                int64_t n, const int64_t* grp_ptr, int64_t g, const void* vals,
+                                                const void* coef, double lr, double eps) {
+  const int step_rc = push_adagrad_rowwise_args(weights, state, rows, step_grads(vals, grp_ptr, g), n, lr, eps);
+  return group_step_push_host(weights, state, push_step_grouped_args(step_rc, grp_ptr, g), rows, n, grp_ptr, g, vals,
+                              coef, push_rows_adagrad_rowwise_grouped<float>,
+                              push_rows_adagrad_rowwise_grouped<double>, lr, eps);
+}
+
+int glint_mat_push_rows_adam_grouped(glint_shard_t weights, glint_shard_t state, const int64_t* rows, int64_t n,
+                                     const int64_t* grp_ptr, int64_t g, const void* vals, const void* coef, double lr,
+                                     double beta1, double beta2, double eps, int64_t step) {
+  const int step_rc =
+      push_adam_args(weights, state, rows, step_grads(vals, grp_ptr, g), n, lr, beta1, beta2, eps, step);
+  return group_step_push_host(weights, state, push_step_grouped_args(step_rc, grp_ptr, g), rows, n, grp_ptr, g, vals,
+                              coef, push_rows_adam_grouped<float>, push_rows_adam_grouped<double>, lr, beta1, beta2,
+                              eps, (i64)step);
+}
+
+int glint_mat_push_rows_ftrl_grouped(glint_shard_t weights, glint_shard_t state, const int64_t* rows, int64_t n,
+                                     const int64_t* grp_ptr, int64_t g, const void* vals, const void* coef,
+                                     double alpha, double beta, double l1, double l2) {
+  const int step_rc = push_ftrl_args(weights, state, rows, step_grads(vals, grp_ptr, g), n, alpha, beta, l1, l2);
+  return group_step_push_host(weights, state, push_step_grouped_args(step_rc, grp_ptr, g), rows, n, grp_ptr, g, vals,
+                              coef, push_rows_ftrl_grouped<float>, push_rows_ftrl_grouped<double>, alpha, beta, l1,
+                              l2);
 }
 
 // glint_mat_pull_pairs_dot: every pair is checked, then the two row arrays are staged in one block, the

@@ -575,6 +575,29 @@ int push_pairs_axpy(glint_shard* dst, glint_shard* src, const i64* rows_dst, con
 template <typename V>
 int push_rows_grouped(glint_shard* s, const i64* rows, i64 n, const i64* grp_ptr, i64 g, const void* vals,
                       const void* coef, int flags, hipStream_t st);
+// grouped optimizer row pushes (glint_rowstep_group.hip), instantiated for float and double: the optimizer
+// push above of the same name without `_grouped`, of the n rows whose record i holds vals[k] (g x cols,
+// dense), k the group of record i under grp_ptr as push_rows_grouped reads it, times coef[i] when coef is
+// given (the product rounded before the add) -- bit for bit in both shards, those rows never built. A record
+// that no group covers contributes nothing, and a row none of whose records contributed is not stepped.
+// Rows outside the partition are skipped and recorded in err_of(weights). The front end's launches
+// (weights' scratch), one launch that writes every record's group id into weights->d_grp and one fold launch
+// on st, no host synchronisation; under both shards' locks.
+template <typename V>
+int push_rows_adagrad_grouped(glint_shard* weights, glint_shard* state, const i64* rows, i64 n, const i64* grp_ptr,
+                              i64 g, const void* vals, const void* coef, double lr, double eps, hipStream_t st);
+template <typename V>
+int push_rows_adagrad_rowwise_grouped(glint_shard* weights, glint_shard* state, const i64* rows, i64 n,
+                                      const i64* grp_ptr, i64 g, const void* vals, const void* coef, double lr,
+                                      double eps, hipStream_t st);
+template <typename V>
+int push_rows_adam_grouped(glint_shard* weights, glint_shard* state, const i64* rows, i64 n, const i64* grp_ptr, i64 g,
+                           const void* vals, const void* coef, double lr, double beta1, double beta2, double eps,
+                           i64 step, hipStream_t st);
+template <typename V>
+int push_rows_ftrl_grouped(glint_shard* weights, glint_shard* state, const i64* rows, i64 n, const i64* grp_ptr, i64 g,
+                           const void* vals, const void* coef, double alpha, double beta, double l1, double l2,
+                           hipStream_t st);
 // narrow-format row transport (glint_rowwire.hip), for the (dtype, wire) pairs glint_wire_plan.h lists (any
 // other pair: GLINT_EINVAL), device pointers. pull_rows_wire: out (n x cols values of the wire type, dense) =
 // the requested rows rounded to the wire type; a row outside the partition answers zero bits and is recorded

@@ -8,33 +8,11 @@
 //                      list order, then h' = h + G * G and w' = w - (lr * G) / (sqrt(h') + eps).
 // The step needs a row's whole sum, so no run is ever split and there is no atomic. Every operation is
 // rounded on its own in the shard's type (include/glint_gpu.h has the contract); nothing of it depends
-// on the alignment of grads, the slice path or the grid.
-#include "glint_rowstep.h"
+// on the alignment of grads, the slice path or the grid. The step policy, AdagradScalars, is in
+// glint_steps.h.
+#include "glint_steps.h"
 
 namespace glint {
-
-// The step policy of the sliced fold (glint_rowstep.h): one state part, h. lr and eps are rounded once to
-// V on the host.
-// The seven operations of the contract, each rounded on its own: hipcc would contract h + G * G into
-// v_fma_* by default (axpy_mul's rule, glint_rowaxpy.hip). u / d stays a division of the rounded lr * G
-// -- G * (lr / d) rounds differently. sqrt and / are the compiler's IEEE ones (step_sqrt's note).
-template <typename V>
-struct AdagradScalars {
-  static constexpr int kParts = 1;
-  V lr, eps;
-  __device__ __forceinline__ void step(V& w, V (&h)[1], V G) const {
-#pragma clang fp contract(off)
-    const V s = G * G;
-    const V h2 = h[0] + s;
-    const V r = step_sqrt(h2);
-    const V d = r + eps;
-    const V u = lr * G;
-    const V p = u / d;
-    const V w2 = w - p;
-    h[0] = h2;
-    w = w2;
-  }
-};
 
 // `h` has w's type, partition, cols and pitch.
 template <typename V>

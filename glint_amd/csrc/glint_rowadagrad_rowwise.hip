@@ -15,38 +15,10 @@
 // One wave per row, not per (row, column slice): the slices of a row would need ss from each other. Every
 // operation is rounded on its own in the shard's type (include/glint_gpu.h has the contract); nothing of it
 // depends on the alignment of grads or the grid. No atomics, no LDS.
-#include "glint_dot.h"  // dot_step, x_load: the row dot pull's arithmetic, word for word
-#include "glint_rowstep.h"
+#include "glint_dot.h"    // dot_step, x_load: the row dot pull's arithmetic, word for word
+#include "glint_steps.h"  // kRowwiseKeep, rowwise_scalars, rowwise_update: shared with the grouped form
 
 namespace glint {
-
-#ifndef GLINT_ROWWISE_KEEP_BUILD  // (a variant build for measurement sets 0: every row sums its run twice)
-#define GLINT_ROWWISE_KEEP_BUILD GLINT_ROWWISE_KEEP_STRIPS
-#endif
-constexpr int kRowwiseKeep = GLINT_ROWWISE_KEEP_BUILD;  // strips kept in registers between the two passes
-
-// The five row scalars of the contract, each rounded on its own; returns k and leaves h' in h. ss / C is
-// a division, not a product with a reciprocal, and k = lr / d is one division per row. sqrt and / are the
-// compiler's IEEE ones (step_sqrt's note, glint_rowstep.h).
-template <typename V>
-__device__ __forceinline__ V rowwise_scalars(V& h, V ss, V C, V lr, V eps) {
-#pragma clang fp contract(off)
-  const V s = ss / C;
-  const V h2 = h + s;
-  const V r = step_sqrt(h2);
-  const V d = r + eps;
-  const V k = lr / d;
-  h = h2;
-  return k;
-}
-
-// w' = w - (k * G), the product rounded before the subtraction: fma(-k, G, w) is not the contract's.
-template <typename V>
-__device__ __forceinline__ V rowwise_update(V w, V k, V G) {
-#pragma clang fp contract(off)
-  const V p = k * G;
-  return w - p;
-}
 
 // Persistent grid; one wave per item. A strip is 64 lanes x E columns, lane L owning columns
 // [(s * 64 + L) * E, +E) of strip s: E = 16 / sizeof(V) when VEC16 (cols * sizeof(V) a multiple of 16; the

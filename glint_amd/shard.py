@@ -625,40 +625,50 @@ class PartialMatrix(_Shard):
         and raise at the sync, and their ``offsets`` are clamped to [0, len(rows)] by the kernel (a record
         that no group covers is not applied)."""
         flags = _flags(deterministic, unordered)
+        dev, args, _keep = self._grouped_args(rows, offsets, values, weights)
+        if dev:
+            rc = self.lib.glint_mat_push_rows_grouped_dev(self.handle, *args, flags, self._stream_of(rows))
+            self._dev_done(rc, rows, sync)
+            return True
+        check(self.lib.glint_mat_push_rows_grouped(self.handle, *args, flags), self.handle)
+        return True
+
+    def _grouped_args(self, rows, offsets, values, weights, name: str = "values") -> tuple:
+        """What the grouped pushes validate before any call, and what they pass: ``rows``, ``offsets``, the
+        (g, cols) or flat value rows (called ``name``) and ``weights`` ((n,) or None) are all device tensors or
+        all host arrays, of the shard's type and the sizes ``offsets`` fixes. Returns (device?, the C arguments
+        (rows, n, grp_ptr, g, vals, coef), the host arrays those point into -- to be kept until the call is
+        over)."""
         dev = _is_torch_cuda(rows)
-        for name, t in (("offsets", offsets), ("values", values)) + ((("weights", weights),) if weights is not None
-                                                                     else ()):
+        for what, t in (("offsets", offsets), (name, values)) + ((("weights", weights),) if weights is not None
+                                                                 else ()):
             if _is_torch_cuda(t) != dev:
-                raise TypeError(f"rows and {name}: mixing host arrays and device tensors")
+                raise TypeError(f"rows and {what}: mixing host arrays and device tensors")
         if dev:
             n = rows.numel()
             g = _check_offsets_dev(offsets, rows)
-            _check_like("values", values, self.torch_dtype, rows, g * self.cols)
+            _check_like(name, values, self.torch_dtype, rows, g * self.cols)
             if weights is not None:
                 _check_like("weights", weights, self.torch_dtype, rows, n)
             self._check_dev(n, rows)
-            rc = self.lib.glint_mat_push_rows_grouped_dev(
-                self.handle, rows.data_ptr(), n, offsets.data_ptr(), g, values.data_ptr() if g else None,
-                weights.data_ptr() if weights is not None else None, flags, self._stream_of(rows))
-            self._dev_done(rc, rows, sync)
-            return True
+            return True, (rows.data_ptr(), n, offsets.data_ptr(), g, values.data_ptr() if g else None,
+                          weights.data_ptr() if weights is not None else None), None
         r = _host(rows, np.int64).reshape(-1)
         o, g = _host_offsets(offsets)
         v = _host(values, self.np_dtype).reshape(-1)
         if v.size != g * self.cols:
-            raise ValueError(f"values: {v.size} elements, expected {g} groups x {self.cols} columns")
+            raise ValueError(f"{name}: {v.size} elements, expected {g} groups x {self.cols} columns")
         w = None
         if weights is not None:
             w = _host(weights, self.np_dtype).reshape(-1)
             if w.size != r.size:
                 raise ValueError(f"weights: {w.size} values, expected {r.size}")
-        check(self.lib.glint_mat_push_rows_grouped(self.handle, r.ctypes.data, r.size, o.ctypes.data, g,
-                                                   v.ctypes.data if g else None,
-                                                   w.ctypes.data if w is not None else None, flags), self.handle)
-        return True
+        return False, (r.ctypes.data, r.size, o.ctypes.data, g, v.ctypes.data if g else None,
+                       w.ctypes.data if w is not None else None), (r, o, v, w)
 
     def updateRowsAdagrad(self, state: "PartialMatrix", rows, grads, lr: float, eps: float = 1e-10,
-                          sync: bool = True) -> bool:
+                          sync: bool = True, *, offsets=None,
+                          weights=None) -> bool:
         """Adagrad row push (an extension; glint_mat_push_rows_adagrad*): this shard holds the weights and
         ``state`` -- a PartialMatrix of the same type, device, partition and cols -- the accumulated
         squared gradients. ``grads`` is (n, cols) or flat, dense row-major. Per distinct row of ``rows``:
@@ -667,18 +677,41 @@ class PartialMatrix(_Shard):
         (include/glint_gpu.h has the contract): duplicates are coalesced, then one step is taken. There
         are no order flags: the call is deterministic. Errors as ``updateRows``: host arrays reject a
         message with a row outside the partition before either shard changes; device tensors skip such a
-        row and raise at the weights shard's sync."""
-        return self._step_push("updateRowsAdagrad", "glint_mat_push_rows_adagrad", state, PartialMatrix, rows, grads,
-                               (float(lr), float(eps)), sync)
+        row and raise at the weights shard's sync.
 
-    def _step_push(self, name: str, symbol: str, state, state_cls, rows, grads, scalars: tuple, sync: bool) -> bool:
+        With ``offsets`` (keyword only; g + 1 int64 entries as ``updateRowsGrouped`` takes them) this is the
+        bag backward fused with the step: ``grads`` is (g, cols) or flat, one value row per group, and record
+        i's gradient row is ``grads[group of i]`` -- times ``weights[i]`` when ``weights`` (n,) is given, the
+        product rounded before the add -- without those n rows ever being built or sent. The bits of both
+        shards are those of the call with the expanded rows. Device ``offsets`` are clamped to [0, len(rows)]
+        by the kernel; a record that no group covers contributes nothing, and a row none of whose records
+        contributed is not stepped. ``weights`` without ``offsets`` raises ValueError."""
+        return self._step_push("updateRowsAdagrad", "glint_mat_push_rows_adagrad", state, PartialMatrix, rows, grads,
+                               (float(lr), float(eps)), sync, offsets, weights)
+
+    def _step_push(self, name: str, symbol: str, state, state_cls, rows, grads, scalars: tuple, sync: bool,
+                   offsets=None, weights=None) -> bool:
         """What the optimizer row pushes share (as step_push_host / step_push_dev do below the C ABI): method
         ``name`` calls ``symbol`` -- ``symbol + "_dev"`` for device tensors -- with the weights shard, a
-        ``state`` shard of class ``state_cls``, the rows, their gradient rows and the step's ``scalars``."""
+        ``state`` shard of class ``state_cls``, the rows, their gradient rows and the step's ``scalars``. With
+        ``offsets`` it is the grouped form, ``symbol + "_grouped"``: ``grads`` holds one value row per group and
+        record i's gradient row is ``grads[group of i]``, times ``weights[i]`` when ``weights`` is given -- built
+        nowhere; the checks are ``updateRowsGrouped``'s."""
         if not isinstance(state, state_cls):
             raise TypeError(f"state: expected a {state_cls.__name__}")
         if np.dtype(self.np_dtype).kind != "f":
             raise TypeError(f"{name} needs a Float or Double shard, not {np.dtype(self.np_dtype).name}")
+        if offsets is not None:
+            dev, args, _keep = self._grouped_args(rows, offsets, grads, weights, "grads")
+            if dev:
+                rc = getattr(self.lib, symbol + "_grouped_dev")(self.handle, state.handle, *args, *scalars,
+                                                                self._stream_of(rows))
+                self._dev_done(rc, rows, sync)
+                return True
+            check(getattr(self.lib, symbol + "_grouped")(self.handle, state.handle, *args, *scalars), self.handle)
+            return True
+        if weights is not None:
+            raise ValueError("weights: given without offsets (only the grouped form takes weights)")
         if _is_torch_cuda(rows) != _is_torch_cuda(grads):
             raise TypeError("rows and grads: mixing host arrays and device tensors")
         if _is_torch_cuda(rows):
@@ -694,7 +727,8 @@ class PartialMatrix(_Shard):
         return True
 
     def updateRowsAdagradRowwise(self, state: "PartialVector", rows, grads, lr: float, eps: float = 1e-10,
-                                 sync: bool = True) -> bool:
+                                 sync: bool = True, *, offsets=None,
+                                 weights=None) -> bool:
         """Row-wise Adagrad row push (an extension; glint_mat_push_rows_adagrad_rowwise*): this shard holds
         the weights and ``state`` -- a PartialVector of the same type, device and partition -- one
         accumulator per row, so the optimizer state is ``1 / cols`` of the table; a zeroed vector is the
@@ -703,12 +737,14 @@ class PartialMatrix(_Shard):
         order, then ``state += ss / cols`` and ``weights -= (lr / (sqrt(state) + eps)) * G``, every
         operation rounded on its own in the shard's type (include/glint_gpu.h has the contract):
         duplicates are coalesced, then one step is taken. There are no order flags: the call is
-        deterministic. Errors as ``updateRowsAdagrad``."""
+        deterministic. Errors as ``updateRowsAdagrad``. ``offsets`` and ``weights`` (keyword only) make it
+        the grouped form, one value row per group in ``grads``, as ``updateRowsAdagrad`` describes it."""
         return self._step_push("updateRowsAdagradRowwise", "glint_mat_push_rows_adagrad_rowwise", state, PartialVector,
-                               rows, grads, (float(lr), float(eps)), sync)
+                               rows, grads, (float(lr), float(eps)), sync, offsets, weights)
 
     def updateRowsAdam(self, state: "PartialMatrix", rows, grads, lr: float, step: int, beta1: float = 0.9,
-                       beta2: float = 0.999, eps: float = 1e-8, sync: bool = True) -> bool:
+                       beta2: float = 0.999, eps: float = 1e-8, sync: bool = True, *, offsets=None,
+                       weights=None) -> bool:
         """Adam row push (an extension; glint_mat_push_rows_adam*): this shard holds the weights and
         ``state`` -- a PartialMatrix of the same type, device and partition with ``2 * cols`` columns --
         both moments, ``m`` in columns ``[0, cols)`` and ``v`` in ``[cols, 2 * cols)``; a zeroed shard is
@@ -719,13 +755,15 @@ class PartialMatrix(_Shard):
         on its own in the shard's type (include/glint_gpu.h has the contract). This is lazy Adam:
         duplicates are coalesced, then one step is taken; ``step`` is the caller's global count from 1,
         and a row that is not named keeps its moments. There are no order flags: the call is
-        deterministic. Errors as ``updateRowsAdagrad``."""
+        deterministic. Errors as ``updateRowsAdagrad``. ``offsets`` and ``weights`` (keyword only) make it
+        the grouped form, one value row per group in ``grads``, as ``updateRowsAdagrad`` describes it."""
         scalars = (float(lr), float(beta1), float(beta2), float(eps), int(step))
         return self._step_push("updateRowsAdam", "glint_mat_push_rows_adam", state, PartialMatrix, rows, grads,
-                               scalars, sync)
+                               scalars, sync, offsets, weights)
 
     def updateRowsFtrl(self, state: "PartialMatrix", rows, grads, alpha: float, beta: float = 1.0, l1: float = 0.0,
-                       l2: float = 0.0, sync: bool = True) -> bool:
+                       l2: float = 0.0, sync: bool = True, *, offsets=None,
+                       weights=None) -> bool:
         """FTRL-proximal row push (an extension; glint_mat_push_rows_ftrl*): this shard holds the weights
         and ``state`` -- a PartialMatrix of the same type, device and partition with ``2 * cols`` columns
         -- ``z`` in columns ``[0, cols)`` and ``n`` in ``[cols, 2 * cols)``; zeroed weights beside a zeroed
@@ -736,10 +774,11 @@ class PartialMatrix(_Shard):
         (include/glint_gpu.h has the contract). The weights are a function of ``(z, n)``: a row's first
         step overwrites whatever the weights shard held. Duplicates are coalesced, then one step is
         taken; a row that is not named is not touched. There are no order flags: the call is
-        deterministic. Errors as ``updateRowsAdagrad``."""
+        deterministic. Errors as ``updateRowsAdagrad``. ``offsets`` and ``weights`` (keyword only) make it
+        the grouped form, one value row per group in ``grads``, as ``updateRowsAdagrad`` describes it."""
         scalars = (float(alpha), float(beta), float(l1), float(l2))
         return self._step_push("updateRowsFtrl", "glint_mat_push_rows_ftrl", state, PartialMatrix, rows, grads,
-                               scalars, sync)
+                               scalars, sync, offsets, weights)
 
     def _axpy_q(self, xshape, cshape, n: int) -> int:
         """q of updateRowsAxpy for vectors of shape ``xshape`` and coefficients of shape ``cshape``."""

@@ -582,6 +582,43 @@ int glint_mat_push_pairs_axpy(glint_shard_t dst, glint_shard_t src, const int64_
 int glint_mat_push_rows_grouped(glint_shard_t shard, const int64_t* rows, int64_t n, const int64_t* grp_ptr,
                                 int64_t g, const void* vals, const void* coef, int flags);
 
+/* Grouped optimizer row pushes (extensions: the reference has no such message): the backward pass of an
+ * embedding bag fused with the optimizer's step -- glint_mat_push_rows_grouped's operands into
+ * glint_mat_push_rows_adagrad, _adagrad_rowwise, _adam or _ftrl. The optimizers are not additive -- a step needs
+ * a row's whole summed gradient -- so they cannot be fed through glint_mat_push_rows_grouped, and without these
+ * calls a bag model must build the n x cols expanded rows for them.
+ *   rows, n, grp_ptr, g, vals, coef   glint_mat_push_rows_grouped's: n rows in g groups, one value row per
+ *                                     group, optionally one coefficient per record (coef may be NULL);
+ *   weights, state and the scalars    the optimizer's own.
+ * Record i, of group k, contributes t_i[c] = vals[k][c] -- the stored bits, no multiply -- when coef is NULL,
+ * else t_i[c] = coef[i] * vals[k][c], the product rounded before any add (no fused multiply-add). Per distinct
+ * row the contributions of its records are added to +0 in push order, then the optimizer takes its one step.
+ * The call therefore equals the optimizer's push of the rows grads[i] = t_i, bit for bit in both shards, and
+ * nothing of size n x cols is built, staged or read. Everything else -- the step's operations and their
+ * rounding, the state's layout, locks, stream order, slabs and the row check before anything is staged (a
+ * rejected message changes neither shard) -- is the optimizer's contract above; the bits never depend on
+ * pointer alignment, g, how records are batched over lanes, or the grid.
+ * GLINT_EINVAL: what the optimizer's call refuses, with vals where grads stands and required only when
+ * g > 0; g < 0, g >= 2^31; a NULL grp_ptr; and -- in these host calls only, before anything is staged -- a
+ * grp_ptr that is not non-decreasing from 0 to n. n == 0 launches nothing and returns GLINT_OK. Staged to the
+ * device in one block, every section 256-B aligned: rows, grp_ptr, coef when given, and vals -- 8 n +
+ * 8 (g + 1) + n * sizeof V + g * cols * sizeof V bytes; nothing is copied back. Device scratch, on `weights`:
+ * the row push's, and one 32-bit group id per record. Kernel timing: the front end and the launch that writes
+ * the group ids are not counted; the one fold launch is recorded under GLINT_K_PUSH_ROWS on `weights`, nothing
+ * on `state`. */
+int glint_mat_push_rows_adagrad_grouped(glint_shard_t weights, glint_shard_t state, const int64_t* rows, int64_t n,
+                                        const int64_t* grp_ptr, int64_t g, const void* vals, const void* coef,
+                                        double lr, double eps);
+int glint_mat_push_rows_adagrad_rowwise_grouped(glint_shard_t weights, glint_shard_t state, const int64_t* rows,
+                                                int64_t n, const int64_t* grp_ptr, int64_t g, const void* vals,
+                                                const void* coef, double lr, double eps);
+int glint_mat_push_rows_adam_grouped(glint_shard_t weights, glint_shard_t state, const int64_t* rows, int64_t n,
+                                     const int64_t* grp_ptr, int64_t g, const void* vals, const void* coef, double lr,
+                                     double beta1, double beta2, double eps, int64_t step);
+int glint_mat_push_rows_ftrl_grouped(glint_shard_t weights, glint_shard_t state, const int64_t* rows, int64_t n,
+                                     const int64_t* grp_ptr, int64_t g, const void* vals, const void* coef,
+                                     double alpha, double beta, double l1, double l2);
+
 /* Weighted row-sum pull (an extension: the reference has no such message): glint_mat_pull_rows_sum with a
  * coefficient per record -- the forward pass of a weighted embedding bag, and the read-side counterpart of
  * glint_mat_push_rows_grouped's coef -- so that g x cols values answer n rows and n weights.
@@ -881,6 +918,29 @@ int glint_mat_push_pairs_axpy_dev(glint_shard_t dst, glint_shard_t src, const in
  * element; coef element by element: the same bits either way. */
 int glint_mat_push_rows_grouped_dev(glint_shard_t shard, const int64_t* rows, int64_t n, const int64_t* grp_ptr,
                                     int64_t g, const void* vals, const void* coef, int flags, void* stream);
+
+/* The grouped optimizer row pushes, device-resident: the same step with the same bits, stream-ordered on
+ * `stream` with no host synchronisation, under both shards' locks as the optimizer's own device call. A row
+ * outside the partition is skipped and reported by glint_shard_sync(weights) (the lowest such record index);
+ * the other records are applied. grp_ptr is not checked on the host: the kernel reads it as
+ * glint_mat_push_rows_grouped_dev does -- every value clamped to [0, n], a record that no group covers
+ * contributes nothing and is not reported. A row NONE of whose records contributed is not stepped: neither
+ * shard's bits change for it (a step with a zero gradient is not a no-op for any of the four optimizers, so
+ * this is part of the contract). vals is read by 16 B when it is 16-B aligned and cols * sizeof V is a
+ * multiple of 16, else element by element; coef element by element: the same bits either way. */
+int glint_mat_push_rows_adagrad_grouped_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows,
+                                            int64_t n, const int64_t* grp_ptr, int64_t g, const void* vals,
+                                            const void* coef, double lr, double eps, void* stream);
+int glint_mat_push_rows_adagrad_rowwise_grouped_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows,
+                                                    int64_t n, const int64_t* grp_ptr, int64_t g, const void* vals,
+                                                    const void* coef, double lr, double eps, void* stream);
+int glint_mat_push_rows_adam_grouped_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows, int64_t n,
+                                         const int64_t* grp_ptr, int64_t g, const void* vals, const void* coef,
+                                         double lr, double beta1, double beta2, double eps, int64_t step,
+                                         void* stream);
+int glint_mat_push_rows_ftrl_grouped_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows, int64_t n,
+                                         const int64_t* grp_ptr, int64_t g, const void* vals, const void* coef,
+                                         double alpha, double beta, double l1, double l2, void* stream);
 
 /* glint_mat_pull_rows_as, device-resident: the same bits, one launch, stream-ordered on `stream` with no host
  * synchronisation (a device call like glint_mat_pull_rows_dev). A row outside the partition is answered with
