@@ -30,6 +30,7 @@ GLINT_DOT_MAX_QUERIES, GLINT_DOT_QUERY_TILE = 1024, 4
 GLINT_AXPY_MAX_VECTORS = 64
 GLINT_ROWWISE_KEEP_STRIPS = 4
 GLINT_TOPK_MAX_K, GLINT_TOPK_MAX_QUERIES, GLINT_TOPK_TILE = 1024, 64, 4096
+GLINT_TOPK_BATCH_MAX_QUERIES, GLINT_TOPK_BATCH_ROWS = 1024, 128
 GLINT_ROUTE_RANGE, GLINT_ROUTE_CYCLIC = 0, 1
 GLINT_RING_SLOTS, GLINT_ZERO_COPY_MAX = 16, 4096
 GLINT_SPARSE_SCAN_TILE = 1024
@@ -107,6 +108,8 @@ SIGNATURES = {
     "glint_mat_push_rows_as_dev": (_I, [_P, _P, _P, _I64, _I, _I, _P]),
     "glint_mat_pull_topk": (_I, [_P, _P, _I64, _I64, _P, _P]),
     "glint_mat_pull_topk_dev": (_I, [_P, _P, _I64, _I64, _P, _P, _P]),
+    "glint_mat_pull_topk_batch": (_I, [_P, _P, _I64, _I64, _P, _P]),
+    "glint_mat_pull_topk_batch_dev": (_I, [_P, _P, _I64, _I64, _P, _P, _P]),
     "glint_shard_last_error": (_I, [_P, C.POINTER(_I64)]),
     "glint_vec_push_dev": (_I, [_P, _P, _P, _I64, _I, _P]),
     "glint_vec_push_dev_gated": (_I, [_P, _P, _P, _I64, _I, _P, _P]),

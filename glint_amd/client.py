@@ -611,6 +611,19 @@ class BigMatrix(_InitMixin):
         row ascending -- and the first ``k`` kept. A matrix of fewer than ``k`` rows fills the rest with
         row -1 and value 0. A score's bits depend on (type, cols) only and the order is total over
         (rank, row), so the answer does not depend on how the matrix is partitioned."""
+        return self._pull_topk(x, k, "getTopK")
+
+    def pullTopKBatch(self, x, k: int):
+        """``pullTopK`` for a serving batch (an extension): Float and Double matrices, up to 1024 query
+        vectors. Every partition answers one PartialMatrix.getTopKBatch -- scores by matrix instructions,
+        the shard read once per 64 queries -- and the merge is ``pullTopK``'s. A score depends on the row
+        and the query only, so the answer does not depend on how the matrix is partitioned; its bits are
+        getTopKBatch's, not getRowsDot's. Use it from a few tens of queries up; below that ``pullTopK``
+        is faster."""
+        return self._pull_topk(x, k, "getTopKBatch")
+
+    def _pull_topk(self, x, k: int, call: str):
+        """pullTopK / pullTopKBatch: one ``call`` per partition, then the merge by (rank, global row)."""
         dtype = self.shards[0].np_dtype
         x = np.ascontiguousarray(x, dtype=dtype)
         self._check_queries(x)
@@ -618,7 +631,7 @@ class BigMatrix(_InitMixin):
         if k < 1:
             raise ValueError(f"k: {k}, expected k >= 1")
         x2 = x.reshape(-1, self.cols)
-        parts = [sh.getTopK(x2, k) for sh in self.shards]
+        parts = [getattr(sh, call)(x2, k) for sh in self.shards]
         rows = np.concatenate([np.asarray(r).reshape(x2.shape[0], k) for r, _ in parts], axis=1)
         vals = np.concatenate([np.asarray(v).reshape(x2.shape[0], k) for _, v in parts], axis=1)
         out_rows = np.full((x2.shape[0], k), -1, np.int64)

@@ -1566,6 +1566,24 @@ inline int pull_topk_args(const glint_shard* s, const void* x, int64_t q, int64_
   return GLINT_OK;
 }
 
+// argument checks of glint_mat_pull_topk_batch / _dev: a Float or Double matrix shard, x and both outputs
+// present, 1 to GLINT_TOPK_BATCH_MAX_QUERIES queries, 1 <= k <= GLINT_TOPK_MAX_K
+inline int pull_topk_batch_args(const glint_shard* s, const void* x, int64_t q, int64_t k, const void* out_rows,
+                                const void* out_vals) {
+  if (!s || s->part.cols == 0 || (s->dtype != GLINT_F32 && s->dtype != GLINT_F64)) return GLINT_EINVAL;
+  if (!x || !out_rows || !out_vals) return GLINT_EINVAL;
+  if (q < 1 || q > GLINT_TOPK_BATCH_MAX_QUERIES || k < 1 || k > GLINT_TOPK_MAX_K) return GLINT_EINVAL;
+  return GLINT_OK;
+}
+
+// the batched top-k pull has Float and Double instances only (pull_topk_batch_args has refused the rest)
+inline int pull_topk_batch_any(glint_shard* s, const void* x, i64 q, i64 k, i64* out_rows, void* out_vals,
+                               hipStream_t st) {
+  if (s->dtype == GLINT_F32) return pull_topk_batch<float>(s, x, q, k, out_rows, out_vals, st);
+  if (s->dtype == GLINT_F64) return pull_topk_batch<double>(s, x, q, k, out_rows, out_vals, st);
+  return GLINT_EINVAL;
+}
+
 // argument check of the element-wise device-resident calls: a vector (matrix) shard, n >= 0
 inline int elem_args(const glint_shard* s, bool mat, int64_t n) {
   if (!s || n < 0) return GLINT_EINVAL;
@@ -1694,7 +1712,7 @@ std::atomic<unsigned> g_env_gen{1};
 extern "C" {
 
 // 0.17.0: glint_mat_pull_rows_wsum / _dev (weighted row-sum pull), glint_mat_pull_rows_gdot / _dev (grouped row dot)
-int glint_version(void) { return 1900; }
+int glint_version(void) { return 2000; }
 
 int glint_wire_supported(int dtype, int wire) { return wire_supported(dtype, wire) ? 1 : 0; }
 
@@ -2117,6 +2135,13 @@ int glint_mat_pull_topk_dev(glint_shard_t s, const void* x, int64_t q, int64_t k
                             void* stream) {
   return dev_call(s, pull_topk_args(s, x, q, k, out_rows, out_vals), stream, [&](hipStream_t st) -> int {
     GLINT_DISPATCH(s->dtype, pull_topk, s, x, q, k, (i64*)out_rows, out_vals, st);
+  });
+}
+
+int glint_mat_pull_topk_batch_dev(glint_shard_t s, const void* x, int64_t q, int64_t k, int64_t* out_rows,
+                                  void* out_vals, void* stream) {
+  return dev_call(s, pull_topk_batch_args(s, x, q, k, out_rows, out_vals), stream, [&](hipStream_t st) -> int {
+    return pull_topk_batch_any(s, x, q, k, (i64*)out_rows, out_vals, st);
   });
 }
 
@@ -3308,6 +3333,20 @@ int glint_mat_pull_topk(glint_shard_t s, const void* x, int64_t q, int64_t k, in
                      back[1] = {out_vals, st.extra + rows_bytes, vals_bytes};
                      GLINT_DISPATCH(s->dtype, pull_topk, s, (const void*)st.p[0], q, k, (i64*)st.extra,
                                     (void*)(st.extra + rows_bytes), stream);
+                   });
+}
+
+// glint_mat_pull_topk_batch: glint_mat_pull_topk's staging and copy-back around the batched pull
+int glint_mat_pull_topk_batch(glint_shard_t s, const void* x, int64_t q, int64_t k, int64_t* out_rows,
+                              void* out_vals) {
+  if (int rc = pull_topk_batch_args(s, x, q, k, out_rows, out_vals)) return rc;
+  const size_t rows_bytes = pad256((size_t)q * (size_t)k * 8), vals_bytes = (size_t)q * (size_t)k * s->vsize;
+  return host_call(s, s, {nullptr, nullptr, 0}, false, {{x, (size_t)q * (size_t)s->part.cols * s->vsize}},
+                   rows_bytes + vals_bytes, [&](const Staged& st, hipStream_t stream, HostBack* back) -> int {
+                     back[0] = {out_rows, st.extra, (size_t)q * (size_t)k * 8};
+                     back[1] = {out_vals, st.extra + rows_bytes, vals_bytes};
+                     return pull_topk_batch_any(s, (const void*)st.p[0], q, k, (i64*)st.extra,
+                                                (void*)(st.extra + rows_bytes), stream);
                    });
 }
 

@@ -659,4 +659,16 @@ int pull_rows_dot(glint_shard* s, const i64* rows, i64 n, const void* x, i64 q, 
 // level on st, no host synchronisation; the scratch is s->d_det.
 template <typename V>
 int pull_topk(glint_shard* s, const void* x, i64 q, i64 k, i64* out_rows, void* out_vals, hipStream_t st);
+// the selection levels of a top-k plan (glint_topk.hip; glint_topk_plan.h), Float and Double: one launch per
+// level on st over the scores [q][size] at the front of s->d_det; the last level writes the q x k answer
+struct TopkPlan;
+template <typename V>
+int topk_select_levels(glint_shard* s, const TopkPlan& p, i64 q, i64 k, i64* out_rows, void* out_vals,
+                       hipStream_t st);
+// batched top-k row pull (glint_topk_batch.hip), Float and Double only: pull_topk's answer layout and order
+// for 1 <= q <= GLINT_TOPK_BATCH_MAX_QUERIES, the scores accumulated by matrix instructions (their bits are
+// not pull_rows_dot's). Per pass of 64 queries one scores launch and the selection levels on st, no host
+// synchronisation; the scratch is s->d_det, that of a 64-query pull_topk.
+template <typename V>
+int pull_topk_batch(glint_shard* s, const void* x, i64 q, i64 k, i64* out_rows, void* out_vals, hipStream_t st);
 }  // namespace glint

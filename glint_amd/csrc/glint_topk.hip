@@ -221,35 +221,19 @@ __global__ __launch_bounds__(kSelTPB) void topk_select_kernel(TopkSel<V> a) {
 }
 
 // ---- host side ----------------------------------------------------------------------------------
-// Enqueues the top-k pull on st (no host synchronisation): the scores launch and one launch per level,
-// all counted under GLINT_K_PULL_ROWS_DOT. x, out_rows and out_vals are device pointers. Under the
-// shard's lock; the scratch is s->d_det.
+// Enqueues the selection levels of plan p on st over the scores [q][size] at the front of s->d_det: one
+// launch per level, counted under GLINT_K_PULL_ROWS_DOT; the last level writes out_rows / out_vals
+// (q x k, device pointers). Shared by the top-k pull below and the batched one (glint_topk_batch.hip).
 template <typename V>
-int pull_topk(glint_shard* s, const void* x, i64 q, i64 k, i64* out_rows, void* out_vals, hipStream_t st) {
+int topk_select_levels(glint_shard* s, const TopkPlan& p, i64 q, i64 k, i64* out_rows, void* out_vals,
+                       hipStream_t st) {
   typedef typename Rank<V>::K K;
-  const TopkPlan p = topk_plan(s->part.size, q, k, (i64)sizeof(V));
-  if (p.levels < 1) return GLINT_EINVAL;
-  int rc = grow(&s->d_det, &s->det_bytes, (size_t)p.total_bytes);
-  if (rc) return rc;
   char* base = (char*)s->d_det;
-  V* scores = (V*)base;
-  const i64 size = s->part.size;
-  if (size > 0) {
-    const bool v16 = ((i64)s->part.cols * (i64)sizeof(V)) % 16 == 0;
-    const int xw = v16 && aligned(x, 16);
-    const i64 qtiles = q == 1 ? 1 : (q + kDotTile - 1) / kDotTile;
-    const unsigned grid = grid_for(size * qtiles, kTPB / 64, (i64)s->cus * 8);
-    void (*sk)(const V*, int, int, const V*, PartDesc, V*);
-    if (q == 1) sk = v16 ? topk_scores_kernel<V, true, 1> : topk_scores_kernel<V, false, 1>;
-    else sk = v16 ? topk_scores_kernel<V, true, kDotTile> : topk_scores_kernel<V, false, kDotTile>;
-    HIPCHK(launch_k(s, GLINT_K_PULL_ROWS_DOT, sk, grid, kTPB, st, (const V*)x, (int)q, xw, (const V*)s->data, s->part,
-                    scores));
-  }
   for (int l = 0; l < p.levels; ++l) {
     const TopkLevel& lv = p.level[l];
     TopkSel<V> a{};
-    a.scores = scores;
-    a.size = size;
+    a.scores = (const V*)base;
+    a.size = s->part.size;
     a.in_key = (const K*)(base + lv.in_key);
     a.in_row = (const u32*)(base + lv.in_row);
     a.n_in = lv.n_in;
@@ -268,6 +252,33 @@ int pull_topk(glint_shard* s, const void* x, i64 q, i64 k, i64* out_rows, void* 
   return GLINT_OK;
 }
 
+// Enqueues the top-k pull on st (no host synchronisation): the scores launch and one launch per level,
+// all counted under GLINT_K_PULL_ROWS_DOT. x, out_rows and out_vals are device pointers. Under the
+// shard's lock; the scratch is s->d_det.
+template <typename V>
+int pull_topk(glint_shard* s, const void* x, i64 q, i64 k, i64* out_rows, void* out_vals, hipStream_t st) {
+  const TopkPlan p = topk_plan(s->part.size, q, k, (i64)sizeof(V));
+  if (p.levels < 1) return GLINT_EINVAL;
+  int rc = grow(&s->d_det, &s->det_bytes, (size_t)p.total_bytes);
+  if (rc) return rc;
+  V* scores = (V*)s->d_det;
+  const i64 size = s->part.size;
+  if (size > 0) {
+    const bool v16 = ((i64)s->part.cols * (i64)sizeof(V)) % 16 == 0;
+    const int xw = v16 && aligned(x, 16);
+    const i64 qtiles = q == 1 ? 1 : (q + kDotTile - 1) / kDotTile;
+    const unsigned grid = grid_for(size * qtiles, kTPB / 64, (i64)s->cus * 8);
+    void (*sk)(const V*, int, int, const V*, PartDesc, V*);
+    if (q == 1) sk = v16 ? topk_scores_kernel<V, true, 1> : topk_scores_kernel<V, false, 1>;
+    else sk = v16 ? topk_scores_kernel<V, true, kDotTile> : topk_scores_kernel<V, false, kDotTile>;
+    HIPCHK(launch_k(s, GLINT_K_PULL_ROWS_DOT, sk, grid, kTPB, st, (const V*)x, (int)q, xw, (const V*)s->data, s->part,
+                    scores));
+  }
+  return topk_select_levels<V>(s, p, q, k, out_rows, out_vals, st);
+}
+
+template int topk_select_levels<float>(glint_shard*, const TopkPlan&, i64, i64, i64*, void*, hipStream_t);
+template int topk_select_levels<double>(glint_shard*, const TopkPlan&, i64, i64, i64*, void*, hipStream_t);
 template int pull_topk<int>(glint_shard*, const void*, i64, i64, i64*, void*, hipStream_t);
 template int pull_topk<long long>(glint_shard*, const void*, i64, i64, i64*, void*, hipStream_t);
 template int pull_topk<float>(glint_shard*, const void*, i64, i64, i64*, void*, hipStream_t);

@@ -1161,6 +1161,25 @@ class PartialMatrix(_Shard):
         Host array: x goes up, the q x k pairs come back -- nothing of the shard's size crosses the
         link. Device tensor: stream-ordered launches on the current stream, device tensors returned
         (``sync=False`` leaves the wait to the caller)."""
+        return self._topk_call("glint_mat_pull_topk", N.GLINT_TOPK_MAX_QUERIES, x, k, sync)
+
+    def getTopKBatch(self, x, k: int, sync: bool = True):
+        """``getTopK`` for a serving batch (an extension; glint_mat_pull_topk_batch*): Float and Double
+        shards, ``x`` of shape (cols,) or (q, cols) with ``1 <= q <= 1024``, the same two arrays back in
+        the same order (rank descending, then global row ascending; NaN below every number; -1 / 0 fill).
+        The scores are computed by matrix instructions over tiles of rows x 64 queries, so the shard is
+        read once per 64 queries. A score's bits depend on (type, cols, the row, the query) only -- never
+        on q, k or positions -- but they are not getRowsDot's: each lies within
+        ``cols*u / (1 - cols*u) * sum|row[c] * x[j][c]|`` of the exact dot.
+
+        Use it from a few tens of queries up. Below that ``getTopK`` is faster -- a pass of 64 queries is
+        then mostly padding -- and only ``getTopK`` gives getRowsDot's bits."""
+        if not np.issubdtype(self.np_dtype, np.floating):
+            raise TypeError(f"getTopKBatch: Float and Double shards only, not {np.dtype(self.np_dtype).name}")
+        return self._topk_call("glint_mat_pull_topk_batch", N.GLINT_TOPK_BATCH_MAX_QUERIES, x, k, sync)
+
+    def _topk_call(self, fn: str, max_q: int, x, k: int, sync: bool):
+        """getTopK / getTopKBatch: the C call ``fn``, or ``fn + "_dev"`` for a device tensor."""
         k = int(k)
         if not 1 <= k <= N.GLINT_TOPK_MAX_K:
             raise ValueError(f"k: {k}, expected 1 <= k <= {N.GLINT_TOPK_MAX_K}")
@@ -1168,29 +1187,29 @@ class PartialMatrix(_Shard):
             import torch
             if x.dtype != self.torch_dtype or not x.is_contiguous() or x.device.index != self.device:
                 raise TypeError(f"x: expected a contiguous {self.torch_dtype} CUDA tensor on cuda:{self.device}")
-            q, shape = self._topk_shape(tuple(x.shape), k)
+            q, shape = self._topk_shape(tuple(x.shape), k, max_q)
             rows = torch.empty(shape, dtype=torch.int64, device=x.device)
             vals = torch.empty(shape, dtype=self.torch_dtype, device=x.device)
-            rc = self.lib.glint_mat_pull_topk_dev(self.handle, x.data_ptr(), q, k, rows.data_ptr(), vals.data_ptr(),
-                                                  self._stream_of(x))
+            rc = getattr(self.lib, fn + "_dev")(self.handle, x.data_ptr(), q, k, rows.data_ptr(), vals.data_ptr(),
+                                                self._stream_of(x))
             self._dev_done(rc, x, sync)
             return rows, vals
         x = _host(x, self.np_dtype)
-        q, shape = self._topk_shape(x.shape, k)
+        q, shape = self._topk_shape(x.shape, k, max_q)
         rows = np.empty(shape, np.int64)
         vals = np.empty(shape, self.np_dtype)
-        check(self.lib.glint_mat_pull_topk(self.handle, x.ctypes.data, q, k, rows.ctypes.data, vals.ctypes.data),
+        check(getattr(self.lib, fn)(self.handle, x.ctypes.data, q, k, rows.ctypes.data, vals.ctypes.data),
               self.handle)
         return rows, vals
 
-    def _topk_shape(self, xshape, k: int):
-        """(q, answer shape) of getTopK for query vectors of shape ``xshape``."""
+    def _topk_shape(self, xshape, k: int, max_q: int):
+        """(q, answer shape) of getTopK / getTopKBatch for query vectors of shape ``xshape``."""
         if xshape == (self.cols,):
             return 1, (k,)
-        if len(xshape) == 2 and xshape[1] == self.cols and 1 <= xshape[0] <= N.GLINT_TOPK_MAX_QUERIES:
+        if len(xshape) == 2 and xshape[1] == self.cols and 1 <= xshape[0] <= max_q:
             return xshape[0], (xshape[0], k)
         raise ValueError(f"x: shape {tuple(xshape)}, expected ({self.cols},) or (q, {self.cols}) with "
-                         f"1 <= q <= {N.GLINT_TOPK_MAX_QUERIES}")
+                         f"1 <= q <= {max_q}")
 
     def to_numpy(self) -> np.ndarray:
         return self.getRows(self._keys())

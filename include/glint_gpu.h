@@ -745,6 +745,35 @@ int glint_mat_push_rows_as(glint_shard_t shard, const int64_t* rows, const void*
 int glint_mat_pull_topk(glint_shard_t shard, const void* x, int64_t q, int64_t k, int64_t* out_rows,
                         void* out_vals);
 
+/* Batched top-k row pull (an extension): glint_mat_pull_topk for a serving batch -- Float and Double
+ * matrix shards, 1 <= q <= GLINT_TOPK_BATCH_MAX_QUERIES, 1 <= k <= GLINT_TOPK_MAX_K; x, out_rows and
+ * out_vals as there (dense q x cols / q x k). The scores are computed as the matrix product they are, by
+ * matrix instructions over tiles of GLINT_TOPK_BATCH_ROWS rows x 64 queries, so the shard is read once per
+ * 64 queries. Use it from q of a few tens up; below that glint_mat_pull_topk is faster (a pass of 64
+ * queries is then mostly padding) and it alone gives glint_mat_pull_rows_dot's bits.
+ * Score. score(row, x[j]) is a floating-point sum of the cols products row[c] * x[j][c] in the shard's
+ * type, accumulated by matrix instructions in a fixed order over ascending columns (DESIGN.md "Batched
+ * top-k pull"). Its bits are a function of (type, cols, the row's values, x[j]'s values) only: they never
+ * depend on q, on the query's position in the batch, on the row's position in the shard, on k, on the grid
+ * or on the alignment of x or of the rows. They are NOT glint_mat_pull_rows_dot's: products may be fused
+ * and the order differs. |score - exact| <= g * sum_c |row[c] * x[j][c]| with g = cols u / (1 - cols u),
+ * u = 2^-24 (Float) or 2^-53 (Double), for inputs whose products and partial sums are normal numbers or
+ * zero; what the matrix pipeline does with subnormal products is unspecified. Non-finite values propagate
+ * as IEEE arithmetic does (an inf * 0 or inf - inf among a row's terms gives NaN); the padding the kernel
+ * adds -- column tail, missing rows, missing queries -- is 0 * 0 and never creates one. Only `cols` elements
+ * of a row are read, never the pitch padding.
+ * Order, fill, keys, determinism: exactly glint_mat_pull_topk's -- rank descending then global row
+ * ascending, every NaN below -inf, -0 equal to +0, row -1 / value +0 fill, range and cyclic keys, out_vals
+ * the computed score's own bits, no atomics. The slab, view, lock and sync rules are glint_mat_pull_topk's.
+ * GLINT_EINVAL: a NULL or vector shard, an Int/Long shard, NULL x, out_rows or out_vals, q outside
+ * [1, GLINT_TOPK_BATCH_MAX_QUERIES], k outside [1, GLINT_TOPK_MAX_K]. Staged to the device: x; copied
+ * back: q * k * (8 + sizeof V) bytes. */
+#define GLINT_TOPK_BATCH_MAX_QUERIES 1024
+/* Rows of one scores tile (tests size their cases by it; the answer never depends on it). */
+#define GLINT_TOPK_BATCH_ROWS 128
+int glint_mat_pull_topk_batch(glint_shard_t shard, const void* x, int64_t q, int64_t k, int64_t* out_rows,
+                              void* out_vals);
+
 /* After GLINT_EOUTOFRANGE: index (within the failing call) of the first rejected record. */
 int glint_shard_last_error(glint_shard_t shard, int64_t* first_bad_record);
 
@@ -833,6 +862,14 @@ int glint_mat_pull_rows_dot_dev(glint_shard_t shard, const int64_t* rows, int64_
  * same bits either way. Scratch is the shard's growable device scratch. */
 int glint_mat_pull_topk_dev(glint_shard_t shard, const void* x, int64_t q, int64_t k, int64_t* out_rows,
                             void* out_vals, void* stream);
+
+/* glint_mat_pull_topk_batch, device-resident: the same answer, stream-ordered on `stream` with no host
+ * synchronisation: per pass of 64 queries one scores launch and one launch per selection level. out_rows
+ * and out_vals must not overlap x. x is read by 16 B when it is 16-B aligned (and cols allow), else element
+ * by element: the same bits either way. Scratch is the shard's growable device scratch, that of a 64-query
+ * glint_mat_pull_topk_dev. */
+int glint_mat_pull_topk_batch_dev(glint_shard_t shard, const void* x, int64_t q, int64_t k, int64_t* out_rows,
+                                  void* out_vals, void* stream);
 
 /* glint_mat_push_rows_axpy, device-resident: the same contributions in the same order, stream-ordered on
  * `stream` with no host synchronisation. A row outside the partition is skipped and reported by
@@ -1275,7 +1312,8 @@ enum glint_kernel_id {
   GLINT_K_PULL_ROWS_SUM = 10,
   /* the row dot-product pull (glint_mat_pull_rows_dot*): one launch per call. Also every launch of a top-k
    * pull (glint_mat_pull_topk*), which is a dot pull over every row plus a selection: its scores launch
-   * and one launch per selection level, so the sum is that pull's whole device time. Also the one launch
+   * and one launch per selection level, so the sum is that pull's whole device time; a batched top-k pull
+   * (glint_mat_pull_topk_batch*) records those launches once per pass of 64 queries. Also the one launch
    * of a row-pair dot pull (glint_mat_pull_pairs_dot*), recorded on its first shard only, and the one launch
    * of a grouped row-dot pull (glint_mat_pull_rows_gdot*) */
   GLINT_K_PULL_ROWS_DOT = 11,
