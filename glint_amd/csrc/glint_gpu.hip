@@ -1584,6 +1584,22 @@ inline int pull_topk_batch_any(glint_shard* s, const void* x, i64 q, i64 k, i64*
   return GLINT_EINVAL;
 }
 
+// argument checks of glint_mat_pull_rows_dot_batch / _dev: pull_dot_args on a Float or Double shard, and x
+// present (there is no self-dot)
+inline int pull_dot_batch_args(const glint_shard* s, const void* rows, int64_t n, const void* x, int64_t q,
+                               const void* out) {
+  if (!s || (s->dtype != GLINT_F32 && s->dtype != GLINT_F64) || !x) return GLINT_EINVAL;
+  return pull_dot_args(s, rows, n, x, q, out);
+}
+
+// the batched row dot pull has Float and Double instances only (pull_dot_batch_args has refused the rest)
+inline int pull_rows_dot_batch_any(glint_shard* s, const i64* rows, i64 n, const void* x, i64 q, void* out,
+                                   hipStream_t st) {
+  if (s->dtype == GLINT_F32) return pull_rows_dot_batch<float>(s, rows, n, x, q, out, st);
+  if (s->dtype == GLINT_F64) return pull_rows_dot_batch<double>(s, rows, n, x, q, out, st);
+  return GLINT_EINVAL;
+}
+
 // argument check of the element-wise device-resident calls: a vector (matrix) shard, n >= 0
 inline int elem_args(const glint_shard* s, bool mat, int64_t n) {
   if (!s || n < 0) return GLINT_EINVAL;
@@ -1712,7 +1728,8 @@ std::atomic<unsigned> g_env_gen{1};
 extern "C" {
 
 // 0.17.0: glint_mat_pull_rows_wsum / _dev (weighted row-sum pull), glint_mat_pull_rows_gdot / _dev (grouped row dot)
-int glint_version(void) { return 2000; }
+// 0.21.0: glint_mat_pull_rows_dot_batch / _dev (batched row dot pull)
+int glint_version(void) { return 2100; }
 
 int glint_wire_supported(int dtype, int wire) { return wire_supported(dtype, wire) ? 1 : 0; }
 
@@ -2128,6 +2145,15 @@ int glint_mat_pull_rows_dot_dev(glint_shard_t s, const int64_t* rows, int64_t n,
   if (args_rc == GLINT_OK && n == 0) return GLINT_OK;
   return dev_call(s, args_rc, stream, [&](hipStream_t st) -> int {
     GLINT_DISPATCH(s->dtype, pull_rows_dot, s, (const i64*)rows, n, x, q, out, st);
+  });
+}
+
+int glint_mat_pull_rows_dot_batch_dev(glint_shard_t s, const int64_t* rows, int64_t n, const void* x, int64_t q,
+                                      void* out, void* stream) {
+  const int args_rc = pull_dot_batch_args(s, rows, n, x, q, out);
+  if (args_rc == GLINT_OK && n == 0) return GLINT_OK;
+  return dev_call(s, args_rc, stream, [&](hipStream_t st) -> int {
+    return pull_rows_dot_batch_any(s, (const i64*)rows, n, x, q, out, st);
   });
 }
 
@@ -3317,6 +3343,23 @@ int glint_mat_pull_rows_dot(glint_shard_t s, const int64_t* rows, int64_t n, con
                      back[0] = {out, s->d_det, out_bytes};
                      GLINT_DISPATCH(s->dtype, pull_rows_dot, s, (const i64*)st.p[0], n, x ? (const void*)st.p[1] : nullptr, q,
                                     s->d_det, stream);
+                   });
+}
+
+// glint_mat_pull_rows_dot_batch: glint_mat_pull_rows_dot's check, staging and copy-back around the batched
+// pull -- rows and x go out in one block (x 256-B aligned in it), n * q values come back
+int glint_mat_pull_rows_dot_batch(glint_shard_t s, const int64_t* rows, int64_t n, const void* x, int64_t q,
+                                  void* out) {
+  if (int rc = pull_dot_batch_args(s, rows, n, x, q, out)) return rc;
+  if (n == 0) return GLINT_OK;
+  const size_t out_bytes = (size_t)n * (size_t)q * s->vsize;
+  return host_call(s, s, {rows, nullptr, n}, false,
+                   {{rows, (size_t)n * 8}, {x, (size_t)q * (size_t)s->part.cols * s->vsize}}, 0,
+                   [&](const Staged& st, hipStream_t stream, HostBack* back) -> int {
+                     if (int rc = grow(&s->d_det, &s->det_bytes, out_bytes)) return rc;
+                     back[0] = {out, s->d_det, out_bytes};
+                     return pull_rows_dot_batch_any(s, (const i64*)st.p[0], n, (const void*)st.p[1], q, s->d_det,
+                                                    stream);
                    });
 }
 

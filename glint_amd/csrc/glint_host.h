@@ -671,4 +671,10 @@ int topk_select_levels(glint_shard* s, const TopkPlan& p, i64 q, i64 k, i64* out
 // synchronisation; the scratch is s->d_det, that of a 64-query pull_topk.
 template <typename V>
 int pull_topk_batch(glint_shard* s, const void* x, i64 q, i64 k, i64* out_rows, void* out_vals, hipStream_t st);
+// batched row dot pull (glint_rowdot_batch.hip), Float and Double only: pull_rows_dot's answer layout for
+// 1 <= q <= GLINT_DOT_MAX_QUERIES and x present, the scores accumulated by matrix instructions (their bits
+// are pull_topk_batch's, not pull_rows_dot's); rows outside the partition answer +0 and are recorded in
+// err_of(s). One launch on st, no scratch, no host synchronisation.
+template <typename V>
+int pull_rows_dot_batch(glint_shard* s, const i64* rows, i64 n, const void* x, i64 q, void* out, hipStream_t st);
 }  // namespace glint

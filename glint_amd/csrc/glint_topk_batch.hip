@@ -35,41 +35,13 @@
 // Groups ascend within a slab and slabs ascend over cols; the columns from cols up to the next multiple
 // of the slab contribute 0 * 0. That chain is the accumulation order of the contract.
 #include "glint_host.h"
+#include "glint_slab.h"  // the slab geometry and tb_chunk: shared with the batched row dot pull
 #include "glint_topk_plan.h"
 
 namespace glint {
 
-constexpr int kTbRows = GLINT_TOPK_BATCH_ROWS;  // rows of a tile
-constexpr int kTbPass = 64;                     // queries of a pass
-constexpr int kTbLines = kTbRows + kTbPass;     // lines of a slab: the tile's rows, then the queries
-constexpr int kTbLineBytes = 128;               // K bytes of a slab
-constexpr int kTbLinePitch = kTbLineBytes + 16; // bytes between lines in LDS
-constexpr int kTbSlabBytes = kTbLines * kTbLinePitch;
-constexpr int kTbStage = kTbLines / 32;         // chunks a thread stages per slab
-static_assert(kTbRows == 32 * (kTPB / 64), "a wave owns 32 rows of the tile");
-static_assert(kTbLines % 32 == 0 && kTPB == 32 * (kTbLineBytes / 16), "a thread stages one chunk of 32 lines apart");
+static_assert(kTbRows == GLINT_TOPK_BATCH_ROWS, "the tile of the header is the slab's");
 static_assert(kTbPass == GLINT_TOPK_MAX_QUERIES, "a pass is selected by a topk_plan of at most its queries");
-
-typedef __attribute__((ext_vector_type(4))) unsigned int TbU4;
-typedef __attribute__((ext_vector_type(4))) float TbF4;
-typedef __attribute__((ext_vector_type(16))) float TbF16;
-typedef __attribute__((ext_vector_type(2))) double TbD2;
-typedef __attribute__((ext_vector_type(4))) double TbD4;
-
-// One 16-B chunk of a line, columns [c, c + E): zero when the line is a pad or c >= cols; one 16-B load
-// when the chunk is whole and the line allows it; else the elements below cols one by one.
-template <typename V>
-__device__ __forceinline__ TbU4 tb_chunk(const V* __restrict__ line, i64 c, i64 cols, bool live, bool wide) {
-  constexpr int E = (int)(16 / sizeof(V));
-  TbU4 r = {0u, 0u, 0u, 0u};
-  if (!live || c >= cols) return r;
-  if (wide && c + E <= cols) return *reinterpret_cast<const TbU4*>(line + c);
-  V e[E];
-#pragma unroll
-  for (int k = 0; k < E; ++k) e[k] = c + k < cols ? line[c + k] : V(0);
-  __builtin_memcpy(&r, e, 16);
-  return r;
-}
 
 // The wave's accumulators, the matrix instructions of one slab and the store of the finished scores.
 template <typename V> struct TbMma;

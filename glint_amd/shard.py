@@ -1026,6 +1026,31 @@ class PartialMatrix(_Shard):
         nothing is written. Device tensors: one stream-ordered launch on the current stream; a row
         outside the partition answers zeros and is raised by the sync (``sync=True``, or a later
         ``sync()``)."""
+        return self._dot_call("glint_mat_pull_rows_dot", rows, x, out, sync)
+
+    def getRowsDotBatch(self, rows, x, out=None, sync: bool = True):
+        """``getRowsDot`` for a batch of vectors (an extension; glint_mat_pull_rows_dot_batch*): Float and
+        Double shards, ``x`` of shape (cols,) or (q, cols) with ``1 <= q <= 1024`` (there is no self-dot),
+        the same (n,) or (n, q) answer with ``out[i, j] = score(row rows[i], x[j])``, host arrays and device
+        tensors handled as there. The scores are computed by matrix instructions over tiles of 128 requests
+        x 64 vectors, so a requested row is walked once per 64 vectors and not once per 4. A score's bits
+        depend on (type, cols, the row, the vector) only -- never on n, q, positions or repeats -- and they
+        are the values ``getTopKBatch`` reports for that row and vector, so a re-rank of its rows returns
+        its values; each lies within ``cols*u / (1 - cols*u) * sum|row[c] * x[j][c]|`` of the exact dot.
+        Device tensors: a row outside the partition answers q values of +0, whatever ``x`` holds.
+
+        Use it from 8 vectors up (measured on 2^17 x 512 with 2^15 requests or more: 1.0 to 1.6 x
+        ``getRowsDot`` at q = 8, 6 to 9 x from q = 64; with 2^12 requests level at q = 64 and 3 to 8 x from
+        q = 256). Below that ``getRowsDot`` is faster, 1.4 to 2 x at q = 1 -- a pass of 64 vectors is then
+        mostly padding -- and only ``getRowsDot`` gives the dot pull's bits."""
+        if not np.issubdtype(self.np_dtype, np.floating):
+            raise TypeError(f"getRowsDotBatch: Float and Double shards only, not {np.dtype(self.np_dtype).name}")
+        if x is None:
+            raise TypeError("getRowsDotBatch: x is required (getRowsDot has the self-dot)")
+        return self._dot_call("glint_mat_pull_rows_dot_batch", rows, x, out, sync)
+
+    def _dot_call(self, fn: str, rows, x, out, sync: bool):
+        """getRowsDot / getRowsDotBatch: the C call ``fn``, or ``fn + "_dev"`` for device tensors."""
         if _is_torch_cuda(rows):
             import torch
             n = rows.numel()
@@ -1036,9 +1061,9 @@ class PartialMatrix(_Shard):
             if out is None:
                 out = torch.empty(shape, dtype=self.torch_dtype, device=rows.device)
             self._check_dev(n, rows, out=out, out_elems=n * q)
-            rc = self.lib.glint_mat_pull_rows_dot_dev(self.handle, rows.data_ptr(), n,
-                                                      x.data_ptr() if x is not None else None, q, out.data_ptr(),
-                                                      self._stream_of(rows))
+            rc = getattr(self.lib, fn + "_dev")(self.handle, rows.data_ptr(), n,
+                                                x.data_ptr() if x is not None else None, q, out.data_ptr(),
+                                                self._stream_of(rows))
             self._dev_done(rc, rows, sync)
             return out
         r = _host(rows, np.int64).reshape(-1)
@@ -1047,9 +1072,8 @@ class PartialMatrix(_Shard):
             x = _host(x, self.np_dtype)
             q, shape = self._dot_shape(x.shape, r.size)
         res = self._host_out(out, shape)
-        check(self.lib.glint_mat_pull_rows_dot(self.handle, r.ctypes.data, r.size,
-                                               x.ctypes.data if x is not None else None, q, res.ctypes.data),
-              self.handle)
+        check(getattr(self.lib, fn)(self.handle, r.ctypes.data, r.size,
+                                    x.ctypes.data if x is not None else None, q, res.ctypes.data), self.handle)
         return res
 
     def _pair_other(self, other, name: str) -> None:

@@ -774,6 +774,40 @@ int glint_mat_pull_topk(glint_shard_t shard, const void* x, int64_t q, int64_t k
 int glint_mat_pull_topk_batch(glint_shard_t shard, const void* x, int64_t q, int64_t k, int64_t* out_rows,
                               void* out_vals);
 
+/* Batched row dot pull (an extension): glint_mat_pull_rows_dot for a batch of vectors -- Float and Double
+ * matrix shards, 1 <= q <= GLINT_DOT_MAX_QUERIES, x never NULL (there is no self-dot) -- with the n x q
+ * answer computed as the matrix product it is, table[rows] * x^T, by matrix instructions over tiles of
+ * GLINT_DOT_BATCH_ROWS requests x 64 vectors: in-batch logits of a two-tower step, a re-rank of the rows
+ * glint_mat_pull_topk_batch returned, scores of a held-out candidate list.
+ *   x     q x cols values of the shard's type, dense row-major;
+ *   out   n x q values of the shard's type, dense: out[i*q + j] = score(row rows[i], x[j]).
+ * Requests keep the caller's order; a row requested twice is answered twice. x must not overlap out. There
+ * are no flags and no atomics: the answer is deterministic. Use it from q of a few tens up (DESIGN.md
+ * "Batched row dot pull" has the measured crossover); below that glint_mat_pull_rows_dot is faster (a pass
+ * of 64 vectors is then mostly padding) and it alone gives glint_mat_pull_rows_dot's bits.
+ * Score. score(row, x[j]) is a floating-point sum of the cols products row[c] * x[j][c] in the shard's
+ * type, accumulated by matrix instructions in a fixed order over ascending columns (DESIGN.md "Batched
+ * top-k pull"). Its bits are a function of (type, cols, the row's values, x[j]'s values) only: they never
+ * depend on n, on q, on the request's position or repetition, on the vector's position in the batch, on the
+ * grid, on the alignment of x or of the rows or on the partition kind, and they are the out_vals
+ * glint_mat_pull_topk_batch reports for that row and vector. They are NOT glint_mat_pull_rows_dot's:
+ * products may be fused and the order differs. |score - exact| <= g * sum_c |row[c] * x[j][c]| with
+ * g = cols u / (1 - cols u), u = 2^-24 (Float) or 2^-53 (Double), for inputs whose products and partial sums
+ * are normal numbers or zero; what the matrix pipeline does with subnormal products is unspecified.
+ * Non-finite values propagate as IEEE arithmetic does (an inf * 0 or inf - inf among a row's terms gives
+ * NaN); the padding the kernel adds -- column tail, missing requests, missing vectors -- is 0 * 0 and never
+ * creates one. Only `cols` elements of a row are read, never the pitch padding.
+ * The slab, view, lock and sync rules are glint_mat_pull_rows_dot's.
+ * GLINT_EINVAL: a NULL or vector shard, an Int/Long shard, n < 0, n >= 2^31, q < 1,
+ * q > GLINT_DOT_MAX_QUERIES, a NULL x, NULL rows or NULL out with n > 0. n == 0 writes nothing and returns
+ * GLINT_OK. Every row is checked first: a row outside the partition returns GLINT_EOUTOFRANGE (its index in
+ * glint_shard_last_error) with nothing staged and nothing written to out. Staged to the device: rows and
+ * x; copied back: n * q values -- never n * cols. */
+/* Requests of one tile (tests size their cases by it; the answer never depends on it). */
+#define GLINT_DOT_BATCH_ROWS 128
+int glint_mat_pull_rows_dot_batch(glint_shard_t shard, const int64_t* rows, int64_t n, const void* x, int64_t q,
+                                  void* out);
+
 /* After GLINT_EOUTOFRANGE: index (within the failing call) of the first rejected record. */
 int glint_shard_last_error(glint_shard_t shard, int64_t* first_bad_record);
 
@@ -855,6 +889,15 @@ int glint_mat_pull_rows_gdot_dev(glint_shard_t shard, const int64_t* rows, int64
  * element. */
 int glint_mat_pull_rows_dot_dev(glint_shard_t shard, const int64_t* rows, int64_t n, const void* x, int64_t q,
                                 void* out, void* stream);
+
+/* glint_mat_pull_rows_dot_batch, device-resident: the same scores, stream-ordered on `stream` with no host
+ * synchronisation, one launch, no scratch. A row outside the partition answers q values of +0 -- stored as
+ * zeros and never computed, so an infinity or a NaN in x makes no NaN there -- and is reported by
+ * glint_shard_sync as the lowest such request index; every other request is answered. x is read by 16 B
+ * when it is 16-B aligned (and cols allow), else element by element: the same bits either way. out is
+ * written element by element. */
+int glint_mat_pull_rows_dot_batch_dev(glint_shard_t shard, const int64_t* rows, int64_t n, const void* x,
+                                      int64_t q, void* out, void* stream);
 
 /* glint_mat_pull_topk, device-resident: the same answer, stream-ordered on `stream` with no host
  * synchronisation: one scores launch and one launch per selection level. out_rows and out_vals must not
@@ -1315,7 +1358,8 @@ enum glint_kernel_id {
    * and one launch per selection level, so the sum is that pull's whole device time; a batched top-k pull
    * (glint_mat_pull_topk_batch*) records those launches once per pass of 64 queries. Also the one launch
    * of a row-pair dot pull (glint_mat_pull_pairs_dot*), recorded on its first shard only, and the one launch
-   * of a grouped row-dot pull (glint_mat_pull_rows_gdot*) */
+   * of a grouped row-dot pull (glint_mat_pull_rows_gdot*) and of a batched row dot pull
+   * (glint_mat_pull_rows_dot_batch*) */
   GLINT_K_PULL_ROWS_DOT = 11,
   /* the fold of a row axpy push (glint_mat_push_rows_axpy*): one launch per non-empty call. Also the fold
    * of a row-pair axpy push (glint_mat_push_pairs_axpy*), recorded on its destination shard only */
