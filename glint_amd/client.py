@@ -15,7 +15,8 @@ Mirrors the reference's client factory and asynchronous models, minus the Akka t
   rows crossing the link as float16 or bfloat16 (Float) or float32 (Double), rounded / widened on the shards
   (PartialMatrix.getRowsAs / updateRowsAs).
 * ``BigMatrix.pushAxpy`` -- an extension: rows += coefficients times caller vectors, the contribution
-  rows rebuilt on the shards (PartialMatrix.updateRowsAxpy) instead of sent.
+  rows rebuilt on the shards (PartialMatrix.updateRowsAxpy) instead of sent. ``BigMatrix.pushAxpyBatch`` is
+  its batched form for up to 1024 vectors, by matrix instructions (PartialMatrix.updateRowsAxpyBatch).
 * ``BigMatrix.pushAdagrad`` -- an extension: gradient rows summed per distinct row, then one Adagrad step
   of this matrix and of a second one that holds the accumulators, on the shards
   (PartialMatrix.updateRowsAdagrad).
@@ -230,6 +231,24 @@ class BigMatrix(_InitMixin):
         is (cols,) or (q, cols), ``coef`` (n,) (only with q == 1) or (n, q). Bucketed by partition as
         ``pushRows``; one PartialMatrix.updateRowsAxpy per non-empty partition, with its rows and
         coefficient rows in the caller's order and the same ``x``."""
+        return self._push_axpy(rows, coef, x, "updateRowsAxpy", deterministic=deterministic)
+
+    def pushAxpyBatch(self, rows, coef, x) -> bool:
+        """``pushAxpy`` for a batch of vectors (an extension), the write half of ``pullDotBatch``: Float and
+        Double matrices, ``x`` of shape (cols,) or (q, cols) with up to 1024 vectors, ``coef`` (n,) (only
+        with q == 1) or (n, q), no order flag. Bucketed exactly as ``pushAxpy``; one
+        PartialMatrix.updateRowsAxpyBatch per non-empty partition -- per distinct row the summed
+        coefficient row times ``x`` by matrix instructions, then one add -- each with the same ``x``. A row
+        lives in one partition and its result depends on its own records and ``x`` only, so the answer does
+        not depend on how the matrix is partitioned; it is deterministic, within updateRowsAxpyBatch's
+        bound, and NOT ``pushAxpy``'s bits. Use it above 64 vectors, where ``pushAxpy`` stops (on a shard 3 to 12 x faster than
+        ``ceil(q / 64)`` calls, measured on 2^17 x 512), and from 8 vectors up when rows repeat little; at
+        q = 1, or below 64 vectors on a list with very hot rows, ``pushAxpy`` is faster."""
+        return self._push_axpy(rows, coef, x, "updateRowsAxpyBatch")
+
+    def _push_axpy(self, rows, coef, x, call: str, **kw) -> bool:
+        """pushAxpy / pushAxpyBatch: one ``call`` per non-empty partition, rows and coefficient rows in the
+        caller's order."""
         rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
         dtype = self.shards[0].np_dtype
         x = np.ascontiguousarray(x, dtype=dtype)
@@ -239,7 +258,7 @@ class BigMatrix(_InitMixin):
         if coef.shape != (rows.size, q) and not (q == 1 and coef.shape == (rows.size,)):
             raise ValueError(f"coef: shape {coef.shape}, expected ({rows.size}, {q})")
         for _, sh, idx in _buckets(self, rows):
-            sh.updateRowsAxpy(rows[idx], coef[idx], x, deterministic=deterministic)
+            getattr(sh, call)(rows[idx], coef[idx], x, **kw)
         return True
 
     def pushGroups(self, rows, offsets, values, weights=None, deterministic: bool = False) -> bool:

@@ -1305,13 +1305,29 @@ inline int push_rows_as_args(const glint_shard* s, const void* rows, const void*
   return wire_supported(s->dtype, wire) ? GLINT_OK : GLINT_EINVAL;
 }
 
-// argument checks of glint_mat_push_rows_axpy / _dev: glint_mat_push_rows's, 1 to GLINT_AXPY_MAX_VECTORS
-// vectors, the three arrays present when there are records
+// argument checks of glint_mat_push_rows_axpy / _dev: glint_mat_push_rows's, 1 to `cap` vectors
+// (GLINT_AXPY_MAX_VECTORS), the three arrays present when there are records
 inline int push_axpy_args(const glint_shard* s, const void* rows, int64_t n, const void* coef, const void* x,
-                          int64_t q, int flags) {
+                          int64_t q, int flags, int64_t cap = GLINT_AXPY_MAX_VECTORS) {
   if (int rc = push_rows_args(s, rows, coef, n, flags)) return rc;
-  if (q < 1 || q > GLINT_AXPY_MAX_VECTORS || (n > 0 && !x)) return GLINT_EINVAL;
+  if (q < 1 || q > cap || (n > 0 && !x)) return GLINT_EINVAL;
   return GLINT_OK;
+}
+
+// argument checks of glint_mat_push_rows_axpy_batch / _dev: push_axpy_args up to
+// GLINT_AXPY_BATCH_MAX_VECTORS vectors on a Float or Double shard, and no flag at all
+inline int push_axpy_batch_args(const glint_shard* s, const void* rows, int64_t n, const void* coef, const void* x,
+                                int64_t q, int flags) {
+  if (!s || (s->dtype != GLINT_F32 && s->dtype != GLINT_F64) || flags != 0) return GLINT_EINVAL;
+  return push_axpy_args(s, rows, n, coef, x, q, flags, GLINT_AXPY_BATCH_MAX_VECTORS);
+}
+
+// the batched row axpy push has Float and Double instances only (push_axpy_batch_args has refused the rest)
+inline int push_rows_axpy_batch_any(glint_shard* s, const i64* rows, i64 n, const void* coef, const void* x, i64 q,
+                                    hipStream_t st) {
+  if (s->dtype == GLINT_F32) return push_rows_axpy_batch<float>(s, rows, n, coef, x, q, st);
+  if (s->dtype == GLINT_F64) return push_rows_axpy_batch<double>(s, rows, n, coef, x, q, st);
+  return GLINT_EINVAL;
 }
 
 // Whether shards w and h hold the same rows: one dtype, device, size and partition (kind, start, and index
@@ -1729,7 +1745,8 @@ extern "C" {
 
 // 0.17.0: glint_mat_pull_rows_wsum / _dev (weighted row-sum pull), glint_mat_pull_rows_gdot / _dev (grouped row dot)
 // 0.21.0: glint_mat_pull_rows_dot_batch / _dev (batched row dot pull)
-int glint_version(void) { return 2100; }
+// 0.22.0: glint_mat_push_rows_axpy_batch / _dev (batched row axpy push)
+int glint_version(void) { return 2200; }
 
 int glint_wire_supported(int dtype, int wire) { return wire_supported(dtype, wire) ? 1 : 0; }
 
@@ -2177,6 +2194,15 @@ int glint_mat_push_rows_axpy_dev(glint_shard_t s, const int64_t* rows, int64_t n
   if (args_rc == GLINT_OK && n == 0) return GLINT_OK;
   return dev_call(s, args_rc, stream, [&](hipStream_t st) -> int {
     GLINT_DISPATCH(s->dtype, push_rows_axpy, s, (const i64*)rows, n, coef, x, q, flags, st);
+  });
+}
+
+int glint_mat_push_rows_axpy_batch_dev(glint_shard_t s, const int64_t* rows, int64_t n, const void* coef,
+                                       const void* x, int64_t q, int flags, void* stream) {
+  const int args_rc = push_axpy_batch_args(s, rows, n, coef, x, q, flags);
+  if (args_rc == GLINT_OK && n == 0) return GLINT_OK;
+  return dev_call(s, args_rc, stream, [&](hipStream_t st) -> int {
+    return push_rows_axpy_batch_any(s, (const i64*)rows, n, coef, x, q, st);
   });
 }
 
@@ -3408,6 +3434,21 @@ int glint_mat_push_rows_axpy(glint_shard_t s, const int64_t* rows, int64_t n, co
                    0, [&](const Staged& st, hipStream_t stream, HostBack*) -> int {
                      GLINT_DISPATCH(s->dtype, push_rows_axpy, s, (const i64*)st.p[0], n, st.p[1], st.p[2], q,
                                     flags | kPushHostSequential, stream);
+                   });
+}
+
+// glint_mat_push_rows_axpy_batch: glint_mat_push_rows_axpy's check of every row and its staging -- rows, coef
+// and x in one block, every section 256-B aligned, nothing copied back -- around the batched push
+int glint_mat_push_rows_axpy_batch(glint_shard_t s, const int64_t* rows, int64_t n, const void* coef, const void* x,
+                                   int64_t q, int flags) {
+  if (int rc = push_axpy_batch_args(s, rows, n, coef, x, q, flags)) return rc;
+  if (n == 0) return GLINT_OK;
+  return host_call(s, s, {rows, nullptr, n}, false,
+                   {{rows, (size_t)n * 8},
+                    {coef, (size_t)n * (size_t)q * s->vsize},
+                    {x, (size_t)q * (size_t)s->part.cols * s->vsize}},
+                   0, [&](const Staged& st, hipStream_t stream, HostBack*) -> int {
+                     return push_rows_axpy_batch_any(s, (const i64*)st.p[0], n, st.p[1], st.p[2], q, stream);
                    });
 }
 

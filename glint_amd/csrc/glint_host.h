@@ -507,6 +507,9 @@ struct RowsFront {
   bool strict;  // message order kept: GLINT_PUSH_DETERMINISTIC, or a host call without GLINT_PUSH_UNORDERED
 };
 int rows_front(glint_shard* s, const i64* rows, i64 n, int flags, hipStream_t st, RowsFront* out);
+// Bytes of s->d_det that rows_front lays out for n records, a multiple of 256: a call that keeps scratch of
+// its own behind them grows s->d_det to the sum first and finds rows_front's pointers unmoved.
+size_t rows_front_bytes(i64 n);
 // row axpy push (glint_rowaxpy.hip), instantiated for the same V: row rows[i] += sum over j of
 // coef[i*q + j] * x[j] (coef n x q, x q x cols, dense, device pointers), in the order include/glint_gpu.h
 // fixes; rows outside the partition are skipped and recorded in err_of(s). The front end's launches and
@@ -514,6 +517,16 @@ int rows_front(glint_shard* s, const i64* rows, i64 n, int flags, hipStream_t st
 template <typename V>
 int push_rows_axpy(glint_shard* s, const i64* rows, i64 n, const void* coef, const void* x, i64 q, int flags,
                    hipStream_t st);
+// batched row axpy push (glint_rowaxpy_batch.hip), Float and Double only: push_rows_axpy's operands for
+// 1 <= q <= GLINT_AXPY_BATCH_MAX_VECTORS and no flags. Per distinct row the records' coefficient lines are
+// summed to +0 in push order, the sum times x is accumulated by matrix instructions and added to the row
+// once (the order include/glint_gpu.h fixes: NOT push_rows_axpy's bits); rows outside the partition are
+// skipped and recorded in err_of(s). Scratch in s->d_det: rows_front_bytes(n), then min(n, part.size) *
+// (q rounded up to 128 B) values; when it cannot be grown nothing is launched. The front end's launches,
+// the coefficient run-sum and the product on st, no host synchronisation.
+template <typename V>
+int push_rows_axpy_batch(glint_shard* s, const i64* rows, i64 n, const void* coef, const void* x, i64 q,
+                         hipStream_t st);
 // Adagrad row push (glint_rowadagrad.hip), instantiated for float and double: per distinct row of the
 // push, G = its gradient rows (grads n x cols, dense, device pointer) added to +0 in push order, then
 // state row += G * G and weights row -= (lr * G) / (sqrt(state row) + eps), in the order

@@ -162,6 +162,11 @@ __global__ __launch_bounds__(kTPB) void rows_fold_kernel(const u32* __restrict__
 // ---- host side ----------------------------------------------------------------------------------
 // The row pushes' shared front end (glint_host.h): scratch layout in s->d_det, then rows_prepare,
 // rs_sort and rows_runs on st. n > 0 and n < 2^32 - kSortTile (32-bit record indices and sort offsets).
+size_t rows_front_bytes(i64 n) {
+  const size_t ntiles = (size_t)((n + kSortTile - 1) / kSortTile);
+  return 4 * pad256((size_t)n * 4) + pad256((size_t)n * sizeof(uint2)) + 2 * pad256(ntiles * 256 * 4) + 1024 + 256;
+}
+
 int rows_front(glint_shard* s, const i64* rows, i64 n, int flags, hipStream_t st, RowsFront* out) {
   const u32 sentinel = (u32)s->part.size;
   int end_bit = 1;
@@ -173,8 +178,7 @@ int rows_front(glint_shard* s, const i64* rows, i64 n, int flags, hipStream_t st
   const u32 ntiles = (u32)((n + kSortTile - 1) / kSortTile);
   const size_t b_key = pad256((size_t)n * 4), b_items = pad256((size_t)n * sizeof(uint2));
   const size_t b_hist = pad256((size_t)ntiles * 256 * 4);
-  const size_t need = 4 * b_key + b_items + 2 * b_hist + 1024 + 256;
-  int rc = grow(&s->d_det, &s->det_bytes, need);
+  int rc = grow(&s->d_det, &s->det_bytes, rows_front_bytes(n));
   if (rc) return rc;
   char* base = (char*)s->d_det;
   u32* key0 = (u32*)base;

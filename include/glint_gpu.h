@@ -808,6 +808,47 @@ int glint_mat_pull_topk_batch(glint_shard_t shard, const void* x, int64_t q, int
 int glint_mat_pull_rows_dot_batch(glint_shard_t shard, const int64_t* rows, int64_t n, const void* x, int64_t q,
                                   void* out);
 
+/* Batched row axpy push (an extension): glint_mat_push_rows_axpy for a batch of vectors, the write half of
+ * glint_mat_pull_rows_dot_batch -- Float and Double matrix shards, 1 <= q <= GLINT_AXPY_BATCH_MAX_VECTORS,
+ * the same operands (rows with repeats, coef n x q, x q x cols, dense row-major) and no flags: the gradient
+ * rows += G * x of a two-tower or in-batch-softmax step whose n x q logits the batched pull computed.
+ * The push is linear in coef, so it is applied as one matrix product per distinct row, by matrix
+ * instructions over tiles of 128 distinct rows x 64 columns. For every distinct local row l the push names,
+ * with i0 < i1 < ... the m records whose row is l:
+ *   1. C[j] = (((+0 + coef[i0][j]) + coef[i1][j]) + ...) for every j: the records' coefficients summed in
+ *      push order, in the shard's type, from +0 (the optimizer pushes' run-sum convention);
+ *   2. t[c] = sum over j of C[j] * x[j][c], accumulated by matrix instructions from a zero accumulator in a
+ *      fixed order over ascending j, q padded up to a whole slab of 128 B with 0 * 0. The bits of t[c] are
+ *      a function of (type, q, C, column c of x) only: they never depend on n, on the row's position among
+ *      the distinct rows, on cols, on the grid or on the alignment of coef or x. Products may be fused;
+ *   3. data[l][c] = data[l][c] + t[c], one rounded add.
+ * A row that is not named is neither read nor written; only `cols` elements of a row are touched, never the
+ * pitch padding. No run is split and no atomic is used: the result is a function of the inputs only.
+ * These are NOT glint_mat_push_rows_axpy's bits (it rounds every product and adds record by record).
+ * |result - exact| <= g * (|row[c]| + sum_i sum_j |coef[i][j] * x[j][c]|) with g = (m + q) u / (1 - (m + q) u),
+ * u = 2^-24 (Float) or 2^-53 (Double) -- m - 1 adds in step 1, a q-term inner product in step 2, one add in
+ * step 3 -- for operands whose products and partial sums are normal numbers or zero; what the matrix
+ * pipeline does with subnormal products is unspecified. Non-finite values follow IEEE (0 * inf is NaN, as
+ * in glint_mat_push_rows_axpy); a non-finite coefficient of one row never reaches another row, and the
+ * padding never creates a NaN.
+ * Use it above GLINT_AXPY_MAX_VECTORS vectors, where glint_mat_push_rows_axpy cannot be called at all (3 to
+ * 12 x faster than ceil(q / 64) such calls over copied column blocks of coef), and from 8 vectors up when
+ * rows repeat little (measured on 2^17 x 512: 1.0 to 1.8 x at q = 8, 1.3 to 3.9 x at q = 64; 0.8 to 0.95 x
+ * at q = 1, where it is slower). A row named thousands of times has its coefficients summed by one wave per
+ * slice of q, strictly in order: on such a list the call is slower than the default (unordered)
+ * glint_mat_push_rows_axpy_dev below q = 64 and level with it there, and faster than the ordered one from
+ * q = 8 (DESIGN.md "Batched row axpy push" has the numbers).
+ * Device scratch: the row push's front end, then min(n, rows of the shard) * (q rounded up to a multiple of
+ * 128 / sizeof(V)) values; when it cannot be grown the call fails with GLINT_ENOMEM and applies nothing.
+ * Errors are glint_mat_push_rows_axpy's, but an Int/Long shard is GLINT_EINVAL, any flag is GLINT_EINVAL
+ * and the cap is GLINT_AXPY_BATCH_MAX_VECTORS. Every row is checked before anything is staged or applied: a
+ * row outside the partition returns GLINT_EOUTOFRANGE (its index in glint_shard_last_error). n == 0
+ * launches nothing and returns GLINT_OK. Staged to the device: rows, coef and x in one block; nothing is
+ * copied back. */
+#define GLINT_AXPY_BATCH_MAX_VECTORS 1024
+int glint_mat_push_rows_axpy_batch(glint_shard_t shard, const int64_t* rows, int64_t n, const void* coef,
+                                   const void* x, int64_t q, int flags);
+
 /* After GLINT_EOUTOFRANGE: index (within the failing call) of the first rejected record. */
 int glint_shard_last_error(glint_shard_t shard, int64_t* first_bad_record);
 
@@ -923,6 +964,15 @@ int glint_mat_pull_topk_batch_dev(glint_shard_t shard, const void* x, int64_t q,
  * element by element; coef element by element: the same bits either way. */
 int glint_mat_push_rows_axpy_dev(glint_shard_t shard, const int64_t* rows, int64_t n, const void* coef,
                                  const void* x, int64_t q, int flags, void* stream);
+
+/* glint_mat_push_rows_axpy_batch, device-resident: the same sums with the same bits, stream-ordered on
+ * `stream` with no host synchronisation: the front end's launches, one coefficient run-sum launch and one
+ * product launch. A row outside the partition is skipped -- its coefficients reach no row -- and is
+ * reported by glint_shard_sync (the lowest such record index); the other rows are applied. x is read by
+ * 16 B when it is 16-B aligned (and cols allow) and coef when it is (and q allows), else element by
+ * element: the same bits either way. */
+int glint_mat_push_rows_axpy_batch_dev(glint_shard_t shard, const int64_t* rows, int64_t n, const void* coef,
+                                       const void* x, int64_t q, int flags, void* stream);
 
 /* glint_mat_push_rows_adagrad, device-resident: the same step with the same bits, stream-ordered on
  * `stream` with no host synchronisation, after both shards' host-pointer work; both shards are marked for
@@ -1362,7 +1412,9 @@ enum glint_kernel_id {
    * (glint_mat_pull_rows_dot_batch*) */
   GLINT_K_PULL_ROWS_DOT = 11,
   /* the fold of a row axpy push (glint_mat_push_rows_axpy*): one launch per non-empty call. Also the fold
-   * of a row-pair axpy push (glint_mat_push_pairs_axpy*), recorded on its destination shard only */
+   * of a row-pair axpy push (glint_mat_push_pairs_axpy*), recorded on its destination shard only, and the
+   * two launches of a batched row axpy push (glint_mat_push_rows_axpy_batch*): its coefficient run-sum, then
+   * its product */
   GLINT_K_PUSH_ROWS_AXPY = 12,
   GLINT_K_COUNT = 13
 };
