@@ -28,6 +28,7 @@ GLINT_K_COUNT = 13
 GLINT_WIRE_F16, GLINT_WIRE_BF16, GLINT_WIRE_F32 = 0, 1, 2
 GLINT_DOT_MAX_QUERIES, GLINT_DOT_QUERY_TILE, GLINT_DOT_BATCH_ROWS = 1024, 4, 128
 GLINT_AXPY_MAX_VECTORS, GLINT_AXPY_BATCH_MAX_VECTORS = 64, 1024
+GLINT_MIX_BATCH_MAX_VECTORS, GLINT_MIX_BATCH_CHUNK, GLINT_MIX_BATCH_MAX_CHUNKS = 1024, 256, 64
 GLINT_ROWWISE_KEEP_STRIPS = 4
 GLINT_TOPK_MAX_K, GLINT_TOPK_MAX_QUERIES, GLINT_TOPK_TILE = 1024, 64, 4096
 GLINT_TOPK_BATCH_MAX_QUERIES, GLINT_TOPK_BATCH_ROWS = 1024, 128
@@ -73,6 +74,8 @@ SIGNATURES = {
     "glint_mat_pull_rows_dot_dev": (_I, [_P, _P, _I64, _P, _I64, _P, _P]),
     "glint_mat_pull_rows_dot_batch": (_I, [_P, _P, _I64, _P, _I64, _P]),
     "glint_mat_pull_rows_dot_batch_dev": (_I, [_P, _P, _I64, _P, _I64, _P, _P]),
+    "glint_mat_pull_rows_mix_batch": (_I, [_P, _P, _I64, _P, _I64, _P]),
+    "glint_mat_pull_rows_mix_batch_dev": (_I, [_P, _P, _I64, _P, _I64, _P, _P]),
     "glint_mat_push_rows_axpy": (_I, [_P, _P, _I64, _P, _P, _I64, _I]),
     "glint_mat_push_rows_axpy_dev": (_I, [_P, _P, _I64, _P, _P, _I64, _I, _P]),
     "glint_mat_push_rows_axpy_batch": (_I, [_P, _P, _I64, _P, _P, _I64, _I]),

@@ -521,6 +521,38 @@ class BigMatrix(_InitMixin):
             raise TypeError("pullDotBatch: x is required (pullDot has the self-dot)")
         return self._pull_dot(rows, x, "getRowsDotBatch")
 
+    def pullMixBatch(self, rows, coef) -> np.ndarray:
+        """The requested rows mixed by caller coefficients (an extension), the third product beside
+        ``pullDotBatch`` and ``pushAxpyBatch``: ``coef`` of shape (n, q) with up to 1024 vectors gives the
+        (q, cols) array ``coef.T @ table[rows]`` -- the gradient of ``pullDotBatch``'s scores with respect
+        to its vectors -- and ``coef`` of shape (n,) gives (cols,). Float and Double matrices. Bucketed by
+        partition as ``pullSum``, keeping the caller's order inside a bucket: one
+        PartialMatrix.getRowsMixBatch per partition that owns a requested row, sent that partition's lines
+        of ``coef``. Per answer element the partitions' partials are added in partition-index order,
+        starting from the first such partial (not from zero): ``pullSum``'s rule. The answer is
+        deterministic, but -- as ``pullSum``'s -- it depends on how the matrix is partitioned.
+
+        Bytes sent to a partition with n_p of the records: ``8 n_p + n_p * q * itemsize``; bytes back:
+        ``q * cols * itemsize`` -- against ``n_p * cols * itemsize`` back for ``pull`` of the rows. So use
+        it when q is well below n_p; with q near n_p pulling the rows moves no more."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        dtype = self.shards[0].np_dtype
+        if coef is None:
+            raise TypeError("pullMixBatch: coef is required")
+        coef = np.ascontiguousarray(coef, dtype=dtype)
+        if coef.shape == (rows.size,):
+            shape = (self.cols,)
+        elif coef.ndim == 2 and coef.shape[0] == rows.size and 1 <= coef.shape[1] <= 1024:
+            shape = (coef.shape[1], self.cols)
+        else:
+            raise ValueError(f"coef: shape {coef.shape}, expected ({rows.size},) or ({rows.size}, q) with "
+                             f"1 <= q <= 1024")
+        out = None
+        for _, sh, idx in _buckets(self, rows):
+            part = np.asarray(sh.getRowsMixBatch(rows[idx], coef[idx]), dtype=dtype)
+            out = part if out is None else out + part
+        return np.zeros(shape, dtype=dtype) if out is None else out
+
     def _pull_dot(self, rows, x, call: str) -> np.ndarray:
         """pullDot / pullDotBatch: one ``call`` per non-empty partition, scattered to the caller's order."""
         rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)

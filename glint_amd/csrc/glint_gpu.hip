@@ -1616,6 +1616,24 @@ inline int pull_rows_dot_batch_any(glint_shard* s, const i64* rows, i64 n, const
   return GLINT_EINVAL;
 }
 
+// argument checks of glint_mat_pull_rows_mix_batch / _dev: pull_dot_args' cases on a Float or Double shard
+// with coef in the place of x (the caps are one number, static-asserted in glint_rowmix_batch.hip), out
+// always present (an empty call writes its zeros) and coef present when there are requests
+inline int pull_mix_batch_args(const glint_shard* s, const void* rows, int64_t n, const void* coef, int64_t q,
+                               const void* out) {
+  if (!s || (s->dtype != GLINT_F32 && s->dtype != GLINT_F64) || !out) return GLINT_EINVAL;
+  if (int rc = pull_dot_args(s, rows, n, out, q, out)) return rc;
+  return n > 0 && !coef ? GLINT_EINVAL : GLINT_OK;
+}
+
+// the batched row mix pull has Float and Double instances only (pull_mix_batch_args has refused the rest)
+inline int pull_rows_mix_batch_any(glint_shard* s, const i64* rows, i64 n, const void* coef, i64 q, void* out,
+                                   hipStream_t st) {
+  if (s->dtype == GLINT_F32) return pull_rows_mix_batch<float>(s, rows, n, coef, q, out, st);
+  if (s->dtype == GLINT_F64) return pull_rows_mix_batch<double>(s, rows, n, coef, q, out, st);
+  return GLINT_EINVAL;
+}
+
 // argument check of the element-wise device-resident calls: a vector (matrix) shard, n >= 0
 inline int elem_args(const glint_shard* s, bool mat, int64_t n) {
   if (!s || n < 0) return GLINT_EINVAL;
@@ -1746,7 +1764,8 @@ extern "C" {
 // 0.17.0: glint_mat_pull_rows_wsum / _dev (weighted row-sum pull), glint_mat_pull_rows_gdot / _dev (grouped row dot)
 // 0.21.0: glint_mat_pull_rows_dot_batch / _dev (batched row dot pull)
 // 0.22.0: glint_mat_push_rows_axpy_batch / _dev (batched row axpy push)
-int glint_version(void) { return 2200; }
+// 0.23.0: glint_mat_pull_rows_mix_batch / _dev (batched row mix pull)
+int glint_version(void) { return 2300; }
 
 int glint_wire_supported(int dtype, int wire) { return wire_supported(dtype, wire) ? 1 : 0; }
 
@@ -2171,6 +2190,13 @@ int glint_mat_pull_rows_dot_batch_dev(glint_shard_t s, const int64_t* rows, int6
   if (args_rc == GLINT_OK && n == 0) return GLINT_OK;
   return dev_call(s, args_rc, stream, [&](hipStream_t st) -> int {
     return pull_rows_dot_batch_any(s, (const i64*)rows, n, x, q, out, st);
+  });
+}
+
+int glint_mat_pull_rows_mix_batch_dev(glint_shard_t s, const int64_t* rows, int64_t n, const void* coef, int64_t q,
+                                      void* out, void* stream) {
+  return dev_call(s, pull_mix_batch_args(s, rows, n, coef, q, out), stream, [&](hipStream_t st) -> int {
+    return pull_rows_mix_batch_any(s, (const i64*)rows, n, coef, q, out, st);
   });
 }
 
@@ -3385,6 +3411,26 @@ int glint_mat_pull_rows_dot_batch(glint_shard_t s, const int64_t* rows, int64_t 
                      if (int rc = grow(&s->d_det, &s->det_bytes, out_bytes)) return rc;
                      back[0] = {out, s->d_det, out_bytes};
                      return pull_rows_dot_batch_any(s, (const i64*)st.p[0], n, (const void*)st.p[1], q, s->d_det,
+                                                    stream);
+                   });
+}
+
+// glint_mat_pull_rows_mix_batch: every row is checked before anything is staged (a rejected call writes
+// nothing), then rows and coef go out in one block (coef 256-B aligned in it) with the q * cols answer behind
+// them -- the chunk partials take the shard's deterministic-path scratch -- and q * cols values come back,
+// never n * cols. An empty call writes its zeros on the host.
+int glint_mat_pull_rows_mix_batch(glint_shard_t s, const int64_t* rows, int64_t n, const void* coef, int64_t q,
+                                  void* out) {
+  if (int rc = pull_mix_batch_args(s, rows, n, coef, q, out)) return rc;
+  const size_t out_bytes = (size_t)q * (size_t)s->part.cols * s->vsize;
+  if (n == 0) {
+    std::memset(out, 0, out_bytes);
+    return GLINT_OK;
+  }
+  return host_call(s, s, {rows, nullptr, n}, false, {{rows, (size_t)n * 8}, {coef, (size_t)n * (size_t)q * s->vsize}},
+                   out_bytes, [&](const Staged& st, hipStream_t stream, HostBack* back) -> int {
+                     back[0] = {out, st.extra, out_bytes};
+                     return pull_rows_mix_batch_any(s, (const i64*)st.p[0], n, (const void*)st.p[1], q, st.extra,
                                                     stream);
                    });
 }

@@ -690,4 +690,13 @@ int pull_topk_batch(glint_shard* s, const void* x, i64 q, i64 k, i64* out_rows, 
 // err_of(s). One launch on st, no scratch, no host synchronisation.
 template <typename V>
 int pull_rows_dot_batch(glint_shard* s, const i64* rows, i64 n, const void* x, i64 q, void* out, hipStream_t st);
+// batched row mix pull (glint_rowmix_batch.hip), Float and Double only: out (q x cols, dense) = coef^T *
+// table[rows], coef n x q dense, 1 <= q <= GLINT_MIX_BATCH_MAX_VECTORS, device pointers, accumulated by
+// matrix instructions per chunk of mix_chunk_len(n) requests (glint_mix_plan.h) and the chunk partials added
+// in ascending order (the order include/glint_gpu.h fixes); rows outside the partition contribute nothing
+// and are recorded in err_of(s). With more than one chunk the partials take chunks * q * cols values at the
+// front of s->d_det -- out must not lie there -- grown before anything is launched. The product and the
+// reduce on st (n == 0: one launch that writes zeros), no host synchronisation.
+template <typename V>
+int pull_rows_mix_batch(glint_shard* s, const i64* rows, i64 n, const void* coef, i64 q, void* out, hipStream_t st);
 }  // namespace glint

@@ -849,6 +849,55 @@ int glint_mat_pull_rows_dot_batch(glint_shard_t shard, const int64_t* rows, int6
 int glint_mat_push_rows_axpy_batch(glint_shard_t shard, const int64_t* rows, int64_t n, const void* coef,
                                    const void* x, int64_t q, int flags);
 
+/* Batched row mix pull (an extension): the third product of the batched trio, the gradient of
+ * glint_mat_pull_rows_dot_batch's scores with respect to the caller's vectors -- Float and Double matrix
+ * shards, 1 <= q <= GLINT_MIX_BATCH_MAX_VECTORS:
+ *   rows  n global rows, repeats allowed, in the caller's order;
+ *   coef  n x q values of the shard's type, dense, request-major (glint_mat_push_rows_axpy_batch's operand);
+ *   out   q x cols values of the shard's type, dense: out[j*cols + c] = sum over i of coef[i*q + j] * row_i[c],
+ *         row_i the table row rows[i].
+ * It is computed as the matrix product it is, coef^T * table[rows], by matrix instructions over tiles of 64
+ * vectors x 128 columns. The product's K is the request list, and K is split into chunks of L consecutive
+ * requests:
+ *   L = GLINT_MIX_BATCH_CHUNK * 2^e, e the smallest integer >= 0 with ceil(n / L) <= GLINT_MIX_BATCH_MAX_CHUNKS.
+ * L is a function of n only -- never of q, cols, the device or the grid. Chunk k takes requests
+ * [k L, min(n, (k + 1) L)).
+ * Order. Per chunk, P_k[j][c] is one chain of matrix instructions from a zero accumulator over the chunk's
+ * requests in slabs of 32 (Float) / 16 (Double) requests ascending; within a slab, groups of 8 requests
+ * ascending; within a group Float takes the request pairs (t, t + 4), t = 0..3 ascending, one instruction
+ * each, and Double the request quadruples (t, t + 2, t + 4, t + 6), t = 0, 1; the last slab is padded with
+ * 0 * 0. Then out[j][c] = ((P_0 + P_1) + P_2) + ..., chunks ascending, starting from P_0 and not from zero.
+ * Nothing is atomic. The bits of out[j][c] are a function of (type, n, the sequence of (coef[i][j],
+ * row_i[c])) only: they never depend on q, on cols, on the positions j or c, on the alignment of coef, on
+ * the partition kind or on whether the call is the host or the device form. Products may be fused.
+ * |out - exact| <= g * sum_i |coef[i][j] * row_i[c]| with g = m u / (1 - m u), m = n + ceil(n / L) - 1,
+ * u = 2^-24 (Float) or 2^-53 (Double), for operands whose products and partial sums are normal numbers or
+ * zero; what the matrix pipeline does with subnormal products is unspecified. Non-finite values follow
+ * IEEE (inf * 0 is NaN); a non-finite coefficient or row element reaches column c of vector j only through
+ * its own request, and the padding is 0 * 0. Only `cols` elements of a row are read, never the pitch
+ * padding. coef must not overlap out.
+ * Device scratch: with more than one chunk, ceil(n / L) * q * cols values (at most
+ * GLINT_MIX_BATCH_MAX_CHUNKS * q * cols); when it cannot be grown the call fails with GLINT_ENOMEM and
+ * nothing is enqueued.
+ * GLINT_EINVAL: a NULL or vector shard, an Int/Long shard, n < 0, n >= 2^31, q < 1,
+ * q > GLINT_MIX_BATCH_MAX_VECTORS, NULL out, NULL coef or NULL rows with n > 0. n == 0 writes q x cols zeros
+ * (+0) and returns GLINT_OK. Every row is checked first: a row outside the partition returns
+ * GLINT_EOUTOFRANGE (its index in glint_shard_last_error) with nothing staged and nothing written to out.
+ * Staged to the device: rows and coef, n * 8 + n * q values; copied back: q * cols values -- never n * cols.
+ * Use it when q is well below n. Measured on 2^17 x 512 with 2^12 and 2^15 distinct rows: 5 to 139 x faster
+ * than glint_mat_pull_rows_wsum_dev over q groups of all n rows at every q from 1 to 1024; against
+ * glint_mat_pull_rows_dev followed by a matrix product outside the library, 1.5 to 5 x faster up to q = 256
+ * and 0.76 to 0.87 x at q = 1024 on a Float shard (DESIGN.md "Batched row mix pull" has the numbers). */
+#define GLINT_MIX_BATCH_MAX_VECTORS 1024
+/* Requests of the smallest K-chunk and the most chunks of a call: with n they fix the chunk boundaries and
+ * so the bits of the answer. (The guard lets tools/mix_batch_rate.py's comparison build other chunk sizes.) */
+#ifndef GLINT_MIX_BATCH_CHUNK
+#define GLINT_MIX_BATCH_CHUNK 256
+#endif
+#define GLINT_MIX_BATCH_MAX_CHUNKS 64
+int glint_mat_pull_rows_mix_batch(glint_shard_t shard, const int64_t* rows, int64_t n, const void* coef, int64_t q,
+                                  void* out);
+
 /* After GLINT_EOUTOFRANGE: index (within the failing call) of the first rejected record. */
 int glint_shard_last_error(glint_shard_t shard, int64_t* first_bad_record);
 
@@ -973,6 +1022,15 @@ int glint_mat_push_rows_axpy_dev(glint_shard_t shard, const int64_t* rows, int64
  * element: the same bits either way. */
 int glint_mat_push_rows_axpy_batch_dev(glint_shard_t shard, const int64_t* rows, int64_t n, const void* coef,
                                        const void* x, int64_t q, int flags, void* stream);
+
+/* glint_mat_pull_rows_mix_batch, device-resident: the same answer with the same bits, stream-ordered on
+ * `stream` with no host synchronisation: one product launch and, with more than one chunk, one reduce
+ * launch (n == 0: one launch that writes the zeros). A request whose row lies outside the partition
+ * contributes nothing, whatever coef holds for it, and is reported by glint_shard_sync (the lowest such
+ * record index). coef is read by 16 B when it is 16-B aligned (and q allows), else element by element: the
+ * same bits either way. */
+int glint_mat_pull_rows_mix_batch_dev(glint_shard_t shard, const int64_t* rows, int64_t n, const void* coef,
+                                      int64_t q, void* out, void* stream);
 
 /* glint_mat_push_rows_adagrad, device-resident: the same step with the same bits, stream-ordered on
  * `stream` with no host synchronisation, after both shards' host-pointer work; both shards are marked for
@@ -1401,7 +1459,8 @@ enum glint_kernel_id {
    * count kernel and the launches of its scan, so the sum is the pull's whole device time */
   GLINT_K_PULL_ROWS_SPARSE = 9,
   /* the grouped row-sum pull (glint_mat_pull_rows_sum*) and the weighted one (glint_mat_pull_rows_wsum*): one
-   * launch per call */
+   * launch per call. Also the launches of a batched row mix pull (glint_mat_pull_rows_mix_batch*), a dense
+   * weighted row sum: its product, then (with more than one chunk) its reduce */
   GLINT_K_PULL_ROWS_SUM = 10,
   /* the row dot-product pull (glint_mat_pull_rows_dot*): one launch per call. Also every launch of a top-k
    * pull (glint_mat_pull_topk*), which is a dot pull over every row plus a selection: its scores launch
