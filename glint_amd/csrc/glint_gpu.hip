@@ -1395,6 +1395,15 @@ inline int push_ftrl_args(const glint_shard* w, const glint_shard* s, const void
   return GLINT_OK;
 }
 
+// What the batched optimizer row pushes add to their optimizer's own argument check, whose result is step_rc:
+// that check is made with coef where grads stood, and then push_axpy_batch_args' 1 to
+// GLINT_AXPY_BATCH_MAX_VECTORS vectors, x present when there are records, and no flag at all.
+inline int push_step_batch_args(int step_rc, const void* x, int64_t n, int64_t q, int flags) {
+  if (step_rc) return step_rc;
+  if (flags != 0 || q < 1 || q > GLINT_AXPY_BATCH_MAX_VECTORS || (n > 0 && !x)) return GLINT_EINVAL;
+  return GLINT_OK;
+}
+
 // argument checks of glint_mat_push_rows_grouped / _dev: glint_mat_push_rows's shard, flags and record count,
 // a 31-bit group count, the arrays present when they have elements (grp_ptr always: it has g + 1); coef may
 // be NULL
@@ -1702,6 +1711,24 @@ int group_step_push_dev(glint_shard* w, glint_shard* s, int args_rc, const int64
   });
 }
 
+// A batched optimizer row push: its push_rows_*_batch<V> (glint_host.h), which all take the two shards, rows,
+// n, coef, x, q, the call's scalars S and the stream.
+template <typename... S>
+using StepBatchPush = int (*)(glint_shard*, glint_shard*, const i64*, i64, const void*, const void*, i64, S...,
+                              hipStream_t);
+
+// The device-resident entry of a batched optimizer row push whose argument check gave args_rc (step_push_dev's
+// frame): pf for Float weights, pd for Double, with the scalars k.
+template <typename... S>
+int step_batch_push_dev(glint_shard* w, glint_shard* s, int args_rc, const int64_t* rows, int64_t n, const void* coef,
+                        const void* x, int64_t q, void* stream, StepBatchPush<S...> pf, StepBatchPush<S...> pd,
+                        S... k) {
+  if (args_rc == GLINT_OK && n == 0) return GLINT_OK;
+  return dev_call2(w, s, args_rc, stream, [&](hipStream_t st) -> int {
+    return (w->dtype == GLINT_F64 ? pd : pf)(w, s, (const i64*)rows, n, coef, x, q, k..., st);
+  });
+}
+
 // What a host-pointer call does first, under the shard's lock: a slab with views is refused, the open
 // ring batch is launched and the shard's stream is ordered after the last device-resident call's.
 enum class HostEntry { Order, FlushOrder, OrderFlush };  // (Order: the call may append to the open batch)
@@ -1765,7 +1792,8 @@ extern "C" {
 // 0.21.0: glint_mat_pull_rows_dot_batch / _dev (batched row dot pull)
 // 0.22.0: glint_mat_push_rows_axpy_batch / _dev (batched row axpy push)
 // 0.23.0: glint_mat_pull_rows_mix_batch / _dev (batched row mix pull)
-int glint_version(void) { return 2300; }
+// 0.24.0: glint_mat_push_rows_adagrad_batch / _adam_batch / _ftrl_batch / _dev (batched optimizer row pushes)
+int glint_version(void) { return 2400; }
 
 int glint_wire_supported(int dtype, int wire) { return wire_supported(dtype, wire) ? 1 : 0; }
 
@@ -2281,6 +2309,31 @@ int glint_mat_push_rows_ftrl_dev(glint_shard_t weights, glint_shard_t state, con
                                  int64_t n, double alpha, double beta, double l1, double l2, void* stream) {
   return step_push_dev(weights, state, push_ftrl_args(weights, state, rows, grads, n, alpha, beta, l1, l2), rows, grads,
                        n, stream, push_rows_ftrl<float>, push_rows_ftrl<double>, alpha, beta, l1, l2);
+}
+
+int glint_mat_push_rows_adagrad_batch_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows, int64_t n,
+                                          const void* coef, const void* x, int64_t q, double lr, double eps, int flags,
+                                          void* stream) {
+  const int step_rc = push_adagrad_args(weights, state, rows, coef, n, lr, eps);
+  return step_batch_push_dev(weights, state, push_step_batch_args(step_rc, x, n, q, flags), rows, n, coef, x, q, stream,
+                             push_rows_adagrad_batch<float>, push_rows_adagrad_batch<double>, lr, eps);
+}
+
+int glint_mat_push_rows_adam_batch_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows, int64_t n,
+                                       const void* coef, const void* x, int64_t q, double lr, double beta1,
+                                       double beta2, double eps, int64_t step, int flags, void* stream) {
+  const int step_rc = push_adam_args(weights, state, rows, coef, n, lr, beta1, beta2, eps, step);
+  return step_batch_push_dev(weights, state, push_step_batch_args(step_rc, x, n, q, flags), rows, n, coef, x, q, stream,
+                             push_rows_adam_batch<float>, push_rows_adam_batch<double>, lr, beta1, beta2, eps,
+                             (i64)step);
+}
+
+int glint_mat_push_rows_ftrl_batch_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows, int64_t n,
+                                       const void* coef, const void* x, int64_t q, double alpha, double beta,
+                                       double l1, double l2, int flags, void* stream) {
+  const int step_rc = push_ftrl_args(weights, state, rows, coef, n, alpha, beta, l1, l2);
+  return step_batch_push_dev(weights, state, push_step_batch_args(step_rc, x, n, q, flags), rows, n, coef, x, q, stream,
+                             push_rows_ftrl_batch<float>, push_rows_ftrl_batch<double>, alpha, beta, l1, l2);
 }
 
 int glint_mat_push_rows_adagrad_grouped_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows, int64_t n,
@@ -3141,6 +3194,27 @@ int group_step_push_host(glint_shard* w, glint_shard* s, int args_rc, const int6
                    });
 }
 
+// The host-pointer entry of a batched optimizer row push (glint_mat_push_rows_adagrad_batch, _adam_batch,
+// _ftrl_batch) whose argument check gave args_rc: step_push_host's locks, row check (against the weights
+// shard, before anything is staged: a rejected message changes neither shard) and stream order, around
+// glint_mat_push_rows_axpy_batch's staging -- rows, coef and x in one block, every section 256-B aligned,
+// n * 8 bytes + n * q + q * cols values, never n * cols. The call ends synchronised. pf, pd and k as
+// step_batch_push_dev's.
+template <typename... S>
+int step_batch_push_host(glint_shard* w, glint_shard* s, int args_rc, const int64_t* rows, int64_t n, const void* coef,
+                         const void* x, int64_t q, StepBatchPush<S...> pf, StepBatchPush<S...> pd, S... k) {
+  if (args_rc) return args_rc;
+  if (n == 0) return GLINT_OK;
+  return host_call(w, s, {rows, nullptr, n}, false,
+                   {{rows, (size_t)n * 8},
+                    {coef, (size_t)n * (size_t)q * w->vsize},
+                    {x, (size_t)q * (size_t)w->part.cols * w->vsize}},
+                   0, [&](const Staged& st, hipStream_t stream, HostBack*) -> int {
+                     return (w->dtype == GLINT_F64 ? pd : pf)(w, s, (const i64*)st.p[0], n, st.p[1], st.p[2], q, k...,
+                                                              stream);
+                   });
+}
+
 int host_push(glint_shard* s, bool mat, const int64_t* keys, const int32_t* cols, const void* vals, int64_t n,
               int flags) {
   if (n < 0 || (n > 0 && (!keys || !vals || (mat && !cols)))) return GLINT_EINVAL;
@@ -3574,6 +3648,30 @@ int glint_mat_push_rows_ftrl(glint_shard_t weights, glint_shard_t state, const i
                              int64_t n, double alpha, double beta, double l1, double l2) {
   return step_push_host(weights, state, push_ftrl_args(weights, state, rows, grads, n, alpha, beta, l1, l2), rows,
                         grads, n, push_rows_ftrl<float>, push_rows_ftrl<double>, alpha, beta, l1, l2);
+}
+
+int glint_mat_push_rows_adagrad_batch(glint_shard_t weights, glint_shard_t state, const int64_t* rows, int64_t n,
+                                      const void* coef, const void* x, int64_t q, double lr, double eps, int flags) {
+  const int step_rc = push_adagrad_args(weights, state, rows, coef, n, lr, eps);
+  return step_batch_push_host(weights, state, push_step_batch_args(step_rc, x, n, q, flags), rows, n, coef, x, q,
+                              push_rows_adagrad_batch<float>, push_rows_adagrad_batch<double>, lr, eps);
+}
+
+int glint_mat_push_rows_adam_batch(glint_shard_t weights, glint_shard_t state, const int64_t* rows, int64_t n,
+                                   const void* coef, const void* x, int64_t q, double lr, double beta1, double beta2,
+                                   double eps, int64_t step, int flags) {
+  const int step_rc = push_adam_args(weights, state, rows, coef, n, lr, beta1, beta2, eps, step);
+  return step_batch_push_host(weights, state, push_step_batch_args(step_rc, x, n, q, flags), rows, n, coef, x, q,
+                              push_rows_adam_batch<float>, push_rows_adam_batch<double>, lr, beta1, beta2, eps,
+                              (i64)step);
+}
+
+int glint_mat_push_rows_ftrl_batch(glint_shard_t weights, glint_shard_t state, const int64_t* rows, int64_t n,
+                                   const void* coef, const void* x, int64_t q, double alpha, double beta, double l1,
+                                   double l2, int flags) {
+  const int step_rc = push_ftrl_args(weights, state, rows, coef, n, alpha, beta, l1, l2);
+  return step_batch_push_host(weights, state, push_step_batch_args(step_rc, x, n, q, flags), rows, n, coef, x, q,
+                              push_rows_ftrl_batch<float>, push_rows_ftrl_batch<double>, alpha, beta, l1, l2);
 }
 
 int glint_mat_push_rows_adagrad_grouped(glint_shard_t weights, glint_shard_t state, const int64_t* rows, int64_t n,

@@ -527,6 +527,37 @@ int push_rows_axpy(glint_shard* s, const i64* rows, i64 n, const void* coef, con
 template <typename V>
 int push_rows_axpy_batch(glint_shard* s, const i64* rows, i64 n, const void* coef, const void* x, i64 q,
                          hipStream_t st);
+// The stages a batched push runs in front of its product (glint_rowaxpy_batch.hip), instantiated for float
+// and double: the scratch above grown, the front end (strict) and the coefficient run-sum on st. `cs` is
+// the summed coefficient lines, `most` lines of `qp` values, line i that of item i of `f`; all of it points
+// into s->d_det and is valid until the shard's next call that uses that scratch.
+struct AxpyBatchFront {
+  RowsFront f;
+  const void* cs;
+  i64 qp;    // q rounded up to a whole slab of K
+  i64 most;  // min(n, part.size): the distinct rows, at most
+};
+template <typename V>
+int axpy_batch_front(glint_shard* s, const i64* rows, i64 n, const void* coef, i64 q, hipStream_t st,
+                     AxpyBatchFront* out);
+// batched optimizer row pushes (glint_rowstep_batch.hip), instantiated for float and double:
+// push_rows_axpy_batch's rows, coef, x and q, and the state shard and scalars of push_rows_adagrad, _adam
+// and _ftrl. Per distinct row, G = push_rows_axpy_batch's product with its bits, then one step of
+// glint_steps.h's policy with that G in place of the summed gradient, state parts stored first and the
+// weights after them. Rows outside the partition are skipped and recorded in err_of(weights). Scratch,
+// error state and profile are the weights shard's: axpy_batch_front's launches, then the stepping product
+// (counted under GLINT_K_PUSH_ROWS as every optimizer fold) on st, no host synchronisation; under both
+// shards' locks.
+template <typename V>
+int push_rows_adagrad_batch(glint_shard* weights, glint_shard* state, const i64* rows, i64 n, const void* coef,
+                            const void* x, i64 q, double lr, double eps, hipStream_t st);
+template <typename V>
+int push_rows_adam_batch(glint_shard* weights, glint_shard* state, const i64* rows, i64 n, const void* coef,
+                         const void* x, i64 q, double lr, double beta1, double beta2, double eps, i64 step,
+                         hipStream_t st);
+template <typename V>
+int push_rows_ftrl_batch(glint_shard* weights, glint_shard* state, const i64* rows, i64 n, const void* coef,
+                         const void* x, i64 q, double alpha, double beta, double l1, double l2, hipStream_t st);
 // Adagrad row push (glint_rowadagrad.hip), instantiated for float and double: per distinct row of the
 // push, G = its gradient rows (grads n x cols, dense, device pointer) added to +0 in push order, then
 // state row += G * G and weights row -= (lr * G) / (sqrt(state row) + eps), in the order

@@ -28,10 +28,8 @@
 // items, so a load or store instruction of the epilogue covers 32 (Float) / 16 (Double) consecutive columns
 // of one row, 128 B. The rows' elements are loaded in front of the last slab's matrix instructions, so the
 // adds do not wait on HBM behind them.
-#include "glint_device.h"
-#include "glint_host.h"
-#include "glint_rowstep.h"  // run_sum
-#include "glint_slab.h"     // the slab geometry of operand A and tb_chunk
+#include "glint_axpy_batch.h"  // the product: Xb, AbMma, ab_product
+#include "glint_rowstep.h"     // run_sum
 
 namespace glint {
 
@@ -67,147 +65,11 @@ __global__ __launch_bounds__(kTPB) void axpy_coef_sum_kernel(const u32* __restri
 }
 
 // ---- stage 3: the product and the add -----------------------------------------------------------
-// Operand B's part of a slab: KS lines (one per vector) of kTbPass columns at a pitch of 72 elements,
-// behind operand A's 128 lines. Both types fill the 64 lines' worth of LDS the batched pulls' vectors take.
-template <typename V> struct Xb {
-  static constexpr int kLineBytes = kTbPass * (int)sizeof(V);          // 256 B Float, 512 B Double
-  static constexpr int kPitch = kLineBytes + kLineBytes / 8;           // 288 B Float, 576 B Double
-  static constexpr int KS = kTbLineBytes / (int)sizeof(V);             // lines: vectors of a slab
-  static constexpr int kChunks = kLineBytes / 16;                      // 16-B chunks of a line
-  static constexpr int kLinesPerTrip = kTPB / kChunks;                 // lines the workgroup stages at once
-  static constexpr int kStage = KS / kLinesPerTrip;                    // chunks a thread stages per slab
-  static constexpr int kBase = kTbRows * kTbLinePitch;                 // behind operand A
-  static_assert(kBase + KS * kPitch <= kTbSlabBytes, "operand B fits where the pulls keep their vectors");
-  static_assert(kStage * kLinesPerTrip == KS && kPitch % 16 == 0, "whole trips of 16-B aligned chunks");
-};
-constexpr int kAbStageA = kTbRows / 32;  // chunks of operand A a thread stages per slab
-
-// The wave's accumulators, the matrix instructions of one slab, the early loads of the rows' elements and
-// the add and store. `local` is the tile's 128 local rows (-1: no such item); c0 the pass's first column.
-template <typename V> struct AbMma;
-
-template <> struct AbMma<float> {
-  TbF16 acc[2];   // the wave's 32 items x columns [32 b, 32 b + 32)
-  float row[2][16];
-  __device__ __forceinline__ void clear() {
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) acc[b][v] = 0.f;
-  }
-  // step (g, t): k = 8 g + 4 (lane / 32) + t of the slab, for A by its 16-B reads, for B by the line
-  __device__ __forceinline__ void slab(const unsigned char* buf, int wave, int lane) {
-    const int l = lane & 31, h = lane >> 5;
-    const unsigned char* pa = buf + (32 * wave + l) * kTbLinePitch + h * 16;
-    const unsigned char* pb = buf + Xb<float>::kBase + 4 * h * Xb<float>::kPitch + l * 4;
-#pragma unroll
-    for (int g = 0; g < kTbLineBytes / 32; ++g) {
-      const TbF4 a = *reinterpret_cast<const TbF4*>(pa + g * 32);
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const float b0 = *reinterpret_cast<const float*>(pb + (8 * g + t) * Xb<float>::kPitch);
-        const float b1 = *reinterpret_cast<const float*>(pb + (8 * g + t) * Xb<float>::kPitch + 128);
-        acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t], b0, acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t], b1, acc[1], 0, 0, 0);
-      }
-    }
-  }
-  // register v of a lane: item 8 (v / 4) + 4 (lane / 32) + v % 4 of the wave's 32, column lane % 32
-  __device__ __forceinline__ void load(const float* data, i64 pitch, const int* local, i64 cols, i64 c0, int wave,
-                                       int lane) {
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-      const int l = local[32 * wave + 8 * (v >> 2) + 4 * (lane >> 5) + (v & 3)];
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        const i64 c = c0 + 32 * b + (lane & 31);
-        row[b][v] = (l >= 0 && c < cols) ? data[(i64)l * pitch + c] : 0.f;
-      }
-    }
-  }
-  __device__ __forceinline__ void store(float* data, i64 pitch, const int* local, i64 cols, i64 c0, int wave,
-                                        int lane) const {
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-      const int l = local[32 * wave + 8 * (v >> 2) + 4 * (lane >> 5) + (v & 3)];
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        const i64 c = c0 + 32 * b + (lane & 31);
-        if (l >= 0 && c < cols) data[(i64)l * pitch + c] = vadd(row[b][v], acc[b][v]);
-      }
-    }
-  }
-};
-
-template <> struct AbMma<double> {
-  TbD4 acc[2][4];  // items [16 m, 16 m + 16) of the wave's 32 x columns [16 b, 16 b + 16)
-  double row[2][4][4];
-  __device__ __forceinline__ void clear() {
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int b = 0; b < 4; ++b)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) acc[m][b][v] = 0.0;
-  }
-  // step (g, t): k = 8 g + 2 (lane / 16) + t of the slab
-  __device__ __forceinline__ void slab(const unsigned char* buf, int wave, int lane) {
-    const int l = lane & 15, kq = lane >> 4;
-    const unsigned char* pa = buf + (32 * wave + l) * kTbLinePitch + kq * 16;
-    const unsigned char* pb = buf + Xb<double>::kBase + 2 * kq * Xb<double>::kPitch + l * 8;
-#pragma unroll
-    for (int g = 0; g < kTbLineBytes / 64; ++g) {
-      TbD2 a[2];
-#pragma unroll
-      for (int m = 0; m < 2; ++m) a[m] = *reinterpret_cast<const TbD2*>(pa + 16 * m * kTbLinePitch + g * 64);
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        double b[4];
-#pragma unroll
-        for (int n = 0; n < 4; ++n)
-          b[n] = *reinterpret_cast<const double*>(pb + (8 * g + t) * Xb<double>::kPitch + 128 * n);
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-          for (int n = 0; n < 4; ++n)
-            acc[m][n] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[m][t], b[n], acc[m][n], 0, 0, 0);
-      }
-    }
-  }
-  // register v of a lane: item 4 v + lane / 16 of the block of 16, column lane % 16
-  __device__ __forceinline__ void load(const double* data, i64 pitch, const int* local, i64 cols, i64 c0, int wave,
-                                       int lane) {
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        const int l = local[32 * wave + 16 * m + 4 * v + (lane >> 4)];
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-          const i64 c = c0 + 16 * b + (lane & 15);
-          row[m][b][v] = (l >= 0 && c < cols) ? data[(i64)l * pitch + c] : 0.0;
-        }
-      }
-  }
-  __device__ __forceinline__ void store(double* data, i64 pitch, const int* local, i64 cols, i64 c0, int wave,
-                                        int lane) const {
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        const int l = local[32 * wave + 16 * m + 4 * v + (lane >> 4)];
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-          const i64 c = c0 + 16 * b + (lane & 15);
-          if (l >= 0 && c < cols) data[(i64)l * pitch + c] = vadd(row[m][b][v], acc[m][b][v]);
-        }
-      }
-  }
-};
-
 // Workgroup b: items [128 (b / npass), + 128) against columns [64 (b % npass), + 64). The grid is sized
 // from n; a tile at or past *nitems returns at once. An item's row is this workgroup's alone for the
-// pass's columns: items are distinct rows.
+// pass's columns: items are distinct rows. The product is glint_axpy_batch.h's; `local` is the tile's 128
+// local rows (-1: no such item). The rows' elements are loaded in front of the last slab's matrix
+// instructions, so the adds do not wait on HBM behind them.
 template <typename V>
 __global__ __launch_bounds__(kTPB) void rows_axpy_batch_kernel(const u32* __restrict__ key,
                                                                const uint2* __restrict__ items,
@@ -215,8 +77,7 @@ __global__ __launch_bounds__(kTPB) void rows_axpy_batch_kernel(const u32* __rest
                                                                const V* __restrict__ cs, int qp,
                                                                const V* __restrict__ x, int q, int npass, int xwide,
                                                                V* data, PartDesc part) {
-  constexpr int E = (int)(16 / sizeof(V));
-  typedef Xb<V> B;
+  typedef AbMma<V> M;
   __shared__ __attribute__((aligned(16))) unsigned char lds[2][kTbSlabBytes];
   __shared__ int local[kTbRows];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -227,64 +88,31 @@ __global__ __launch_bounds__(kTPB) void rows_axpy_batch_kernel(const u32* __rest
   if (i0 >= nit) return;
   const i64 c0 = (i64)(blockIdx.x % (unsigned)npass) * kTbPass;
   if (tid < kTbRows) local[tid] = i0 + tid < nit ? (int)key[items[i0 + tid].x] : -1;
-  // staging. A: chunk `ch` of lines ln + 32 p of Cs, a line past nitems zero-filled and never loaded.
-  // B: chunk `bch` (columns c0 + E bch ..) of the vectors bln + kLinesPerTrip p of the slab.
-  const int ch = tid & 7, ln = tid >> 3;
-  const int bch = tid % B::kChunks, bln = tid / B::kChunks;
-  const V* srca[kAbStageA];
-  bool live[kAbStageA];
+  M mma;
+  V row[kAbElems];
+  ab_product<V>(mma, lds, cs, qp, x, q, xwide, cols, c0, i0, nit, tid, wave, lane, [&]() {
 #pragma unroll
-  for (int p = 0; p < kAbStageA; ++p) {
-    live[p] = i0 + ln + 32 * p < nit;
-    srca[p] = cs + (i64)(live[p] ? i0 + ln + 32 * p : i0) * qp;
-  }
-  TbU4 sa[kAbStageA], sb[B::kStage];
-  auto fetch = [&](int k0) {
-#pragma unroll
-    for (int p = 0; p < kAbStageA; ++p) sa[p] = tb_chunk<V>(srca[p], k0 + ch * E, qp, live[p], true);
-#pragma unroll
-    for (int p = 0; p < B::kStage; ++p) {
-      const int j = k0 + bln + B::kLinesPerTrip * p;
-      sb[p] = tb_chunk<V>(x + (i64)(j < q ? j : 0) * cols, c0 + bch * E, cols, j < q, xwide != 0);
+    for (int i = 0; i < kAbElems; ++i) {
+      const int l = local[M::item(i, wave, lane)];
+      const i64 c = c0 + M::col(i, lane);
+      row[i] = (l >= 0 && c < cols) ? data[(i64)l * part.pitch + c] : V(0);
     }
-  };
-  auto stash = [&](int b) {
+  });
 #pragma unroll
-    for (int p = 0; p < kAbStageA; ++p)
-      *reinterpret_cast<TbU4*>(&lds[b][(ln + 32 * p) * kTbLinePitch + ch * 16]) = sa[p];
-#pragma unroll
-    for (int p = 0; p < B::kStage; ++p)
-      *reinterpret_cast<TbU4*>(&lds[b][B::kBase + (bln + B::kLinesPerTrip * p) * B::kPitch + bch * 16]) = sb[p];
-  };
-  const int nslab = qp / B::KS;
-  AbMma<V> mma;
-  mma.clear();
-  fetch(0);
-  stash(0);
-  __syncthreads();  // also publishes `local`
-  for (int s = 0; s + 1 < nslab; ++s) {
-    fetch((s + 1) * B::KS);
-    mma.slab(lds[s & 1], wave, lane);
-    // slab s + 1's buffer was last read in iteration s - 1, in front of that iteration's barrier
-    stash((s + 1) & 1);
-    __syncthreads();
+  for (int i = 0; i < kAbElems; ++i) {
+    const int l = local[M::item(i, wave, lane)];
+    const i64 c = c0 + M::col(i, lane);
+    if (l >= 0 && c < cols) data[(i64)l * part.pitch + c] = vadd(row[i], mma.get(i));
   }
-  mma.load(data, part.pitch, local, cols, c0, wave, lane);  // in flight over the last slab's instructions
-  mma.slab(lds[(nslab - 1) & 1], wave, lane);
-  mma.store(data, part.pitch, local, cols, c0, wave, lane);
 }
 
 // ---- host side ----------------------------------------------------------------------------------
-// Enqueues the batched row axpy push on st (no host synchronisation): the front end's launches, the
-// coefficient run-sum and the product, the last two counted under GLINT_K_PUSH_ROWS_AXPY. rows, coef and x
-// are device pointers. Cs lies in s->d_det behind the front end's layout (rows_front_bytes):
-// min(n, part.size) * qp values; the scratch is grown before anything is launched. Under the shard's lock.
+// The first two stages of a batched push of n records on st: s->d_det is grown to hold Cs behind the front
+// end's layout (rows_front_bytes) -- min(n, part.size) * qp values -- before anything is launched, then the
+// front end's launches and the coefficient run-sum, counted under GLINT_K_PUSH_ROWS_AXPY.
 template <typename V>
-int push_rows_axpy_batch(glint_shard* s, const i64* rows, i64 n, const void* coef, const void* x, i64 q,
-                         hipStream_t st) {
-  if (n <= 0) return GLINT_OK;
-  if (!rows || !coef || !x || q < 1 || q > GLINT_AXPY_BATCH_MAX_VECTORS) return GLINT_EINVAL;
-  if (n >= ((i64)1 << 32) - kSortTile) return GLINT_EINVAL;  // 32-bit record indices and sort offsets
+int axpy_batch_front(glint_shard* s, const i64* rows, i64 n, const void* coef, i64 q, hipStream_t st,
+                     AxpyBatchFront* out) {
   constexpr int KS = Xb<V>::KS;
   const i64 qp = (q + KS - 1) / KS * KS;
   const i64 most = n < (i64)s->part.size ? n : (i64)s->part.size;  // distinct rows, at most
@@ -299,13 +127,30 @@ int push_rows_axpy_batch(glint_shard* s, const i64* rows, i64 n, const void* coe
   const unsigned gs = grid_for(most * row_slices<V>(qp, c16), kTPB / 64, (i64)s->cus * 8);
   HIPCHK(launch_k(s, GLINT_K_PUSH_ROWS_AXPY, c16 ? axpy_coef_sum_kernel<V, true> : axpy_coef_sum_kernel<V, false>, gs,
                   kTPB, st, f.idx, f.items, f.nitems, (const V*)coef, (int)q, (int)qp, cs));
+  *out = {f, cs, qp, most};
+  return GLINT_OK;
+}
+
+template int axpy_batch_front<float>(glint_shard*, const i64*, i64, const void*, i64, hipStream_t, AxpyBatchFront*);
+template int axpy_batch_front<double>(glint_shard*, const i64*, i64, const void*, i64, hipStream_t, AxpyBatchFront*);
+
+// Enqueues the batched row axpy push on st (no host synchronisation): axpy_batch_front's launches and the
+// product, counted under GLINT_K_PUSH_ROWS_AXPY. rows, coef and x are device pointers. Under the shard's lock.
+template <typename V>
+int push_rows_axpy_batch(glint_shard* s, const i64* rows, i64 n, const void* coef, const void* x, i64 q,
+                         hipStream_t st) {
+  if (n <= 0) return GLINT_OK;
+  if (!rows || !coef || !x || q < 1 || q > GLINT_AXPY_BATCH_MAX_VECTORS) return GLINT_EINVAL;
+  if (n >= ((i64)1 << 32) - kSortTile) return GLINT_EINVAL;  // 32-bit record indices and sort offsets
+  AxpyBatchFront a;
+  if (int rc = axpy_batch_front<V>(s, rows, n, coef, q, st, &a)) return rc;
   const i64 cols = s->part.cols;
   const int xw = (cols * (i64)sizeof(V)) % 16 == 0 && aligned(x, 16);
-  const i64 npass = (cols + kTbPass - 1) / kTbPass;
-  const i64 grid = (most + kTbRows - 1) / kTbRows * npass;
-  if (grid >= ((i64)1 << 31)) return GLINT_EINVAL;
-  HIPCHK(launch_k(s, GLINT_K_PUSH_ROWS_AXPY, rows_axpy_batch_kernel<V>, (unsigned)grid, kTPB, st, f.key, f.items,
-                  f.nitems, (const V*)cs, (int)qp, (const V*)x, (int)q, (int)npass, xw, (V*)s->data, s->part));
+  i64 npass;
+  const i64 grid = ab_grid(a.most, cols, &npass);
+  if (!grid) return GLINT_EINVAL;
+  HIPCHK(launch_k(s, GLINT_K_PUSH_ROWS_AXPY, rows_axpy_batch_kernel<V>, (unsigned)grid, kTPB, st, a.f.key, a.f.items,
+                  a.f.nitems, (const V*)a.cs, (int)a.qp, (const V*)x, (int)q, (int)npass, xw, (V*)s->data, s->part));
   return GLINT_OK;
 }
 

@@ -620,23 +620,31 @@ class PartialMatrix(_Shard):
     def _axpy_call(self, fn: str, cap: int, rows, coef, x, flags: int, sync: bool) -> bool:
         """updateRowsAxpy / updateRowsAxpyBatch: the C call ``fn``, or ``fn + "_dev"`` for device tensors,
         for up to ``cap`` vectors."""
+        dev, args, _keep = self._axpy_args(rows, coef, x, cap)
+        if dev:
+            rc = getattr(self.lib, fn + "_dev")(self.handle, *args, flags, self._stream_of(rows))
+            self._dev_done(rc, rows, sync)
+            return True
+        check(getattr(self.lib, fn)(self.handle, *args, flags), self.handle)
+        return True
+
+    def _axpy_args(self, rows, coef, x, cap: int) -> tuple:
+        """What the axpy pushes and the batched optimizer pushes validate before any call, and what they pass:
+        ``rows``, ``coef`` and ``x`` are all device tensors or all host arrays, of the shard's type and of
+        ``_axpy_q``'s shapes for up to ``cap`` vectors. Returns (device?, the C arguments (rows, n, coef, x, q),
+        the host arrays those point into -- to be kept until the call is over)."""
         if _is_torch_cuda(rows):
             n = rows.numel()
             _check_like("coef", coef, self.torch_dtype, rows)
             _check_like("x", x, self.torch_dtype, rows)
             q = self._axpy_q(tuple(x.shape), tuple(coef.shape), n, cap)
             self._check_dev(n, rows)
-            rc = getattr(self.lib, fn + "_dev")(self.handle, rows.data_ptr(), n, coef.data_ptr(), x.data_ptr(), q,
-                                                flags, self._stream_of(rows))
-            self._dev_done(rc, rows, sync)
-            return True
+            return True, (rows.data_ptr(), n, coef.data_ptr(), x.data_ptr(), q), None
         r = _host(rows, np.int64).reshape(-1)
         cf = _host(coef, self.np_dtype)
         xs = _host(x, self.np_dtype)
         q = self._axpy_q(xs.shape, cf.shape, r.size, cap)
-        check(getattr(self.lib, fn)(self.handle, r.ctypes.data, r.size, cf.ctypes.data, xs.ctypes.data, q, flags),
-              self.handle)
-        return True
+        return False, (r.ctypes.data, r.size, cf.ctypes.data, xs.ctypes.data, q), (r, cf, xs)
 
     def updateRowsGrouped(self, rows, offsets, values, weights=None, deterministic: bool = False,
                           sync: bool = True, unordered: bool = False) -> bool:
@@ -807,6 +815,71 @@ class PartialMatrix(_Shard):
         scalars = (float(alpha), float(beta), float(l1), float(l2))
         return self._step_push("updateRowsFtrl", "glint_mat_push_rows_ftrl", state, PartialMatrix, rows, grads,
                                scalars, sync, offsets, weights)
+
+    def updateRowsAdagradBatch(self, state: "PartialMatrix", rows, coef, x, lr: float, eps: float = 1e-10,
+                               sync: bool = True) -> bool:
+        """Batched Adagrad row push (an extension; glint_mat_push_rows_adagrad_batch*): ``updateRowsAxpyBatch``
+        with ``updateRowsAdagrad``'s step where that call adds, for training a scoring layer whose gradient
+        rows are ``coef @ x``. ``rows``, ``coef``, ``x`` and ``q`` are ``updateRowsAxpyBatch``'s (``x`` of shape
+        (cols,) or (q, cols) with ``1 <= q <= 1024``, ``coef`` (n,) only with q == 1 or (n, q), host arrays or
+        device tensors, no order flags); ``state`` and the scalars are ``updateRowsAdagrad``'s. Per distinct
+        row of ``rows``: ``C`` = its coefficient rows added to +0 in push order, ``G = C @ x`` formed exactly
+        as ``updateRowsAxpyBatch`` forms it -- ``G[c]`` has the bits that call would add to column c -- then
+        one step with that ``G``, every operation rounded on its own, the state written first and the
+        weights after it: duplicates are coalesced, then one step is taken. The n x cols gradient is never
+        built. A row that is not named is touched in neither shard. Nothing is atomic and no run is split: a
+        row's bits depend on its own records, ``x``, its old weights and state and the scalars only, not on
+        the batch or on the alignment of ``coef`` or ``x``. They are NOT the bits of ``updateRowsAdagrad``
+        over explicit gradient rows: ``G`` lies within ``updateRowsAxpyBatch``'s bound of the exact product.
+        Errors as ``updateRowsAxpyBatch``: host arrays reject a message with a row outside the partition
+        before either shard changes (the lowest such record); device tensors skip such records and raise at
+        the weights shard's sync.
+
+        Use it wherever the gradient rows are ``coef @ x``: against ``updateRowsAxpyBatch`` into zeroed rows
+        of a scratch table, ``getRows`` and ``updateRowsAdagrad`` it saves one write and two reads of
+        ``distinct x cols`` values and one sort of the row list, and was faster on every shape measured (2^17
+        x 512, all three optimizers, both types, one run): 2.5 to 2.8 x at q = 8 and 1.7 to 2.0 x at q = 1024
+        on 2^12 distinct rows, 2.0 to 2.5 x and 1.3 to 1.4 x on 2^15, and 1.2 to 1.4 x on a Zipf-drawn list,
+        where the strictly ordered coefficient sum of the hottest row dominates both (DESIGN.md "Batched
+        optimizer row pushes")."""
+        return self._step_batch("updateRowsAdagradBatch", "glint_mat_push_rows_adagrad_batch", state, rows, coef, x,
+                                (float(lr), float(eps)), sync)
+
+    def updateRowsAdamBatch(self, state: "PartialMatrix", rows, coef, x, lr: float, step: int, beta1: float = 0.9,
+                            beta2: float = 0.999, eps: float = 1e-8, sync: bool = True) -> bool:
+        """Batched Adam row push (an extension; glint_mat_push_rows_adam_batch*): ``updateRowsAdagradBatch``'s
+        operands, product, order, errors and guidance with ``updateRowsAdam``'s lazy step, ``state`` (both
+        moments packed in ``2 * cols`` columns; ``m``, then ``v``, then the weights are written) and scalars."""
+        scalars = (float(lr), float(beta1), float(beta2), float(eps), int(step))
+        return self._step_batch("updateRowsAdamBatch", "glint_mat_push_rows_adam_batch", state, rows, coef, x, scalars,
+                                sync)
+
+    def updateRowsFtrlBatch(self, state: "PartialMatrix", rows, coef, x, alpha: float, beta: float = 1.0,
+                            l1: float = 0.0, l2: float = 0.0, sync: bool = True) -> bool:
+        """Batched FTRL-proximal row push (an extension; glint_mat_push_rows_ftrl_batch*):
+        ``updateRowsAdagradBatch``'s operands, product, order, errors and guidance with ``updateRowsFtrl``'s
+        step, ``state`` (``z`` and ``n`` packed in ``2 * cols`` columns; ``z``, then ``n``, then the weights are
+        written) and scalars."""
+        scalars = (float(alpha), float(beta), float(l1), float(l2))
+        return self._step_batch("updateRowsFtrlBatch", "glint_mat_push_rows_ftrl_batch", state, rows, coef, x, scalars,
+                                sync)
+
+    def _step_batch(self, name: str, symbol: str, state, rows, coef, x, scalars: tuple, sync: bool) -> bool:
+        """What the batched optimizer row pushes share: method ``name`` calls ``symbol`` -- ``symbol + "_dev"``
+        for device tensors -- with the weights shard, the ``state`` shard, ``_axpy_call``'s rows, coefficients
+        and vectors (validated as there) and the step's ``scalars``."""
+        if not isinstance(state, PartialMatrix):
+            raise TypeError("state: expected a PartialMatrix")
+        if np.dtype(self.np_dtype).kind != "f":
+            raise TypeError(f"{name} needs a Float or Double shard, not {np.dtype(self.np_dtype).name}")
+        dev, args, _keep = self._axpy_args(rows, coef, x, N.GLINT_AXPY_BATCH_MAX_VECTORS)
+        if dev:
+            rc = getattr(self.lib, symbol + "_dev")(self.handle, state.handle, *args, *scalars, 0,
+                                                    self._stream_of(rows))
+            self._dev_done(rc, rows, sync)
+            return True
+        check(getattr(self.lib, symbol)(self.handle, state.handle, *args, *scalars, 0), self.handle)
+        return True
 
     def _axpy_q(self, xshape, cshape, n: int, cap: int) -> int:
         """q of updateRowsAxpy / updateRowsAxpyBatch (at most ``cap``) for vectors of shape ``xshape`` and

@@ -849,6 +849,53 @@ int glint_mat_pull_rows_dot_batch(glint_shard_t shard, const int64_t* rows, int6
 int glint_mat_push_rows_axpy_batch(glint_shard_t shard, const int64_t* rows, int64_t n, const void* coef,
                                    const void* x, int64_t q, int flags);
 
+/* Batched optimizer row pushes (extensions): glint_mat_push_rows_axpy_batch with an optimizer step where it
+ * adds -- the Adagrad, Adam or FTRL-proximal step of a scoring layer whose n x cols gradient is coef * x.
+ * That gradient is never built: the product and the step are one kernel. rows, n, coef, x, q and flags are
+ * glint_mat_push_rows_axpy_batch's (Float and Double matrix shards, 1 <= q <= GLINT_AXPY_BATCH_MAX_VECTORS,
+ * no flag); `state` and the hyper-parameters are those of glint_mat_push_rows_adagrad (a state of the
+ * weights' cols and pitch), glint_mat_push_rows_adam and glint_mat_push_rows_ftrl (two parts packed side by
+ * side in 2 * cols columns). For every distinct local row l the push names:
+ *   1. C[j] is step 1 of glint_mat_push_rows_axpy_batch, unchanged: the row's coefficient rows added to +0
+ *      in push order;
+ *   2. G[c] is its step 2, unchanged: the same slabs of K, the same matrix instructions in the same order,
+ *      accumulators starting at +0. G[c] carries the bits that call would add to column c of the row;
+ *   3. one step of the matching unbatched push's contract is taken per element with that G in the place of
+ *      the summed gradient, every operation rounded on its own in the shard's type (IEEE division and
+ *      square root, no fused multiply-add). The state parts are written first, in ascending order, and the
+ *      weights after them. Duplicates are coalesced before the step: a row takes one step per call.
+ * A row that is not named is touched in neither shard; only `cols` (state: 2 * cols) elements of a row are
+ * touched, never the pitch padding. Nothing is atomic and no run is split: a row's bits depend only on its
+ * own records, x, its old weights and state and the scalars -- not on the batch, on where the row falls in
+ * a tile, or on the alignment of coef or x. They are NOT the bits of the unbatched optimizer pushes over
+ * explicit gradient rows: G lies within glint_mat_push_rows_axpy_batch's stated bound of the exact product
+ * (the terms of its step 3 left out). Non-finite values follow IEEE through the product and the step.
+ * Use them wherever the gradient rows are coef * x: against glint_mat_push_rows_axpy_batch into zeroed rows
+ * of a scratch shard, glint_mat_pull_rows and the unbatched push they save one write and two reads of
+ * distinct x cols values and one sort of the row list, and were faster on every shape measured (2^17 x 512,
+ * the three optimizers, both types, device calls, one run): 2.5 to 2.8 x at q = 8 and 1.7 to 2.0 x at
+ * q = 1024 on 2^12 distinct rows, 2.0 to 2.5 x and 1.3 to 1.4 x on 2^15, and 1.2 to 1.4 x on 2^15 records
+ * drawn from a Zipf law, where the strictly ordered coefficient sum of the hottest row dominates both
+ * (DESIGN.md "Batched optimizer row pushes" has the numbers).
+ * Device scratch is glint_mat_push_rows_axpy_batch's, in the weights shard, whose error state and profile
+ * the call uses; the coefficient run-sum is counted under GLINT_K_PUSH_ROWS_AXPY and the stepping product
+ * under GLINT_K_PUSH_ROWS. Locks, views and stream order are the unbatched optimizer pushes'.
+ * Errors: GLINT_EINVAL for what the matching unbatched push refuses (coef standing where grads stood: a
+ * NULL, vector, Int or Long shard, a state that is the same shard, overlaps it, or has another type,
+ * partition or shape, a bad hyper-parameter, NULL rows or coef with n > 0) and for q < 1,
+ * q > GLINT_AXPY_BATCH_MAX_VECTORS, a NULL x with n > 0 or any flag. Every row is checked before anything is
+ * staged or applied: a row outside the partition returns GLINT_EOUTOFRANGE (the lowest such record in
+ * glint_shard_last_error(weights)) and neither shard changes. n == 0 launches nothing and returns GLINT_OK.
+ * Staged to the device: rows, coef and x in one block; nothing is copied back. */
+int glint_mat_push_rows_adagrad_batch(glint_shard_t weights, glint_shard_t state, const int64_t* rows, int64_t n,
+                                      const void* coef, const void* x, int64_t q, double lr, double eps, int flags);
+int glint_mat_push_rows_adam_batch(glint_shard_t weights, glint_shard_t state, const int64_t* rows, int64_t n,
+                                   const void* coef, const void* x, int64_t q, double lr, double beta1, double beta2,
+                                   double eps, int64_t step, int flags);
+int glint_mat_push_rows_ftrl_batch(glint_shard_t weights, glint_shard_t state, const int64_t* rows, int64_t n,
+                                   const void* coef, const void* x, int64_t q, double alpha, double beta, double l1,
+                                   double l2, int flags);
+
 /* Batched row mix pull (an extension): the third product of the batched trio, the gradient of
  * glint_mat_pull_rows_dot_batch's scores with respect to the caller's vectors -- Float and Double matrix
  * shards, 1 <= q <= GLINT_MIX_BATCH_MAX_VECTORS:
@@ -1022,6 +1069,23 @@ int glint_mat_push_rows_axpy_dev(glint_shard_t shard, const int64_t* rows, int64
  * element: the same bits either way. */
 int glint_mat_push_rows_axpy_batch_dev(glint_shard_t shard, const int64_t* rows, int64_t n, const void* coef,
                                        const void* x, int64_t q, int flags, void* stream);
+
+/* glint_mat_push_rows_adagrad_batch, _adam_batch and _ftrl_batch, device-resident: the same steps with the
+ * same bits, stream-ordered on `stream` with no host synchronisation, after both shards' host-pointer work;
+ * both shards are marked for their next sync: the front end's launches, one coefficient run-sum launch and
+ * one launch of the stepping product. A record whose row lies outside the partition is skipped -- its
+ * coefficients reach no row -- and is reported by glint_shard_sync(weights, ...) as the lowest such record
+ * index; every other row is stepped. x and coef are read by 16 B when they allow it, else element by
+ * element: the same bits either way. */
+int glint_mat_push_rows_adagrad_batch_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows, int64_t n,
+                                          const void* coef, const void* x, int64_t q, double lr, double eps, int flags,
+                                          void* stream);
+int glint_mat_push_rows_adam_batch_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows, int64_t n,
+                                       const void* coef, const void* x, int64_t q, double lr, double beta1,
+                                       double beta2, double eps, int64_t step, int flags, void* stream);
+int glint_mat_push_rows_ftrl_batch_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows, int64_t n,
+                                       const void* coef, const void* x, int64_t q, double alpha, double beta,
+                                       double l1, double l2, int flags, void* stream);
 
 /* glint_mat_pull_rows_mix_batch, device-resident: the same answer with the same bits, stream-ordered on
  * `stream` with no host synchronisation: one product launch and, with more than one chunk, one reduce
