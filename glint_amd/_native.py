@@ -97,6 +97,9 @@ SIGNATURES = {
                                             C.c_double, _I]),
     "glint_mat_push_rows_ftrl_batch_dev": (_I, [_P, _P, _P, _I64, _P, _P, _I64, C.c_double, C.c_double, C.c_double,
                                                 C.c_double, _I, _P]),
+    "glint_mat_push_rows_adagrad_rowwise_batch": (_I, [_P, _P, _P, _I64, _P, _P, _I64, C.c_double, C.c_double, _I]),
+    "glint_mat_push_rows_adagrad_rowwise_batch_dev": (_I, [_P, _P, _P, _I64, _P, _P, _I64, C.c_double, C.c_double, _I,
+                                                           _P]),
     "glint_mat_push_rows_adagrad_rowwise": (_I, [_P, _P, _P, _P, _I64, C.c_double, C.c_double]),
     "glint_mat_push_rows_adagrad_rowwise_dev": (_I, [_P, _P, _P, _P, _I64, C.c_double, C.c_double, _P]),
     "glint_mat_push_rows_adagrad_grouped": (_I, [_P, _P, _P, _I64, _P, _I64, _P, _P, C.c_double, C.c_double]),

@@ -23,7 +23,9 @@ Mirrors the reference's client factory and asynchronous models, minus the Akka t
   of this matrix and of a second one that holds the accumulators, on the shards
   (PartialMatrix.updateRowsAdagrad).
 * ``BigMatrix.pushAdagradRowwise`` -- an extension: row-wise Adagrad, one accumulator per row held in a
-  ``BigVector`` with this matrix's partitioner (PartialMatrix.updateRowsAdagradRowwise).
+  ``BigVector`` with this matrix's partitioner (PartialMatrix.updateRowsAdagradRowwise);
+  ``BigMatrix.pushAdagradRowwiseBatch`` takes that step with ``pushAxpyBatch``'s product
+  (PartialMatrix.updateRowsAdagradRowwiseBatch).
 * ``BigMatrix.pushAdam`` -- an extension: the same with one lazy Adam step, the second matrix holding both
   moments of a row side by side in ``2 * cols`` columns (PartialMatrix.updateRowsAdam).
 * ``BigMatrix.pushFtrl`` -- an extension: the same with one FTRL-proximal step, the second matrix holding
@@ -411,11 +413,13 @@ class BigMatrix(_InitMixin):
                                      lambda sh, st, r, c, xs: sh.updateRowsFtrlBatch(st, r, c, xs, alpha, beta, l1,
                                                                                      l2))
 
-    def _push_step_batch(self, state, state_cols_factor: int, message: str, rows, coef, x, call) -> bool:
+    def _push_step_batch(self, state, state_cols_factor: int, message: str, rows, coef, x, call,
+                         kind=None) -> bool:
         """What the batched optimizer row pushes share: ``state`` validated as ``_push_step`` validates a
-        matrix state, the records bucketed as ``_push_axpy`` buckets them, and one ``call(shard, its state
-        shard, its rows, their coefficient rows, x)`` per non-empty partition, in the caller's order."""
-        self._check_state(state, BigMatrix, state_cols_factor, message)
+        state of class ``kind`` (a BigMatrix unless given: the row-wise push's is a BigVector), the records
+        bucketed as ``_push_axpy`` buckets them, and one ``call(shard, its state shard, its rows, their
+        coefficient rows, x)`` per non-empty partition, in the caller's order."""
+        self._check_state(state, kind or BigMatrix, state_cols_factor, message)
         for p, sh, r, c, xs in self._axpy_buckets(rows, coef, x):
             call(sh, state.shards[p], r, c, xs)
         return True
@@ -437,6 +441,26 @@ class BigMatrix(_InitMixin):
                                "and dtype", rows, grads,
                                lambda sh, st, r, g, **kw: sh.updateRowsAdagradRowwise(st, r, g, lr, eps, **kw),
                                offsets, weights)
+
+    def pushAdagradRowwiseBatch(self, state: "BigVector", rows, coef, x, lr: float, eps: float = 1e-10) -> bool:
+        """Batched row-wise Adagrad row push (an extension): ``pushAdagradBatch``'s operands, product,
+        validation and bucketing with ``pushAdagradRowwise``'s step and ``state`` -- a BigVector with the same
+        partitioner, ``size == rows`` and dtype, one accumulator per row -- so neither the gradient rows
+        ``coef @ x`` nor a table of state is ever built. Per distinct row: its coefficient rows are summed in
+        the caller's order, ``G`` = that sum times ``x`` with ``pushAxpyBatch``'s bits, then ``state += sum(G *
+        G) / cols`` and ``weights -= (lr / (sqrt(state) + eps)) * G`` on the shard that holds the row
+        (PartialMatrix.updateRowsAdagradRowwiseBatch, which states the sum's order: it is not
+        ``pushAdagradRowwise``'s). ``state``, the shapes and -- by the partitioner -- every row are validated
+        before any shard is called; one shard call per non-empty partition, with its rows and coefficient rows
+        in the caller's order, that partition's state shard and the same ``x``. A row lives in one partition
+        and its bits depend on its own records, ``x``, its old weights and accumulator and the scalars only,
+        so the answer does not depend on how the matrix is partitioned. On a shard it was 1.2 to 2.8 x faster than ``pushAxpyBatch`` into a
+        scratch table, ``pull`` and ``pushAdagradRowwise`` up to 256 vectors on the shapes measured, and slower
+        (0.8 to 0.9 x) on 2^15 distinct rows at 1024 vectors (DESIGN.md "Batched row-wise Adagrad push")."""
+        return self._push_step_batch(state, 0, "state: expected a vector with this matrix's partitioner, rows "
+                                     "and dtype", rows, coef, x,
+                                     lambda sh, st, r, c, xs: sh.updateRowsAdagradRowwiseBatch(st, r, c, xs, lr, eps),
+                                     BigVector)
 
     def pushAdam(self, state: "BigMatrix", rows, grads, lr: float, step: int, beta1: float = 0.9,
                  beta2: float = 0.999, eps: float = 1e-8, *, offsets=None, weights=None) -> bool:

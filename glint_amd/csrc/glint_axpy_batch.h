@@ -1,9 +1,9 @@
 // glint_axpy_batch.h -- the product t = Cs[tile] * x[:, pass] of the batched row axpy push
-// (glint_rowaxpy_batch.hip) and of the batched optimizer row pushes (glint_rowstep_batch.hip): operand B's
-// LDS layout, the wave's accumulators with the matrix instructions of one slab, and the two-slab pipeline
-// around them. Both kernels form the product here, with the same slabs of K and the same instructions in the
-// same order on accumulators that start at +0, which is what makes t's bits the same in both
-// (include/glint_gpu.h); they differ in what their epilogue does with t.
+// (glint_rowaxpy_batch.hip) and of the batched optimizer row pushes (glint_rowstep_batch.hip,
+// glint_rowwise_batch.hip): operand B's LDS layout, the wave's accumulators with the matrix instructions of
+// one slab, and the two-slab pipeline around them. All their kernels form the product here, with the same slabs of K and the same instructions in the
+// same order on accumulators that start at +0, which is what makes t's bits the same in all of
+// them (include/glint_gpu.h); they differ in what their epilogue does with t.
 #pragma once
 #include "glint_device.h"
 #include "glint_host.h"
@@ -166,6 +166,16 @@ __device__ __forceinline__ void ab_product(AbMma<V>& mma, unsigned char (*lds)[k
   }
   early();
   mma.slab(lds[(nslab - 1) & 1], wave, lane);
+}
+
+// Bytes of s->d_det that axpy_batch_front lays out for n records and q vectors, a multiple of 128:
+// rows_front_bytes(n), then Cs -- min(n, part.size) lines of q rounded up to a whole slab of K. A call that
+// keeps scratch of its own behind Cs grows s->d_det to the sum first and finds the front's pointers unmoved.
+template <typename V>
+inline size_t axpy_batch_bytes(const glint_shard* s, i64 n, i64 q) {
+  const i64 qp = (q + Xb<V>::KS - 1) / Xb<V>::KS * Xb<V>::KS;
+  const i64 most = n < (i64)s->part.size ? n : (i64)s->part.size;
+  return rows_front_bytes(n) + (size_t)most * (size_t)qp * sizeof(V);
 }
 
 // The product's grid: one workgroup per (tile of 128 of at most `most` items, pass of 64 columns), the pass

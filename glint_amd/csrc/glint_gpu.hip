@@ -1793,7 +1793,7 @@ extern "C" {
 // 0.22.0: glint_mat_push_rows_axpy_batch / _dev (batched row axpy push)
 // 0.23.0: glint_mat_pull_rows_mix_batch / _dev (batched row mix pull)
 // 0.24.0: glint_mat_push_rows_adagrad_batch / _adam_batch / _ftrl_batch / _dev (batched optimizer row pushes)
-int glint_version(void) { return 2400; }
+int glint_version(void) { return 2500; }
 
 int glint_wire_supported(int dtype, int wire) { return wire_supported(dtype, wire) ? 1 : 0; }
 
@@ -2317,6 +2317,14 @@ int glint_mat_push_rows_adagrad_batch_dev(glint_shard_t weights, glint_shard_t s
   const int step_rc = push_adagrad_args(weights, state, rows, coef, n, lr, eps);
   return step_batch_push_dev(weights, state, push_step_batch_args(step_rc, x, n, q, flags), rows, n, coef, x, q, stream,
                              push_rows_adagrad_batch<float>, push_rows_adagrad_batch<double>, lr, eps);
+}
+
+int glint_mat_push_rows_adagrad_rowwise_batch_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows,
+                                                  int64_t n, const void* coef, const void* x, int64_t q, double lr,
+                                                  double eps, int flags, void* stream) {
+  const int step_rc = push_adagrad_rowwise_args(weights, state, rows, coef, n, lr, eps);
+  return step_batch_push_dev(weights, state, push_step_batch_args(step_rc, x, n, q, flags), rows, n, coef, x, q, stream,
+                             push_rows_adagrad_rowwise_batch<float>, push_rows_adagrad_rowwise_batch<double>, lr, eps);
 }
 
 int glint_mat_push_rows_adam_batch_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows, int64_t n,
@@ -3195,7 +3203,7 @@ int group_step_push_host(glint_shard* w, glint_shard* s, int args_rc, const int6
 }
 
 // The host-pointer entry of a batched optimizer row push (glint_mat_push_rows_adagrad_batch, _adam_batch,
-// _ftrl_batch) whose argument check gave args_rc: step_push_host's locks, row check (against the weights
+// _ftrl_batch, _adagrad_rowwise_batch) whose argument check gave args_rc: step_push_host's locks, row check (against the weights
 // shard, before anything is staged: a rejected message changes neither shard) and stream order, around
 // glint_mat_push_rows_axpy_batch's staging -- rows, coef and x in one block, every section 256-B aligned,
 // n * 8 bytes + n * q + q * cols values, never n * cols. The call ends synchronised. pf, pd and k as
@@ -3655,6 +3663,14 @@ int glint_mat_push_rows_adagrad_batch(glint_shard_t weights, glint_shard_t state
   const int step_rc = push_adagrad_args(weights, state, rows, coef, n, lr, eps);
   return step_batch_push_host(weights, state, push_step_batch_args(step_rc, x, n, q, flags), rows, n, coef, x, q,
                               push_rows_adagrad_batch<float>, push_rows_adagrad_batch<double>, lr, eps);
+}
+
+int glint_mat_push_rows_adagrad_rowwise_batch(glint_shard_t weights, glint_shard_t state, const int64_t* rows,
+                                              int64_t n, const void* coef, const void* x, int64_t q, double lr,
+                                              double eps, int flags) {
+  const int step_rc = push_adagrad_rowwise_args(weights, state, rows, coef, n, lr, eps);
+  return step_batch_push_host(weights, state, push_step_batch_args(step_rc, x, n, q, flags), rows, n, coef, x, q,
+                              push_rows_adagrad_rowwise_batch<float>, push_rows_adagrad_rowwise_batch<double>, lr, eps);
 }
 
 int glint_mat_push_rows_adam_batch(glint_shard_t weights, glint_shard_t state, const int64_t* rows, int64_t n,

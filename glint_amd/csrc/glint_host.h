@@ -558,6 +558,18 @@ int push_rows_adam_batch(glint_shard* weights, glint_shard* state, const i64* ro
 template <typename V>
 int push_rows_ftrl_batch(glint_shard* weights, glint_shard* state, const i64* rows, i64 n, const void* coef,
                          const void* x, i64 q, double alpha, double beta, double l1, double l2, hipStream_t st);
+// batched row-wise Adagrad row push (glint_rowwise_batch.hip), instantiated for float and double:
+// push_rows_adagrad_batch's rows, coef, x and q with push_rows_adagrad_rowwise's vector `state` and scalars.
+// Per distinct row, G = push_rows_axpy_batch's product with its bits, ss = the sum of its squares in the order
+// include/glint_gpu.h fixes (the accumulators' layout: NOT the row dot pull's), then rowwise_scalars and
+// rowwise_update of glint_steps.h. Rows outside the partition are skipped and recorded in err_of(weights).
+// Scratch, error state and profile are the weights shard's: axpy_batch_bytes, then min(n, part.size) *
+// (ceil(cols / 64) + 1) values, grown before anything is launched. axpy_batch_front's launches, then two
+// product launches (both counted under GLINT_K_PUSH_ROWS) on st, no host synchronisation; under both shards'
+// locks.
+template <typename V>
+int push_rows_adagrad_rowwise_batch(glint_shard* weights, glint_shard* state, const i64* rows, i64 n, const void* coef,
+                                    const void* x, i64 q, double lr, double eps, hipStream_t st);
 // Adagrad row push (glint_rowadagrad.hip), instantiated for float and double: per distinct row of the
 // push, G = its gradient rows (grads n x cols, dense, device pointer) added to +0 in push order, then
 // state row += G * G and weights row -= (lr * G) / (sqrt(state row) + eps), in the order

@@ -117,7 +117,7 @@ int axpy_batch_front(glint_shard* s, const i64* rows, i64 n, const void* coef, i
   const i64 qp = (q + KS - 1) / KS * KS;
   const i64 most = n < (i64)s->part.size ? n : (i64)s->part.size;  // distinct rows, at most
   const size_t front = rows_front_bytes(n);
-  int rc = grow(&s->d_det, &s->det_bytes, front + (size_t)most * (size_t)qp * sizeof(V));
+  int rc = grow(&s->d_det, &s->det_bytes, axpy_batch_bytes<V>(s, n, q));  // a no-op when the caller grew it
   if (rc) return rc;
   RowsFront f;
   rc = rows_front(s, rows, n, GLINT_PUSH_DETERMINISTIC, st, &f);  // finds its scratch grown already

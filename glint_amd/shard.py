@@ -845,6 +845,37 @@ class PartialMatrix(_Shard):
         return self._step_batch("updateRowsAdagradBatch", "glint_mat_push_rows_adagrad_batch", state, rows, coef, x,
                                 (float(lr), float(eps)), sync)
 
+    def updateRowsAdagradRowwiseBatch(self, state: "PartialVector", rows, coef, x, lr: float, eps: float = 1e-10,
+                                      sync: bool = True) -> bool:
+        """Batched row-wise Adagrad row push (an extension; glint_mat_push_rows_adagrad_rowwise_batch*):
+        ``updateRowsAdagradBatch``'s operands and product with ``updateRowsAdagradRowwise``'s step and ``state``
+        -- a PartialVector of the same type, device and partition, one accumulator per row -- for a scoring
+        layer whose gradient rows are ``coef @ x`` and whose table is too large for a second table of state.
+        Per distinct row of ``rows``: ``C`` = its coefficient rows added to +0 in push order, ``G = C @ x``
+        with ``updateRowsAxpyBatch``'s bits, ``ss`` = the sum of ``G * G`` in the order of the product's
+        accumulators (include/glint_gpu.h states it; it is NOT ``getRowsDot``'s order, which
+        ``updateRowsAdagradRowwise`` uses), then ``state += ss / cols`` and ``weights -= (lr / (sqrt(state) +
+        eps)) * G``, every operation rounded on its own: duplicates are coalesced, then one step is taken.
+        Neither the n x cols gradient nor a scratch table is built: the product is formed twice, once for
+        ``ss`` and once for the update. A row that is not named is touched in neither shard. Nothing is atomic
+        and no run is split: a row's bits depend on its own records, ``x``, its old weights and accumulator
+        and the scalars only, not on the batch or on the alignment of ``coef`` or ``x``. Columns past ``cols``
+        never reach ``ss``: an infinite coefficient gives an infinite accumulator, not a NaN. Errors as
+        ``updateRowsAdagradBatch``: host arrays reject a message with a row outside the partition before
+        either shard changes (the lowest such record); device tensors skip such records and raise at the
+        weights shard's sync.
+
+        Use it where the gradient rows are ``coef @ x`` and the state must stay a vector: against
+        ``updateRowsAxpyBatch`` into zeroed rows of a scratch table, ``getRows`` and ``updateRowsAdagradRowwise``
+        it needs no scratch table and one sort of the row list, and forms the product twice. Measured (2^17 x
+        512, both types, one run): 2.5 to 2.8 x faster at q = 8 and 64 and 1.2 to 1.5 x at q = 1024 on 2^12
+        distinct rows; 1.9 to 2.7 x at q = 8 and 64 and 1.2 to 1.4 x at q = 256 on 2^15; 1.3 to 1.4 x up to q =
+        256 and 1.0 to 1.1 x at q = 1024 on a Zipf-drawn list. It was slower on 2^15 distinct rows at q = 1024
+        (0.87 x Float, 0.78 x Double), and on the Zipf list at q = 1024 in Double its lead (1.03 x) barely
+        exceeded the baseline's spread (DESIGN.md "Batched row-wise Adagrad push")."""
+        return self._step_batch("updateRowsAdagradRowwiseBatch", "glint_mat_push_rows_adagrad_rowwise_batch", state,
+                                rows, coef, x, (float(lr), float(eps)), sync, PartialVector)
+
     def updateRowsAdamBatch(self, state: "PartialMatrix", rows, coef, x, lr: float, step: int, beta1: float = 0.9,
                             beta2: float = 0.999, eps: float = 1e-8, sync: bool = True) -> bool:
         """Batched Adam row push (an extension; glint_mat_push_rows_adam_batch*): ``updateRowsAdagradBatch``'s
@@ -864,12 +895,15 @@ class PartialMatrix(_Shard):
         return self._step_batch("updateRowsFtrlBatch", "glint_mat_push_rows_ftrl_batch", state, rows, coef, x, scalars,
                                 sync)
 
-    def _step_batch(self, name: str, symbol: str, state, rows, coef, x, scalars: tuple, sync: bool) -> bool:
+    def _step_batch(self, name: str, symbol: str, state, rows, coef, x, scalars: tuple, sync: bool,
+                    state_cls=None) -> bool:
         """What the batched optimizer row pushes share: method ``name`` calls ``symbol`` -- ``symbol + "_dev"``
-        for device tensors -- with the weights shard, the ``state`` shard, ``_axpy_call``'s rows, coefficients
+        for device tensors -- with the weights shard, the ``state`` shard of class ``state_cls`` (a
+        PartialMatrix unless given: the row-wise push's is a PartialVector), ``_axpy_call``'s rows, coefficients
         and vectors (validated as there) and the step's ``scalars``."""
-        if not isinstance(state, PartialMatrix):
-            raise TypeError("state: expected a PartialMatrix")
+        state_cls = state_cls or PartialMatrix
+        if not isinstance(state, state_cls):
+            raise TypeError(f"state: expected a {state_cls.__name__}")
         if np.dtype(self.np_dtype).kind != "f":
             raise TypeError(f"{name} needs a Float or Double shard, not {np.dtype(self.np_dtype).name}")
         dev, args, _keep = self._axpy_args(rows, coef, x, N.GLINT_AXPY_BATCH_MAX_VECTORS)

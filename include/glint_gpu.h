@@ -896,6 +896,70 @@ int glint_mat_push_rows_ftrl_batch(glint_shard_t weights, glint_shard_t state, c
                                    const void* coef, const void* x, int64_t q, double alpha, double beta, double l1,
                                    double l2, int flags);
 
+/* Batched row-wise Adagrad row push (an extension): the batched optimizer row pushes' fourth member, for a
+ * table whose optimizer state is one accumulator per row. rows, n, coef, x, q and flags are
+ * glint_mat_push_rows_adagrad_batch's (Float and Double matrix shards, 1 <= q <= GLINT_AXPY_BATCH_MAX_VECTORS,
+ * no flag); `state`, lr and eps are glint_mat_push_rows_adagrad_rowwise's: a vector shard of the weights'
+ * dtype, device, size and partition. The n x cols gradient coef * x is never built, and no table of a
+ * row's width is needed beside the weights. For every distinct local row l the push names:
+ *   1. C[j] is step 1 of glint_mat_push_rows_axpy_batch, unchanged: the row's coefficient rows added to +0
+ *      in push order;
+ *   2. G[c] is its step 2, unchanged: the same slabs of K, the same matrix instructions in the same order,
+ *      accumulators starting at +0. G[c] carries the bits that call would add to column c of the row. The
+ *      call forms G twice, once for step 3 and once for step 5, both times with that one product: the two
+ *      hold the same bits;
+ *   3. ss, the sum of the squares of G, a function of (type, cols, G) only, in the order of the product's
+ *      accumulators -- NOT the row dot pull's order, which glint_mat_push_rows_adagrad_rowwise uses. Let
+ *      W = 32 (Float) or 16 (Double) and B = 64 / W. For pass p over columns [64 p, 64 p + 64) and sub-lane
+ *      t in [0, W): a_t = +0; for b = 0 .. B - 1 in ascending order, with c = 64 p + W b + t, if c < cols
+ *      then a_t = a_t + (G[c] * G[c]), the product rounded before the add (no fused multiply-add); then the
+ *      xor butterfly a_t = a_t + a_(t xor d) for d = W / 2, ..., 1, after which every a_t holds the same
+ *      bits (IEEE addition commutes): partial_p. ss = +0, then ss = ss + partial_p for p ascending. A
+ *      column c >= cols contributes nothing, whatever the product left in its place (with an infinite
+ *      coefficient, inf * 0 = NaN: it is left out by a select, never multiplied by zero);
+ *   4. the row scalars of glint_mat_push_rows_adagrad_rowwise's step 3 with that ss, h = state[l] as it was
+ *      before the call and C = cols rounded once to V:
+ *        s = ss / C;  h' = h + s;  r = sqrt(h');  d = r + eps_V;  k = lr_V / d
+ *   5. per column its step 4:  p = k * G[c];  w' = w - p. h' is stored to state[l] once, w' to weights[l][c].
+ * Duplicates are coalesced, then one step is taken. A row that is not named is touched in neither shard;
+ * only `cols` elements of a weights row are touched, never the pitch padding. Nothing is atomic and no run
+ * is split: a row's bits depend only on its own records, x, its old weights and accumulator and the scalars
+ * -- not on the batch, on where the row falls in a tile, or on the alignment of coef or x. They are NOT the
+ * bits of glint_mat_push_rows_adagrad_rowwise over explicit gradient rows: G lies within
+ * glint_mat_push_rows_axpy_batch's bound of the exact product, and ss has its own order. Non-finite values
+ * follow IEEE through the product and the step: the row is coupled, so one NaN in G makes h' and every w'
+ * of that row NaN, and never reaches another row.
+ * Use it where the gradient rows are coef * x and the state must stay a vector: against
+ * glint_mat_push_rows_axpy_batch into zeroed rows of a scratch shard, glint_mat_pull_rows and
+ * glint_mat_push_rows_adagrad_rowwise it needs no scratch table and one sort of the row list, at the price of
+ * forming the product twice. Measured (2^17 x 512, both types, device calls, one run): 2.5 to 2.8 x faster at
+ * q = 8 and 64 and 1.2 to 1.5 x at q = 1024 on 2^12 distinct rows; 1.9 to 2.7 x at q = 8 and 64 and 1.2 to 1.4 x at
+ * q = 256 on 2^15 distinct rows; 1.3 to 1.4 x up to q = 256 and 1.0 to 1.1 x at q = 1024 on 2^15 records drawn
+ * from a Zipf law, where the strictly ordered coefficient sum of the hottest row dominates both. It was SLOWER on
+ * 2^15 distinct rows at q = 1024: 0.87 x (Float) and 0.78 x (Double), the second product costing more than the
+ * scratch table's traffic; and on the Zipf list at q = 1024 in Double its lead (1.03 x) barely exceeded the
+ * baseline's spread. Against glint_mat_push_rows_adagrad_batch with a full table of state it took the same time within 8 %
+ * up to q = 64 and 1.1 to 1.7 x the time at q = 1024 (DESIGN.md "Batched row-wise Adagrad push" has the
+ * numbers).
+ * Device scratch, in the weights shard: glint_mat_push_rows_axpy_batch's, then min(n, rows of the shard) *
+ * (ceil(cols / 64) + 1) values -- the partial sums of step 3 and a copy of the old accumulators, so that no
+ * workgroup reads a state element another one writes. The whole is grown before anything is launched; when
+ * it cannot be, the call fails with GLINT_ENOMEM and applies nothing. Error state and profile are the weights
+ * shard's: the coefficient run-sum is counted under GLINT_K_PUSH_ROWS_AXPY and the two product launches under
+ * GLINT_K_PUSH_ROWS; nothing is recorded on `state`. Locks, views and stream order are
+ * glint_mat_push_rows_adagrad_rowwise's: the call is ordered after both shards' earlier work, the vector
+ * shard's ring entries and open batch included.
+ * Errors: GLINT_EINVAL for what glint_mat_push_rows_adagrad_rowwise refuses (coef standing where grads
+ * stood: a NULL, vector, Int or Long `weights`, a NULL `state`, one that is a matrix, differs in dtype,
+ * device, size or partition or shares memory with the weights, a NaN lr, !(eps >= 0), NULL rows or coef with
+ * n > 0) and for q < 1, q > GLINT_AXPY_BATCH_MAX_VECTORS, a NULL x with n > 0 or any flag. Every row is
+ * checked before anything is staged or applied: a row outside the partition returns GLINT_EOUTOFRANGE (the
+ * lowest such record in glint_shard_last_error(weights)) and neither shard changes. n == 0 launches nothing
+ * and returns GLINT_OK. Staged to the device: rows, coef and x in one block; nothing is copied back. */
+int glint_mat_push_rows_adagrad_rowwise_batch(glint_shard_t weights, glint_shard_t state, const int64_t* rows,
+                                              int64_t n, const void* coef, const void* x, int64_t q, double lr,
+                                              double eps, int flags);
+
 /* Batched row mix pull (an extension): the third product of the batched trio, the gradient of
  * glint_mat_pull_rows_dot_batch's scores with respect to the caller's vectors -- Float and Double matrix
  * shards, 1 <= q <= GLINT_MIX_BATCH_MAX_VECTORS:
@@ -1086,6 +1150,17 @@ int glint_mat_push_rows_adam_batch_dev(glint_shard_t weights, glint_shard_t stat
 int glint_mat_push_rows_ftrl_batch_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows, int64_t n,
                                        const void* coef, const void* x, int64_t q, double alpha, double beta,
                                        double l1, double l2, int flags, void* stream);
+
+/* glint_mat_push_rows_adagrad_rowwise_batch, device-resident: the same step with the same bits,
+ * stream-ordered on `stream` with no host synchronisation, after both shards' host-pointer work; both shards
+ * are marked for their next sync: the front end's launches, one coefficient run-sum launch and the two
+ * product launches. A record whose row lies outside the partition is skipped -- its coefficients reach no
+ * row -- and is reported by glint_shard_sync(weights, ...) as the lowest such record index; every other row
+ * is stepped. x and coef are read by 16 B when they allow it, else element by element: the same bits
+ * either way. A slab that has views is GLINT_EINVAL for either shard. */
+int glint_mat_push_rows_adagrad_rowwise_batch_dev(glint_shard_t weights, glint_shard_t state, const int64_t* rows,
+                                                  int64_t n, const void* coef, const void* x, int64_t q, double lr,
+                                                  double eps, int flags, void* stream);
 
 /* glint_mat_pull_rows_mix_batch, device-resident: the same answer with the same bits, stream-ordered on
  * `stream` with no host synchronisation: one product launch and, with more than one chunk, one reduce
